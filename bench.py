@@ -16,6 +16,10 @@ one all-reduce of {episodes, sum of returns, sum of squares} + the step counters
 `value` counts simulator.step calls of the planner (tree + rollout) plus those of the belief
 update, exactly as BASELINE.md defines the metric; inputs (priors, particles, trees) are resident
 in HBM before the timed region.
+
+A plain run sets up, warms up, times the K steps and prints the line; `--full` adds the CPU baseline
+(`cpu_baseline`, minutes of oracle processes after the timed steps).  `--dump-outputs DIR` writes what
+the last timed step computed as DIR/*.npy; the inputs are seeded, so the same arguments give the same inputs.
 """
 import argparse
 import datetime
@@ -252,6 +256,35 @@ def gather_per_rank(dist, torch, world, values):
     return [p.tolist() for p in parts]
 
 
+DUMP_SLOTS = 32768   # slots whose last-step records --dump-outputs writes (at most 53 doubles each with its index: 14 MB); all of them when there are fewer
+DUMP_SEED = 0
+# the fields of the per-slot step record that the timed path fills with tracing off: the search kernels write the tree's size and depth
+# and the root's visit counts and Q values, the belief update its count (rejection attempts, or -1).  run / episode / t / action / state /
+# obs / terminal / reward and the belief checksum are written only by a traced run, so a bench run leaves them zero and they are not dumped.
+DUMP_FIELDS = ("n_nodes", "tree_depth", "root_n", "root_q", "update_count")
+
+
+def dump_outputs(path, eng, c0, c1, rets, belief):
+    """--dump-outputs: what a caller of the timed path (fba_run_ticks) receives after its last step, as float64 .npy files -- the
+    DUMP_FIELDS of that step's per-slot record (fba_last_step_info), plus the filter's total weight where an importance update writes
+    it, over a fixed, seeded sample of the slots; the running return sums; the timed region's step counters.  With several ranks,
+    rank 0's."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    info = eng.last_step_info()
+    pick = np.arange(len(info)) if len(info) <= DUMP_SLOTS else np.sort(
+        np.random.default_rng(DUMP_SEED).choice(len(info), DUMP_SLOTS, replace=False))
+    rec = info[pick]
+    fields = DUMP_FIELDS + (("weight_total",) if belief == "importance_sampling" else ())
+    arrays = {"slot_index": pick}
+    for name in fields:
+        arrays["last_step_" + name] = rec[name]
+    arrays["return_sums"] = rets    # {episodes finished, sum of returns, sum of squared returns} since the context was created
+    arrays["timed_counters"] = [c1.sim_steps - c0.sim_steps, c1.belief_steps - c0.belief_steps, c1.env_steps - c0.env_steps]
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a).astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -270,15 +303,21 @@ def main():
                     help="c4: iterations of the search loop per launch (slots advance on their own; 0 = lock-step ticks); default: the workload's")
     ap.add_argument("--tree-buckets", type=int, default=None,
                     help="c4: 64-byte node buckets per slot's search tree (fba_config.tree_buckets; 0 = 2 * (sims + 2), which no search can fill); default: the workload's")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline (cpu_baseline) after the timed steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64; see dump_outputs)")
     ap.add_argument("--cpu-cores", type=int, default=16,
-                    help="processes of the CPU baseline (a 1-GPU box's CPU share is 16 cores, whatever the affinity mask says)")
+                    help="--full: processes of the CPU baseline (a 1-GPU box's CPU share is 16 cores, whatever the affinity mask says)")
     ap.add_argument("--cpu-runs", type=int, default=None)
     ap.add_argument("--cpu-episodes", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--all-ranks-on-device", type=int, default=None,
                     help="rehearsal only: put every rank on this one GPU (a 1-GPU box cannot give each rank its own)")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.cpu_worker is not None:
         cpu_worker(args)
         return
@@ -460,7 +499,9 @@ def main():
             # what every rank did in the timed region (gathered over gloo): simulated steps, its own wall seconds, its slots
             "per_rank": {"steps": [r[0] for r in per_rank_rows], "seconds": [r[1] for r in per_rank_rows], "slots": [int(r[2]) for r in per_rank_rows]},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, eng, c0, c1, rets, w["belief"])
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -10,7 +10,7 @@ rm -rf $OUT && mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 B="python3 $R/bench.py"
 S="--steps 4 --warmup 0 --no-cpu-baseline"    # (warm-up 0: every search launch of the run is inside the bench line's own step count)
-timeout -k 10 400 $B > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout -k 10 400 $B --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o run -- $B --no-cpu-baseline > $OUT/stats.log 2>&1
 timeout -k 10 300 $B --belief importance_sampling --no-cpu-baseline > $OUT/bench_importance.json 2> $OUT/bench_importance.err
 timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o run -- $B $S > $OUT/fetch.log 2>&1
@@ -38,11 +38,11 @@ fi
 echo "[refresh] randline done"
 # the other BASELINE configs through the same bench.py (c4 apart: its steady state needs a warm-up past one whole first episode)
 for wl in c1 c3 c5; do
-  timeout -k 10 400 $B --workload $wl --steps 4 --warmup 1 > $OUT/bench_$wl.json 2> $OUT/bench_$wl.err || echo "[refresh] $wl failed"
+  timeout -k 10 400 $B --full --workload $wl --steps 4 --warmup 1 > $OUT/bench_$wl.json 2> $OUT/bench_$wl.err || echo "[refresh] $wl failed"
 done
 ( while sleep 60; do echo "[refresh] c4 running"; done ) &
 HB=$!
-timeout -k 10 900 $B --workload c4 --steps 10 --warmup 20 > $OUT/bench_c4.json 2> $OUT/bench_c4.err || echo "[refresh] c4 failed"
+timeout -k 10 900 $B --full --workload c4 --steps 10 --warmup 20 > $OUT/bench_c4.json 2> $OUT/bench_c4.err || echo "[refresh] c4 failed"
 kill $HB
 # C3's rejection kernel: traffic passes
 S3="--workload c3 --steps 4 --warmup 0 --no-cpu-baseline"
