@@ -1480,11 +1480,17 @@ int fba_create(const fba_config* cfg, fba_ctx** out)
     // shared prior tables -- 100-500 bytes instead of 191 KB (N = 7) -- where the importance filter is the plain one,
     // the run fits the record (one entry per belief update), the grid fits 3-bit coordinates and prior + j is exact in
     // fp32 for every count a run can reach (so a row read through the entries is bit for bit the dense row).
+    // The plain rejection filter (reject_hist_kernel) stores them too where its search is the bucket-tree one (hist2_flat_search: po-uct or
+    // random, at most 65536 simulations, a table whose keys fit -- the flat root sample exists there only); ts and the rest stay dense.
     P.hist = 0; P.hist_cap = 0; P.hist_row = 0; P.hist_base = nullptr; P.hist_alt = nullptr;
     P.hist_lds = nullptr; P.hist_rid_bytes = 0; P.hist_distinct = 0;
-    if (cfg->model == FBA_MODEL_BA_FACTORED && cfg->domain == FBA_DOM_GRIDWORLD && cfg->belief == FBA_BELIEF_IMPORTANCE &&
-        !cfg->dirichlet_regular && cfg->particles <= IS_MAX_CHUNKS * 256 && !std::getenv("FBA_IS_MULTI_MIN") &&
-        !std::getenv("FBA_DENSE_PARTICLES") && (long long)cfg->episodes * cfg->horizon <= HIST_MAX_CAP && cfg->size <= HIST_MAX_N) {
+    const bool hist_records_tree = std::getenv("FBA_HIST_TREE") && !std::strcmp(std::getenv("FBA_HIST_TREE"), "records");
+    const bool hist_flat = cfg->belief == FBA_BELIEF_REJECTION && !point && (cfg->planner == FBA_PLANNER_POUCT || cfg->planner == FBA_PLANNER_RANDOM) &&
+                           cfg->sims <= 65536 && !hist_records_tree &&
+                           (cfg->tree_buckets <= 0 || (long long)cfg->tree_buckets <= (1ll << 28) / (4ll * P.O) - 2);   // (fit, below)
+    const bool hist_weighted = cfg->belief == FBA_BELIEF_IMPORTANCE && cfg->particles <= IS_MAX_CHUNKS * 256 && !std::getenv("FBA_IS_MULTI_MIN");
+    if (cfg->model == FBA_MODEL_BA_FACTORED && cfg->domain == FBA_DOM_GRIDWORLD && (hist_weighted || hist_flat) &&
+        !cfg->dirichlet_regular && !std::getenv("FBA_DENSE_PARTICLES") && (long long)cfg->episodes * cfg->horizon <= HIST_MAX_CAP && cfg->size <= HIST_MAX_N) {
         const int cap = cfg->episodes * cfg->horizon;
         build_gridworld_alt_prior(c);
         std::vector<float> counts(c->prior.begin(), c->prior.begin() + c->fdesc.ncounts);
@@ -1579,7 +1585,7 @@ int fba_create(const fba_config* cfg, fba_ctx** out)
     // (search_hist_kernel), for A/B runs and for what does not fit.
     D.bkt = nullptr; D.bkt_lines = 0; D.s_root = nullptr; D.search_order = nullptr;
     size_t bkt_lines = 0;
-    const bool force_records = std::getenv("FBA_HIST_TREE") && !std::strcmp(std::getenv("FBA_HIST_TREE"), "records");
+    const bool force_records = hist_records_tree;
     if (P.hist && P.sims <= 65536 && !force_records) {
         long long buckets = cfg->tree_buckets > 0 ? cfg->tree_buckets : 2ll * (P.sims + 2);
         buckets = std::max(buckets, 8ll);
@@ -1601,7 +1607,9 @@ int fba_create(const fba_config* cfg, fba_ctx** out)
     }
 
     // slots
-    const size_t per_slot = (size_t)P.N * (2 * 8 + 8 + 4 * (MAXINC + 1) + ((P.reinvig || P.cheat) ? 4 : (P.incub ? 6 : (P.hist ? 1 : 2))) * (size_t)P.Cs * 4) +
+    // (per particle: two weights, a prefix sum and a side row, which a plain rejection filter of history records does not have, + its records)
+    const size_t per_particle_aux = (P.hist && P.belief == FBA_BELIEF_REJECTION) ? 0 : (size_t)(2 * 8 + 8 + 4 * (MAXINC + 1));
+    const size_t per_slot = (size_t)P.N * (per_particle_aux + ((P.reinvig || P.cheat) ? 4 : (P.incub ? 6 : (P.hist ? 1 : 2))) * (size_t)P.Cs * 4) +
                             (bkt_lines ? bkt_lines * 128 : (size_t)D.max_nodes * D.node_words * 4 + (size_t)hcap * hash_entry) + 1024;
     int E = cfg->slots;
     if (E <= 0) {
@@ -2426,6 +2434,10 @@ int fba_get_kernel_times(fba_ctx* c, fba_kernel_time* out)
             const uint64_t rec = (uint64_t)P.Cs * 4, rows = 4 * (uint64_t)(c->fdesc.FS + c->fdesc.FO);
             out[FBA_K_BELIEF_RS].bytes = attempts * (rec + rows) + particles * rec;
         }
+        // history particles (reject_hist_kernel): an attempt reads its source's two header words (8) and the entries
+        // of the real action, an accepted one is gathered -- its source record read (8 + 4 per entry) and written with the new entry
+        // (8 + 4 per entry + 4); `entries` counts the 4-byte entries of both (fba_state.h upd_entries); the Dirichlet rows come from LDS
+        if (P.hist) out[FBA_K_BELIEF_RS].bytes = attempts * 8 + particles * 20 + entries * 4;
     } else {
         out[FBA_K_BELIEF_IS].units = particles;
         out[FBA_K_BELIEF_IS].bytes = particles * (32 + Rt + Ro) + particles * (8 + 2 * Pb);

@@ -272,8 +272,9 @@ __device__ __forceinline__ void gather_records_side(float* __restrict__ dst, con
 // History particles (fba_device.h): output record j = source record s_src[j] -- its state replaced, its structure
 // bits kept -- with the source particle's pending entry (side row {new state, entry}) inserted as word `ins`, the
 // end of its action's group: the `len` entries behind it move up by one.  A power-of-two group of lanes moves
-// one record in 16-byte pieces.
-template <class IDX>
+// one record in 16-byte pieces.  SIDE_BY_OUT: the side row is the OUTPUT record's (row j, not row s_src[j]) -- the rejection update, whose
+// accepted attempts each carry a step of their own while one source may be drawn by several of them.
+template <class IDX, bool SIDE_BY_OUT = false>
 __device__ __forceinline__ void gather_hist_records(float* __restrict__ dst, const float* __restrict__ src, const IDX* s_src,
                                                     const int32_t* __restrict__ side, int len, int ins, int m, int C4, int group, int nthreads,
                                                     int C4d = 0)   // C4 / C4d: 16-byte pieces between source / destination records (hist_stride)
@@ -296,7 +297,7 @@ __device__ __forceinline__ void gather_hist_records(float* __restrict__ dst, con
                 const uint4* sp = reinterpret_cast<const uint4*>(src) + (size_t)p * C4;
                 cur[q]    = sp[part];
                 before[q] = part > 0 ? sp[part - 1].w : 0u;
-                sd[q]     = *reinterpret_cast<const int2*>(side + (size_t)p * 2);
+                sd[q]     = *reinterpret_cast<const int2*>(side + (size_t)(SIDE_BY_OUT ? j : p) * 2);
             }
 #pragma unroll
             for (int q = 0; q < FLY; ++q) {
@@ -321,7 +322,7 @@ __device__ __forceinline__ void gather_hist_records(float* __restrict__ dst, con
         const int p      = s_src[j];
         const uint4* sp  = reinterpret_cast<const uint4*>(src) + (size_t)p * C4;
         uint4* dp        = reinterpret_cast<uint4*>(dst) + (size_t)j * C4d;
-        const int2 sd    = *reinterpret_cast<const int2*>(side + (size_t)p * 2);
+        const int2 sd    = *reinterpret_cast<const int2*>(side + (size_t)(SIDE_BY_OUT ? j : p) * 2);
         for (int part = part0; part < n4; part += group) {
             const uint4 cur = sp[part];
             const uint32_t before = part > 0 ? sp[part - 1].w : 0u;
@@ -459,6 +460,117 @@ __global__ void __launch_bounds__(BLK) reject_kernel(Problem P, DeviceState D, i
             D.lazy_reset[e]       = 0;  // every record of the new buffer carries its real state
             D.cur[e].update_count = s_count;
         }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// reject_hist_kernel: the same rejectSample on history particles (gridworld FBA-POMDP, fba_device.h), one workgroup per slot of a
+// chunk of slots (for_each_chunk: the new filter is built in the slot's scratch place and swapped in, DeviceState::single_rec).
+// Attempt k is reject_kernel's: stream (REJECT, k), its source uniform_int(N), one step of the source particle read through its
+// entries (gridworld_hist_step, the draws of the dense step), accepted iff the sampled observation is the real one; the accepted
+// attempts are compacted in attempt order by ballot + popcount, the first N are the new filter and update_count is the index of
+// the N-th + 1.  Output record j is its attempt's source record with the step's entry inserted at the end of action a's group and
+// its state set to s' (gather_hist_records).  Every particle of a slot steps with the same real action, so every record keeps the
+// same per-action layout and hist_cnt advances once per update, as under importance sampling.
+// K > 0: the prior's Dirichlet rows from LDS (Problem::hist_lds, rows of K floats), as is_multi_step_kernel<false, true, K> has them.
+// ---------------------------------------------------------------------------------------------
+template <int K>
+__global__ void __launch_bounds__(REJECT_BLOCK) reject_hist_kernel(Problem P, DeviceState D)
+{
+    constexpr int BLK = REJECT_BLOCK;
+    extern __shared__ uint4 s_prior_rows[];   // K > 0: one byte per row slot (HistRowIds numbering), then the distinct rows
+    __shared__ int32_t s_src[BLK];
+    __shared__ __attribute__((aligned(8))) int32_t s_side[2 * BLK];   // accepted attempt j of the chunk: {s', the step's entry}
+    __shared__ int32_t s_wave[BLK / 64];
+    __shared__ int32_t s_count;
+    const int e = chunk_slot(D, blockIdx.x), tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (!D.need_update[e]) return;
+    const uint32_t hist_cnt = D.hist_cnt[e];
+    const int hist_n = hist_total(hist_cnt);
+    if (hist_n >= P.hist_cap) {   // the records are full (only the per-step interface gets here): FBA_ESTATE on the host (check_fault)
+        if (tid == 0) {
+            atomicCAS(D.fault, 0, 0x40000000 + e);
+            D.need_update[e] = 0;
+            D.active[e]      = 0;
+        }
+        return;
+    }
+    if (K > 0) {   // every thread, before any leaves
+        const uint4* src = reinterpret_cast<const uint4*>(P.hist_lds);
+        const int n16 = (P.hist_rid_bytes + P.hist_distinct * K * (int)sizeof(float)) / 16;
+        for (int i = tid; i < n16; i += BLK) s_prior_rows[i] = src[i];
+        __syncthreads();
+    }
+    const int a = D.action[e], o = D.obs[e], N = P.N;
+    const int cur = D.bufsel[e];
+    const float* scn = D.p_rec + rec_base(P, D, e, cur) * (size_t)P.Cs;
+    float* dcn       = rec_dst(P, D, e, cur ^ 1);
+    const int rs = hist_stride(P, hist_n), rd = hist_stride(P, hist_n + 1);   // words between source / new records
+    const int off = hist_offset(hist_cnt, a), na = hist_count(hist_cnt, a);
+    const int group = record_group(rd / 4);
+    Rng g = slot_rng(P, D, e);
+
+    int acc = 0, base = 0;
+    while (acc < N) {
+        if (base >= REJECT_MAX_ATTEMPTS) {   // (as reject_kernel: park the slot, the host reports "accepted fewer than")
+            if (tid == 0) {
+                atomicCAS(D.fault, 0, 1 + e);
+                D.need_update[e] = 0;
+                D.active[e]      = 0;
+            }
+            return;
+        }
+        const int k = base + tid;
+        g.stream(FBA_PHASE_REJECT, (uint32_t)k);
+        const int src = g.uniform_int(N);   // FlatFilter::sample
+        const uint32_t* rec = reinterpret_cast<const uint32_t*>(scn + (size_t)src * rs);
+        const uint32_t mask = rec[1];
+        uint32_t sp = (mask >> 16) & 0x3ffu, entry;
+        int so;
+        double r, prob;
+        if (K > 0) {
+            const HistRowsLds<(K > 0 ? K : 8)> rl{reinterpret_cast<const uint8_t*>(s_prior_rows),
+                                                   reinterpret_cast<const float*>(reinterpret_cast<const char*>(s_prior_rows) + P.hist_rid_bytes),
+                                                   HistRowIds(P.gw_N, P.gw_G, 4)};
+            gridworld_hist_step(P, g, rl, rec + 2 + off, na, mask, sp, a, so, r, entry, o, prob);
+        } else
+            gridworld_hist_step(P, g, rec + 2 + off, na, mask, sp, a, so, r, entry, o, prob);
+        const bool ok = (so == o);
+        const unsigned long long ballot = __ballot(ok);
+        const int prefix = __popcll(ballot & ((1ull << lane) - 1ull));
+        if (lane == 0) s_wave[wave] = __popcll(ballot);
+        __syncthreads();
+        int woff = 0, chunk = 0;
+        for (int w = 0; w < BLK / 64; ++w) {
+            if (w < wave) woff += s_wave[w];
+            chunk += s_wave[w];
+        }
+        const int j = woff + prefix;   // position among this chunk's accepted attempts
+        if (ok && acc + j < N) {
+            s_src[j]          = src;
+            s_side[2 * j]     = gridworld_unpack_state(P, sp);
+            s_side[2 * j + 1] = (int32_t)entry;
+            if (acc + j == N - 1) s_count = k + 1;
+        }
+        __syncthreads();
+        const int m = min(chunk, N - acc);
+        gather_hist_records<int32_t, true>(dcn + (size_t)acc * rd, scn, s_src, s_side, hist_n, 2 + off + na, m, rs / 4, group, BLK, rd / 4);
+        acc += m;
+        base += BLK;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        D.hist_cnt[e] = hist_cnt + (1u << (8 * a));
+        if (D.single_rec) D.copy_pending[e] = 1;
+        D.bufsel[e] ^= 1;
+        D.belief_steps[e] += (unsigned long long)s_count;
+        D.upd_attempts[e] += (unsigned long long)s_count;
+        D.upd_particles[e] += (unsigned long long)N;
+        // words beyond a record's two header words: the attempts read their action's entries, the gather reads and writes whole records
+        D.upd_entries[e] += (unsigned long long)s_count * (unsigned long long)na + (unsigned long long)N * (unsigned long long)(2 * hist_n);
+        D.need_update[e]      = 0;
+        D.lazy_reset[e]       = 0;
+        D.cur[e].update_count = s_count;
     }
 }
 
@@ -1913,7 +2025,7 @@ __global__ void __launch_bounds__(256) init_kernel(Problem P, DeviceState D, int
                 for (int k = 0; k < 2 * P.A; ++k)
                     if (g.boolean()) mask |= 1u << k;
             rec[1] = mask | (gridworld_pack_state(P, s0) << 16);
-            D.p_weight[pb + i] = w1h;
+            if (P.belief == FBA_BELIEF_IMPORTANCE) D.p_weight[pb + i] = w1h;   // (a rejection filter has no weights)
         }
         return;
     }
@@ -2034,6 +2146,29 @@ __global__ void __launch_bounds__(256) reset_kernel(Problem P, DeviceState D, in
     }
 }
 
+// The plain rejection filter on history particles: the reset in place.  lazy_state stands in for word 0 only, and a history record
+// keeps its state twice -- word 0 as an index, bits 16-25 of word 1 packed (hist_pack) -- and the search and the update step from the
+// packed one.  Both are written here, from the same stream (run, episode, 0, RESET, i) as lazy_state's; the structure bits stay.
+__global__ void __launch_bounds__(256) reset_hist_flat_kernel(Problem P, DeviceState D)
+{
+    const int e = blockIdx.y, tid = threadIdx.x;
+    if (D.need_reset[e] != 1) return;
+    const int i_lo = blockIdx.x * PARTICLE_TILE, i_hi = min(P.N, i_lo + PARTICLE_TILE);
+    if (i_lo >= P.N) return;
+    const int rs = hist_stride(P, hist_total(D.hist_cnt[e]));
+    uint32_t* recs = reinterpret_cast<uint32_t*>(D.p_rec + rec_base(P, D, e, D.bufsel[e]) * (size_t)P.Cs);
+    Rng g = slot_rng(P, D, e);
+    g.position((uint32_t)D.run[e], (uint32_t)D.episode[e], 0);
+    for (int i = i_lo + tid; i < i_hi; i += 256) {
+        g.stream(FBA_PHASE_RESET, (uint32_t)i);
+        const int s = domain_start(P, g);
+        uint2* w = reinterpret_cast<uint2*>(recs + (size_t)i * rs);   // (rs is a multiple of four words)
+        uint2 v  = *w;
+        v.x = (uint32_t)s;
+        v.y = (v.y & 0xffffu) | (gridworld_pack_state(P, s) << 16);
+        *w  = v;
+    }
+}
 // Plain rejection filter: flag the reset instead of performing it (lazy_state).
 __global__ void lazy_reset_kernel(Problem P, DeviceState D)
 {
@@ -2412,6 +2547,19 @@ void launch_belief_update(const Problem& P, const DeviceState& D, hipStream_t st
         const int ft = (P.model == FBA_MODEL_BA_FACTORED && !P.dirichlet_regular &&
                         (P.domain == FBA_DOM_FTIGER_EPISODIC || P.domain == FBA_DOM_FTIGER_CONTINUOUS))
                            ? 31 - __builtin_clz((unsigned)P.S) : 0;  // S = 2^FS
+        if (P.hist) {   // (fba_create: the plain filter, expected Dirichlet)
+            const int K = P.hist_row <= 8 ? 8 : (P.hist_row <= 10 ? 12 : 0);
+            const bool lrows = P.hist_lds && K > 0 && !D.ab_rows_hbm;   // the prior's rows from LDS (FBA_HIST_ROWS=hbm: from L2)
+            const size_t lds = lrows ? (size_t)P.hist_rid_bytes + (size_t)P.hist_distinct * K * sizeof(float) : 0;
+            const auto launch = [&](const DeviceState& Dc, int cnt) {
+                if (lrows && K == 8) hipLaunchKernelGGL(reject_hist_kernel<8>, dim3(cnt), dim3(REJECT_BLOCK), lds, st, P, Dc);
+                else if (lrows) hipLaunchKernelGGL(reject_hist_kernel<12>, dim3(cnt), dim3(REJECT_BLOCK), lds, st, P, Dc);
+                else hipLaunchKernelGGL(reject_hist_kernel<0>, dim3(cnt), dim3(REJECT_BLOCK), 0, st, P, Dc);
+            };
+            if (D.single_rec) for_each_chunk(P, D, st, launch, D.need_update);
+            else launch(D, P.E);
+            return;
+        }
         for (int fc = (P.reinvig || P.incub) ? 1 : 0; fc >= 0; --fc) {  // the main filter's launch clears the request flag: last
             if (ft == 2 && P.ft_packed) hipLaunchKernelGGL((reject_kernel<false, 0, 2, REJECT_BLOCK, true>), dim3(P.E), dim3(REJECT_BLOCK), 0, st, P, D, fc);
             else if (ft == 3 && P.ft_packed) hipLaunchKernelGGL((reject_kernel<false, 0, 3, REJECT_BLOCK, true>), dim3(P.E), dim3(REJECT_BLOCK), 0, st, P, D, fc);
@@ -2468,6 +2616,11 @@ void launch_materialize_reset(const Problem& P, const DeviceState& D, hipStream_
 void launch_reset(const Problem& P, const DeviceState& D, hipStream_t st)
 {
     if (P.belief == FBA_BELIEF_REJECTION && !P.reinvig && !P.cheat && !P.incub) {  // the plain rejection filter resets lazily
+        if (P.hist) {   // ... except on history particles, which keep a second copy of the state (reset_hist_flat_kernel)
+            hipLaunchKernelGGL(reset_hist_flat_kernel, dim3(ceil_div(P.N, PARTICLE_TILE), P.E), dim3(256), 0, st, P, D);
+            hipLaunchKernelGGL(post_reset_kernel, dim3(ceil_div(P.E, 256)), dim3(256), 0, st, P, D);
+            return;
+        }
         hipLaunchKernelGGL(lazy_reset_kernel, dim3(ceil_div(P.E, 256)), dim3(256), 0, st, P, D);
         return;
     }

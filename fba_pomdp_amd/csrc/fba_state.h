@@ -145,7 +145,8 @@ struct DeviceState {
     double* ep_sums;    // [E][3] finished episodes of this slot: count, sum of returns, sum of squares
     unsigned long long* upd_particles; // [E] particles written by belief updates
     unsigned long long* upd_attempts;  // [E] rejection attempts / importance particles stepped
-    unsigned long long* upd_entries;   // [E] history particles: sum over updates of N * (entries per record before the update)
+    unsigned long long* upd_entries;   // [E] history particles: sum over updates of N * (entries per record before the update);
+                                       //     rejection (reject_hist_kernel): attempts * (entries of the real action) + 2 * N * (entries per record)
     fba_trace_rec* cur;  // [E] record being assembled for the current tick
     fba_trace_rec* trace; // [trace_cap]
     uint32_t* trace_hist;  // [trace_cap][FBA_TRACE_HIST_BINS] or null: the filter's state histogram after the update of each record (cfg.trace = 2)

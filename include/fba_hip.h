@@ -126,7 +126,7 @@ typedef struct fba_config {
                               * belief / copied per cheat by the cheating belief (BeliefConf.cpp:17-21) */
     double threshold;        /* --threshold: log likelihood below which the cheating belief cheats (< 0) */
     int32_t belief_option;   /* --belief-option: mh-within-gibbs 0 = state histories by message passing (default), 1 = "rs" */
-    int32_t search_budget;   /* history-particle searches (gridworld FBA-POMDP, importance filter): iterations of the search loop per launch.
+    int32_t search_budget;   /* history-particle searches (gridworld FBA-POMDP, fba_particle_bytes): iterations of the search loop per launch.
                               * 0 = a launch runs every slot's whole search (lock-step ticks: a tick lasts as long as its deepest tree);
                               * > 0 = a launch stops at the first simulation boundary behind that many iterations, unfinished searches
                               * are parked in their trees and resumed by the next launch, and slots whose search is done take their
@@ -198,8 +198,12 @@ int fba_domain_sizes(const fba_ctx* ctx, int32_t* S, int32_t* A, int32_t* O);
 int fba_counts_len(const fba_ctx* ctx); /* floats per particle count blob (0 for plain POMDP) */
 int fba_particle_bytes(const fba_ctx* ctx); /* HBM bytes of one particle record.  Tabular tiger particles are stored packed
                                              * (uint16 increment counts over the shared prior, 64 B instead of 128 B) when the
-                                             * prior allows it exactly; FBA_DENSE_PARTICLES=1 in the environment forces fp32 counts.
-                                             * fba_belief_get / fba_belief_set always speak fp32 counts. */
+                                             * prior allows it exactly.  Gridworld FBA-POMDP particles are stored as histories of
+                                             * their own steps over the shared prior (8 B + 4 B per real step instead of 191 KB at
+                                             * --size 7) under the importance filter, and under the plain rejection filter where
+                                             * the planner is po-uct or random with at most 65 536 simulations; such contexts refuse
+                                             * fba_belief_set of states or counts.  FBA_DENSE_PARTICLES=1 in the environment forces
+                                             * fp32 counts.  fba_belief_get / fba_belief_set always speak fp32 counts. */
 int fba_slots(const fba_ctx* ctx);      /* slots actually resident (cfg.slots, or the library's choice) */
 
 /* Prior count tables.  fba_create builds the domain's own prior (TigerPriors.cpp:14-43,
