@@ -327,7 +327,9 @@ struct Problem {
     int32_t point;      // point-estimate belief: N = 1 and Belief::sample() returns the state without a draw
     int32_t reinvig;    // reinvigoration belief: particles bred per update (belief = REJECTION then); 0 = off
     int32_t hist;       // history particles (gridworld FBA-POMDP, importance filter): a record holds the particle's increments as one
-                        // 4-byte entry per real step over the shared prior tables (HistView below); C = 0 then, hist_cap entries per record
+                        // 4-byte entry per real step over the shared prior tables (HistView below); C = 0 then, hist_cap entries per record.
+                        // 2 = the same records for the TABULAR gridworld BA-POMDP (TabRows below): entries of state indices, and
+                        // hist_base points at the prior's sparse rows instead (hist_alt, hist_lds unused)
     int32_t hist_cap;
     int32_t hist_compact;   // records of short histories stand closer than Cs words (hist_stride below)
     int32_t gw_N, gw_G;          // gridworld: N, number of goals (copies of GridDesc's, as kernel arguments)
@@ -1445,6 +1447,106 @@ __device__ __forceinline__ bool gridworld_hist_step(const Problem& P, Rng& g, co
 {
     const HistLayout L(P.gw_N, P.gw_G, P.A);
     return gridworld_hist_step(P, g, HistRowsGlobal{P.hist_base, P.hist_alt, P.hist_base + L.obase0, L}, ent, n, mask, sp, a, o, r, entry, real_o, prob);
+}
+
+// ---- history particles of the TABULAR gridworld BA-POMDP (Problem::hist == 2) ------------------------------------
+// The record is the one above -- word 0 the state, word 1 unused bits, words 2.. one entry per real step, grouped by action
+// through DeviceState::hist_cnt -- but an entry holds state INDICES: s | s' << 10 | o << 20 (S = O = N*N*G <= 640).  That is
+// the tabular model's sufficient statistic: T(s, a, s') = prior + the entries of a's group with (s, s'), O(a, s', o) = prior + the
+// entries with (s', o) (BAFlatModel::incrementCountsOf, BAFlatModel.cpp:126-139).  The prior (GridWorldFlatBAPrior,
+// GridWorldBAPriors.cpp:45-150) is sparse: a transition row has 1-2 nonzero columns (2 G on the agent's goal), an observation
+// row the cells obsDisplProb reaches inside s' own goal slice.  Problem::hist_base holds those rows (TabRows):
+//   words [0, 2*A*S + 1)       where row r's columns start: r = s*A + a for T(s, a, .), A*S + a*S + s' for O(a, s', .)
+//   then, from tab_cols_word   {column, fp32 count} pairs, columns ascending within a row
+// 380 KB at N = 7 (16 KB of offsets, 45 K pairs), L2-resident; the dense 7.68 MB table is never read by a step.
+__host__ __device__ __forceinline__ int tab_cols_word(int A, int S) { return (2 * A * S + 1 + 3) & ~3; }
+struct TabRows {
+    const uint32_t* ptr; const uint2* col;
+    __device__ __forceinline__ TabRows(const Problem& P)
+        : ptr(reinterpret_cast<const uint32_t*>(P.hist_base)), col(reinterpret_cast<const uint2*>(P.hist_base + tab_cols_word(P.A, P.S))) {}
+};
+// One Dirichlet row of a history particle, walked column by column in ascending order: the prior's nonzero columns merged with
+// the columns its entries raised -- an entry of a's group whose field at `kshift` equals `key` adds 1 at its field at `tshift`, and
+// `extra` >= 0 adds one more there (the step's own pending increment).  A record can raise a column the prior leaves at 0 (the
+// fall-through of sampleFromMult below returns column n - 1 whatever its count; an importance filter records an entry whose
+// observation had probability 0), so the entries are merged in, not only counted at the prior's columns.  A column's value is
+// prior + j, which the host checked to be the float that j additions of 1.0f reach (increments_exact), so it is the dense value.
+// visit(column, value) returns true to stop.
+template <int STRIDE, class F>
+__device__ __forceinline__ void tab_row_walk(const TabRows& T, int row, const uint32_t* ent, int n, uint32_t key, int kshift, int tshift, int extra, F visit)
+{
+    constexpr int END = 0x7fffffff;
+    // the smallest entry column above `last` and how many entries (+ extra) hold it
+    auto next_entry = [&](int last, int& t, int& cnt) {
+        t = (extra > last) ? extra : END;
+        cnt = (extra > last) ? 1 : 0;
+        for (int j = 0; j < n; ++j) {
+            const uint32_t e = ent[j * STRIDE];
+            const int c = (int)((e >> tshift) & 0x3ffu);
+            if (((e >> kshift) & 0x3ffu) != key || c <= last) continue;
+            cnt = c < t ? 1 : (c == t ? cnt + 1 : cnt);
+            t   = min(t, c);
+        }
+    };
+    int ip = (int)T.ptr[row];
+    const int ie = (int)T.ptr[row + 1];
+    int t, tc;
+    next_entry(-1, t, tc);
+    while (true) {
+        const uint2 pc = ip < ie ? T.col[ip] : make_uint2((uint32_t)END, 0u);
+        const int c = min((int)pc.x, t);
+        if (c == END) return;
+        float v = 0.f;
+        if ((int)pc.x == c) { v = __uint_as_float(pc.y); ++ip; }
+        if (t == c) { v += (float)tc; next_entry(c, t, tc); }
+        if (visit(c, v)) return;
+    }
+}
+// sampleFromExpectedMult (random.cpp:244-255) on such a row of n columns: the double total over every column in order (the zeros
+// add nothing), then the float CDF against p = u * total; when p passes the float sum by rounding, the dense walk falls through
+// to column n - 1, whatever its count, and so does this one.
+template <int STRIDE>
+__device__ __forceinline__ int tab_row_sample(const TabRows& T, int row, const uint32_t* ent, int n, uint32_t key, int kshift, int tshift, double u, int ncol)
+{
+    double total = 0;
+    tab_row_walk<STRIDE>(T, row, ent, n, key, kshift, tshift, -1, [&](int, float v) { total += (double)v; return false; });
+    const double p = u * total;
+    float sum = 0.f;
+    int pick  = ncol - 1;
+    tab_row_walk<STRIDE>(T, row, ent, n, key, kshift, tshift, -1, [&](int c, float v) {
+        if (c > ncol - 2) return true;   // (the dense walk tests columns 0 .. n - 2 only)
+        sum += v;
+        if (p < (double)sum) { pick = c; return true; }
+        return false;
+    });
+    return pick;
+}
+// BAPOMDP::step over BAFlatModel (sim_step's tabular branch) on a history particle of the tabular gridworld model, one lane: the
+// transition row T(s, a, .) with draw uT, the observation row O(a, s', .) with draw uO -- the two draws sim_step makes, in its
+// order -- plus P(real_o | a, s') from the counts after the step's own two increments (sim_obs_prob -> expected_mult_at: float
+// sum, float division).  `ent` = the particle's n entries of action a, STRIDE words apart; `s` = the state index.  Returns the
+// step's entry and whether the step was terminal (GridWorldBAExtension.cpp:74-99: terminal and reward from the OLD state).
+template <int STRIDE, bool PROB>
+__device__ __forceinline__ bool gridworld_tab_hist_step(const Problem& P, const TabRows& T, const uint32_t* ent, int n, int& s, int a, int& o, double& r,
+                                                        uint32_t& entry, double uT, double uO, int real_o, double& prob)
+{
+    const int S = P.S, A = P.A, N = P.gw_N, G = P.gw_G;
+    const int ns = tab_row_sample<STRIDE>(T, s * A + a, ent, n, (uint32_t)s, 0, 10, uT, S);
+    o = tab_row_sample<STRIDE>(T, A * S + a * S + ns, ent, n, (uint32_t)ns, 10, 20, uO, P.O);
+    if (PROB) {
+        float sum = 0.f, mine = 0.f;
+        tab_row_walk<STRIDE>(T, A * S + a * S + ns, ent, n, (uint32_t)ns, 10, 20, o, [&](int c, float v) {
+            sum += v;
+            mine = c == real_o ? v : mine;
+            return false;
+        });
+        prob = ((double)sum <= 1e-300) ? 0.0 : (double)(mine / sum);
+    }
+    const bool found = gridworld_on_goal(P, (s / (N * G)) * N + (s / G) % N, s % G);
+    r     = found ? 1 : 0;
+    entry = hist_entry((uint32_t)s, (uint32_t)ns, (uint32_t)o);
+    s     = ns;
+    return found;
 }
 
 // ---- the same step shared by the four lanes of a quad (search_hist_kernel) ---------------------------------------

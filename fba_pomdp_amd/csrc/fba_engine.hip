@@ -45,6 +45,7 @@ struct fba_ctx {
     float* d_hist_base   = nullptr;  // ... and both tables on the device, rows padded to 16 bytes (HistLayout)
     float* d_hist_alt    = nullptr;
     uint8_t* d_hist_lds  = nullptr;  // ... and deduplicated: row ids + distinct rows (Problem::hist_lds)
+    uint32_t* d_tab_rows = nullptr;  // tabular history particles (Problem::hist == 2): the prior's sparse rows (TabRows, fba_device.h)
     FDesc fdesc{};          // host copy of the factored model description
     FDesc* d_fdesc       = nullptr;
     GridDesc gdesc{};
@@ -847,12 +848,47 @@ bool increments_exact(const std::vector<float>& table, int most)
     return true;
 }
 
+// The sparse rows of a tabular prior (TabRows, fba_device.h): row offsets, then {column, fp32 count} pairs of the nonzero columns, ascending
+std::vector<uint32_t> tab_sparse_rows(const Problem& P, const std::vector<float>& prior)
+{
+    const int S = P.S, A = P.A, O = P.O, R = 2 * A * S;
+    std::vector<uint32_t> ptr((size_t)tab_cols_word(A, S), 0u), cols;
+    for (int r = 0; r < R; ++r) {
+        ptr[(size_t)r] = (uint32_t)(cols.size() / 2);
+        const size_t off = r < A * S ? (size_t)r * S : (size_t)P.phi_len + (size_t)(r - A * S) * O;
+        const int n = r < A * S ? S : O;
+        for (int i = 0; i < n; ++i)
+            if (prior[off + i] != 0.f) {
+                uint32_t bits;
+                std::memcpy(&bits, &prior[off + i], 4);
+                cols.push_back((uint32_t)i);
+                cols.push_back(bits);
+            }
+    }
+    ptr[(size_t)R] = (uint32_t)(cols.size() / 2);
+    ptr.insert(ptr.end(), cols.begin(), cols.end());
+    return ptr;
+}
+
 int upload_prior(fba_ctx* c)
 {
     std::vector<float> padded((size_t)c->P.Cs, 0.f);
     if (c->P.ft_packed) {  // the prior record in packed form: no increments, the correct structure's bits
         const uint32_t m = 1u;
         std::memcpy(&padded[(size_t)c->fdesc.ncounts / 2], &m, 4);
+    } else if (c->P.hist == 2) {
+        // tabular records: the prior's nonzero columns per row (TabRows, fba_device.h), and the dense table for the belief checksum
+        // (flush_kernel) and fba_belief_get
+        if (!increments_exact(c->prior, c->P.hist_cap + 1))
+            return fail(c, FBA_EINVAL, "this context stores particles as histories over the prior table, which needs prior counts c with c + j exact "
+                                       "in fp32 for j <= %d; create it with FBA_DENSE_PARTICLES=1 in the environment for other tables", c->P.hist_cap + 1);
+        const std::vector<uint32_t> rows = tab_sparse_rows(c->P, c->prior);
+        dev_free(c, c->d_tab_rows);
+        if (const int rc = dev_alloc(c, &c->d_tab_rows, rows.size(), false)) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->d_tab_rows, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->d_prior_dense, c->prior.data(), c->prior.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // (rows is a local)
+        c->P.hist_base = reinterpret_cast<const float*>(c->d_tab_rows);
     } else if (c->P.hist) {  // records carry no counts: the tables sit beside them, rows padded to 16 bytes (HistLayout, fba_device.h)
         const HistLayout L(c->gdesc.N, c->gdesc.G, c->P.A);
         const int N = L.N, G = L.G, A = L.A, XYd = N * N * G * N, GGd = N * N * G * G, NNd = N * N;
@@ -1489,13 +1525,23 @@ int fba_create(const fba_config* cfg, fba_ctx** out)
                            cfg->sims <= 65536 && !hist_records_tree &&
                            (cfg->tree_buckets <= 0 || (long long)cfg->tree_buckets <= (1ll << 28) / (4ll * P.O) - 2);   // (fit, below)
     const bool hist_weighted = cfg->belief == FBA_BELIEF_IMPORTANCE && cfg->particles <= IS_MAX_CHUNKS * 256 && !std::getenv("FBA_IS_MULTI_MIN");
-    if (cfg->model == FBA_MODEL_BA_FACTORED && cfg->domain == FBA_DOM_GRIDWORLD && (hist_weighted || hist_flat) &&
+    // The tabular gridworld BA-POMDP stores them too (P.hist = 2: entries of state indices over the prior's sparse rows, 176 B instead of
+    // 7.68 MB at N = 7) under the same filters, where its search is the bucket-tree one (search_tabhist_kernel: po-uct or random, at most 65536
+    // simulations, a table whose keys fit, no records tree); ts and the rest stay dense.
+    const bool hist_tab = cfg->model == FBA_MODEL_BA_TABLE && (cfg->planner == FBA_PLANNER_POUCT || cfg->planner == FBA_PLANNER_RANDOM) &&
+                          cfg->sims <= 65536 && !hist_records_tree && (cfg->tree_buckets <= 0 || (long long)cfg->tree_buckets <= (1ll << 28) / (4ll * P.O) - 2);
+    if ((cfg->model == FBA_MODEL_BA_FACTORED || hist_tab) && cfg->domain == FBA_DOM_GRIDWORLD && (hist_weighted || hist_flat) &&
         !cfg->dirichlet_regular && !std::getenv("FBA_DENSE_PARTICLES") && (long long)cfg->episodes * cfg->horizon <= HIST_MAX_CAP && cfg->size <= HIST_MAX_N) {
         const int cap = cfg->episodes * cfg->horizon;
-        build_gridworld_alt_prior(c);
-        std::vector<float> counts(c->prior.begin(), c->prior.begin() + c->fdesc.ncounts);
-        if (increments_exact(counts, cap + 1) && increments_exact(c->prior_alt, cap + 1)) {
-            P.hist     = 1;
+        bool exact = false;
+        if (hist_tab) exact = build_tabular_prior(c) == FBA_OK && increments_exact(c->prior, cap + 1);   // (built again below, as for every tabular context)
+        else {
+            build_gridworld_alt_prior(c);
+            std::vector<float> counts(c->prior.begin(), c->prior.begin() + c->fdesc.ncounts);
+            exact = increments_exact(counts, cap + 1) && increments_exact(c->prior_alt, cap + 1);
+        }
+        if (exact) {
+            P.hist     = hist_tab ? 2 : 1;
             P.hist_cap = cap;
             P.hist_row = std::max(c->gdesc.N, c->gdesc.G);
             P.gw_N = c->gdesc.N; P.gw_G = c->gdesc.G;
@@ -1790,7 +1836,7 @@ int fba_create(const fba_config* cfg, fba_ctx** out)
     if (!D.search_order) D.ab_lockstep = 0;   // (lock-step waves exist on the bucket tree only: search_hist2_kernel)
     CHK(dev_alloc(c, &c->d_prior, P.Cs));
     CHK(dev_alloc(c, &c->d_prior_dense, std::max(c->dense_C, 1)));
-    if (P.hist) {
+    if (P.hist == 1) {
         const HistLayout L(c->gdesc.N, c->gdesc.G, P.A);
         CHK(dev_alloc(c, &c->d_hist_base, (size_t)L.total + 16));   // (+16: a row fetch may run up to a row width past the last row)
         CHK(dev_alloc(c, &c->d_hist_alt, (size_t)L.alt_total + 16));
@@ -1927,7 +1973,7 @@ int fba_set_model_tabular(fba_ctx* c, const float* phi, const float* psi)
     if (rc) c->prior = keep;
     // The prior is what Belief::initiate copies into every particle (BAPOMDPPrior::sample).  Packed particles hold
     // increments over the table, so live particles would silently move to the new table: require a new initiate.
-    else if (c->P.packed) c->belief_ready = false;
+    else if (c->P.packed || c->P.hist == 2) c->belief_ready = false;
     return rc;
 }
 
@@ -2096,6 +2142,18 @@ int fba_belief_update(fba_ctx* c, const int32_t* action, const int32_t* obs, con
 // (BABNModel::incrementCountsOf BABNModel.cpp:354-382 replayed; `cnt` = the slot's entries per action).
 static void hist_materialize(const fba_ctx* c, const uint32_t* rec, uint32_t cnt, float* counts)
 {
+    if (c->P.hist == 2) {   // tabular records: entry (s, s', o) of action a adds 1.0f at T(s, a, s') and at O(a, s', o) (BAFlatModel.cpp:126-139)
+        const int S = c->P.S, A = c->P.A, O = c->P.O;
+        std::copy(c->prior.begin(), c->prior.end(), counts);
+        int j = 0;
+        for (int a = 0; a < A; ++a)
+            for (int q = 0; q < hist_count(cnt, a); ++q, ++j) {
+                const uint32_t en = rec[2 + j], s0 = en & 0x3ffu, s1 = (en >> 10) & 0x3ffu, ob = en >> 20;
+                counts[((size_t)s0 * A + a) * S + s1] += 1.0f;
+                counts[(size_t)c->P.phi_len + ((size_t)a * S + s1) * O + ob] += 1.0f;
+            }
+        return;
+    }
     const GridDesc& g = c->gdesc;
     const int N = g.N, G = g.G, A = c->P.A;
     const int XY = N * N * G * N, GG = N * N * G * G, NN = N * N, ncounts = c->fdesc.ncounts;
@@ -2247,7 +2305,7 @@ int fba_belief_set(fba_ctx* c, int32_t slot, const int32_t* state, const double*
     HIPCHK(c, hipMemcpy(&sel, c->D.bufsel + slot, 1, hipMemcpyDeviceToHost));
     const size_t pb = ((size_t)sel * P.E + slot) * (size_t)P.N;
     if (P.hist && (state || counts))
-        return fail(c, FBA_EINVAL, "this context stores particles as histories of their own steps over the shared prior (gridworld FBA-POMDP), which "
+        return fail(c, FBA_EINVAL, "this context stores particles as histories of their own steps over the shared prior (gridworld BA-POMDP), which "
                                    "cannot take on arbitrary states or counts; create it with FBA_DENSE_PARTICLES=1 in the environment to set them");
     if (state)
         for (int i = 0; i < P.N; ++i)
@@ -2437,6 +2495,7 @@ int fba_get_kernel_times(fba_ctx* c, fba_kernel_time* out)
         // history particles (reject_hist_kernel): an attempt reads its source's two header words (8) and the entries
         // of the real action, an accepted one is gathered -- its source record read (8 + 4 per entry) and written with the new entry
         // (8 + 4 per entry + 4); `entries` counts the 4-byte entries of both (fba_state.h upd_entries); the Dirichlet rows come from LDS
+        // (tabular records, reject_tab_hist_kernel: the same formula; their sparse prior rows are L2-resident, 380 KB at N = 7, and not counted)
         if (P.hist) out[FBA_K_BELIEF_RS].bytes = attempts * 8 + particles * 20 + entries * 4;
     } else {
         out[FBA_K_BELIEF_IS].units = particles;
@@ -2444,6 +2503,7 @@ int fba_get_kernel_times(fba_ctx* c, fba_kernel_time* out)
         // history particles (alternative formula, stated in DESIGN.md section 5 before it was measured): per particle the
         // weight read and written (16), the record -- 8 bytes + 4 per entry -- read once by the update, once as a
         // resample source, written once with its new entry (+4); the Dirichlet rows come from the shared tables
+        // (tabular records, is_multi_tab_step_kernel: the same formula; their sparse prior rows are L2-resident and not counted)
         if (P.hist) out[FBA_K_BELIEF_IS].bytes = particles * 44 + entries * 12;
         // packed tiger particles (64-byte records): the same formula on the bytes a packed particle has -- the update reads
         // state + weight + its two rows and writes state + weight + two counts (32 + Rt + Ro = 48), the resample reads the

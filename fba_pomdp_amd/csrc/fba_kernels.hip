@@ -574,6 +574,95 @@ __global__ void __launch_bounds__(REJECT_BLOCK) reject_hist_kernel(Problem P, De
     }
 }
 
+// The same rejectSample on history particles of the tabular gridworld BA-POMDP (Problem::hist == 2): reject_hist_kernel's streams,
+// sources, ballot compaction, gather and counters; the step is gridworld_tab_hist_step (the draws of sim_step's tabular branch) with the
+// prior's sparse rows from L2, and the state is read from word 0 (a gather writes word 1's state bits from the entry, which holds an index here).
+__global__ void __launch_bounds__(REJECT_BLOCK) reject_tab_hist_kernel(Problem P, DeviceState D)
+{
+    constexpr int BLK = REJECT_BLOCK;
+    __shared__ int32_t s_src[BLK];
+    __shared__ __attribute__((aligned(8))) int32_t s_side[2 * BLK];   // accepted attempt j of the chunk: {s', the step's entry}
+    __shared__ int32_t s_wave[BLK / 64];
+    __shared__ int32_t s_count;
+    const int e = chunk_slot(D, blockIdx.x), tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (!D.need_update[e]) return;
+    const uint32_t hist_cnt = D.hist_cnt[e];
+    const int hist_n = hist_total(hist_cnt);
+    if (hist_n >= P.hist_cap) {   // the records are full (only the per-step interface gets here): FBA_ESTATE on the host (check_fault)
+        if (tid == 0) {
+            atomicCAS(D.fault, 0, 0x40000000 + e);
+            D.need_update[e] = 0;
+            D.active[e]      = 0;
+        }
+        return;
+    }
+    const int a = D.action[e], o = D.obs[e], N = P.N;
+    const int cur = D.bufsel[e];
+    const float* scn = D.p_rec + rec_base(P, D, e, cur) * (size_t)P.Cs;
+    float* dcn       = rec_dst(P, D, e, cur ^ 1);
+    const int rs = hist_stride(P, hist_n), rd = hist_stride(P, hist_n + 1);   // words between source / new records
+    const int off = hist_offset(hist_cnt, a), na = hist_count(hist_cnt, a);
+    const int group = record_group(rd / 4);
+    const TabRows T(P);
+    Rng g = slot_rng(P, D, e);
+
+    int acc = 0, base = 0;
+    while (acc < N) {
+        if (base >= REJECT_MAX_ATTEMPTS) {   // (as reject_kernel: park the slot, the host reports "accepted fewer than")
+            if (tid == 0) {
+                atomicCAS(D.fault, 0, 1 + e);
+                D.need_update[e] = 0;
+                D.active[e]      = 0;
+            }
+            return;
+        }
+        const int k = base + tid;
+        g.stream(FBA_PHASE_REJECT, (uint32_t)k);
+        const int src = g.uniform_int(N);   // FlatFilter::sample
+        const uint32_t* rec = reinterpret_cast<const uint32_t*>(scn + (size_t)src * rs);
+        int s = (int)rec[0], so;
+        uint32_t entry;
+        double r, prob;
+        const double uT = g.u01(), uO = g.u01();
+        gridworld_tab_hist_step<1, false>(P, T, rec + 2 + off, na, s, a, so, r, entry, uT, uO, o, prob);
+        const bool ok = (so == o);
+        const unsigned long long ballot = __ballot(ok);
+        const int prefix = __popcll(ballot & ((1ull << lane) - 1ull));
+        if (lane == 0) s_wave[wave] = __popcll(ballot);
+        __syncthreads();
+        int woff = 0, chunk = 0;
+        for (int w = 0; w < BLK / 64; ++w) {
+            if (w < wave) woff += s_wave[w];
+            chunk += s_wave[w];
+        }
+        const int j = woff + prefix;   // position among this chunk's accepted attempts
+        if (ok && acc + j < N) {
+            s_src[j]          = src;
+            s_side[2 * j]     = s;
+            s_side[2 * j + 1] = (int32_t)entry;
+            if (acc + j == N - 1) s_count = k + 1;
+        }
+        __syncthreads();
+        const int m = min(chunk, N - acc);
+        gather_hist_records<int32_t, true>(dcn + (size_t)acc * rd, scn, s_src, s_side, hist_n, 2 + off + na, m, rs / 4, group, BLK, rd / 4);
+        acc += m;
+        base += BLK;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        D.hist_cnt[e] = hist_cnt + (1u << (8 * a));
+        if (D.single_rec) D.copy_pending[e] = 1;
+        D.bufsel[e] ^= 1;
+        D.belief_steps[e] += (unsigned long long)s_count;
+        D.upd_attempts[e] += (unsigned long long)s_count;
+        D.upd_particles[e] += (unsigned long long)N;
+        D.upd_entries[e] += (unsigned long long)s_count * (unsigned long long)na + (unsigned long long)N * (unsigned long long)(2 * hist_n);
+        D.need_update[e]      = 0;
+        D.lazy_reset[e]       = 0;
+        D.cur[e].update_count = s_count;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // reject_tiger_lds_kernel: the same rejectSample for packed tabular-tiger particles with N <= 4096, arranged so
 // that the attempts never touch HBM.  For the slot's action a, a step from particle i reads only three words
@@ -1884,6 +1973,43 @@ __global__ void __launch_bounds__(256) is_multi_step_kernel(Problem P, DeviceSta
     const double incl = wave_inclusive_scan(sum, lane);
     if (lane == 63) D.ctot[(size_t)e * D.ctot_stride + c + 1] = incl;
 }
+// The same update pass on history particles of the tabular gridworld BA-POMDP (Problem::hist == 2): gridworld_tab_hist_step with the
+// prior's sparse rows from L2, the state from word 0.  The rest of the update is is_multi_step_kernel<false, true>'s launches.
+__global__ void __launch_bounds__(256) is_multi_tab_step_kernel(Problem P, DeviceState D)
+{
+    const int e = chunk_slot(D, blockIdx.y), tid = threadIdx.x, lane = tid & 63;
+    if (!D.need_update[e] || hist_update_refused(P, D, e)) return;
+    const int c = blockIdx.x * 4 + (tid >> 6), N = P.N;
+    if (c * 256 >= N) return;
+    const int a = D.action[e], o = D.obs[e];
+    double* sw = D.p_weight + pbase(P, e, D.bufsel[e]);
+    const float* scn = D.p_rec + rec_base(P, D, e, D.bufsel[e]) * (size_t)P.Cs;
+    const uint32_t hist_cnt = D.hist_cnt[e];
+    const int rs = hist_stride(P, hist_total(hist_cnt));
+    const TabRows T(P);
+    Rng g = slot_rng(P, D, e);
+    const int i0 = c * 256 + lane * 4;
+    double sum = 0;
+    for (int k = 0; k < 4; ++k) {
+        const int i = i0 + k;
+        double v = 0.0;
+        if (i < N) {
+            g.stream(FBA_PHASE_IS_UPDATE, (uint32_t)i);
+            const uint32_t* rec = reinterpret_cast<const uint32_t*>(scn + (size_t)i * rs);
+            int s = (int)rec[0], so;
+            uint32_t entry;
+            double r, prob;
+            const double uT = g.u01(), uO = g.u01();
+            gridworld_tab_hist_step<1, true>(P, T, rec + 2 + hist_offset(hist_cnt, a), hist_count(hist_cnt, a), s, a, so, r, entry, uT, uO, o, prob);
+            *reinterpret_cast<int2*>(D.p_side + ((size_t)e * N + i) * 2) = make_int2(s, (int)entry);
+            v     = sw[i] * prob;
+            sw[i] = v;
+        }
+        sum = (k == 0) ? v : sum + v;
+    }
+    const double incl = wave_inclusive_scan(sum, lane);
+    if (lane == 63) D.ctot[(size_t)e * D.ctot_stride + c + 1] = incl;
+}
 
 __global__ void __launch_bounds__(256) is_multi_norm_kernel(Problem P, DeviceState D)
 {
@@ -2291,6 +2417,43 @@ __device__ uint64_t hist_hash_counts(const Problem& P, const uint32_t* rec, uint
     return h;
 }
 
+// The same for the tabular model's records (Problem::hist == 2): cell (s*A + a)*S + s' of the transition table and phi_len + (a*S + s')*O + o
+// of the observation table per entry, over the dense prior (DeviceState::prior_dense).
+__device__ void tab_hist_next_cell(const Problem& P, const uint32_t* rec, uint32_t cnt, long long kmin, long long& nxt, int& mult)
+{
+    const int S = P.S, A = P.A, O = P.O;
+    nxt = 0x7fffffffffffffffll; mult = 0;
+    int j = 0;
+    for (int a = 0; a < A; ++a)
+        for (int q = 0; q < hist_count(cnt, a); ++q, ++j) {
+            const uint32_t en = rec[2 + j];
+            const int s0 = (int)(en & 0x3ffu), s1 = (int)((en >> 10) & 0x3ffu), ob = (int)(en >> 20);
+            const long long c[2] = {((long long)s0 * A + a) * S + s1, (long long)P.phi_len + ((long long)a * S + s1) * O + ob};
+#pragma unroll
+            for (int k = 0; k < 2; ++k)
+                if (c[k] >= kmin) {
+                    if (c[k] < nxt) { nxt = c[k]; mult = 1; }
+                    else if (c[k] == nxt) ++mult;
+                }
+        }
+}
+__device__ uint64_t tab_hist_hash_counts(const Problem& P, const float* prior, const uint32_t* rec, uint32_t len, uint64_t h)
+{
+    const long long dense = (long long)P.phi_len + (long long)P.A * P.S * P.O;
+    long long nxt;
+    int mult;
+    tab_hist_next_cell(P, rec, len, 0, nxt, mult);
+    for (long long k = 0; k < dense; ++k) {
+        float v = prior[k];
+        if (k == nxt) {
+            v = v + (float)mult;
+            tab_hist_next_cell(P, rec, len, k + 1, nxt, mult);
+        }
+        h = mix64(h ^ ((uint64_t)__float_as_uint(v) + ((uint64_t)k << 32)));
+    }
+    return h;
+}
+
 __global__ void __launch_bounds__(256) flush_kernel(Problem P, DeviceState D)
 {
     __shared__ unsigned long long s_sum;
@@ -2321,7 +2484,8 @@ __global__ void __launch_bounds__(256) flush_kernel(Problem P, DeviceState D)
                 else v = packed_ftiger_view<4>(P, GlobalView{cnt}).at(k);
                 h = mix64(h ^ ((uint64_t)__float_as_uint(v) + ((uint64_t)k << 32)));
             }
-        } else if (P.hist) h = hist_hash_counts(P, reinterpret_cast<const uint32_t*>(cnt), D.hist_cnt[e], h);
+        } else if (P.hist == 2) h = tab_hist_hash_counts(P, D.prior_dense, reinterpret_cast<const uint32_t*>(cnt), D.hist_cnt[e], h);
+        else if (P.hist) h = hist_hash_counts(P, reinterpret_cast<const uint32_t*>(cnt), D.hist_cnt[e], h);
         else if (P.packed) {  // the checksum is over the counts themselves, whatever the storage (PackedView)
             const PackedView<GlobalView> pv{GlobalView{cnt}, D.prior_dense};
             const int dense = P.phi_len + P.A * P.S * P.O;
@@ -2497,7 +2661,8 @@ static void launch_importance_multi(const Problem& P, const DeviceState& D, int 
     const int nchunks = (P.N + 255) / 256;
     const dim3 cgrid(ceil_div(nchunks, 4), count), eg(ceil_div(count, 64));
     const int32_t* list = D.use_list ? D.slot_list : nullptr;
-    if (P.hist) {
+    if (P.hist == 2) hipLaunchKernelGGL(is_multi_tab_step_kernel, cgrid, dim3(256), 0, st, P, D);   // (tabular records: sparse prior rows from L2)
+    else if (P.hist) {
         // the prior's rows from LDS where the deduplicated blob exists (rows of K floats, K as upload_prior chose it) -- FBA_HIST_ROWS=hbm: from L2
         const bool rows_hbm = D.ab_rows_hbm != 0;
         const int K = P.hist_row <= 8 ? 8 : (P.hist_row <= 10 ? 12 : 0);
@@ -2547,6 +2712,12 @@ void launch_belief_update(const Problem& P, const DeviceState& D, hipStream_t st
         const int ft = (P.model == FBA_MODEL_BA_FACTORED && !P.dirichlet_regular &&
                         (P.domain == FBA_DOM_FTIGER_EPISODIC || P.domain == FBA_DOM_FTIGER_CONTINUOUS))
                            ? 31 - __builtin_clz((unsigned)P.S) : 0;  // S = 2^FS
+        if (P.hist == 2) {   // tabular history particles (fba_create: the plain filter, expected Dirichlet)
+            const auto launch = [&](const DeviceState& Dc, int cnt) { hipLaunchKernelGGL(reject_tab_hist_kernel, dim3(cnt), dim3(REJECT_BLOCK), 0, st, P, Dc); };
+            if (D.single_rec) for_each_chunk(P, D, st, launch, D.need_update);
+            else launch(D, P.E);
+            return;
+        }
         if (P.hist) {   // (fba_create: the plain filter, expected Dirichlet)
             const int K = P.hist_row <= 8 ? 8 : (P.hist_row <= 10 ? 12 : 0);
             const bool lrows = P.hist_lds && K > 0 && !D.ab_rows_hbm;   // the prior's rows from LDS (FBA_HIST_ROWS=hbm: from L2)
@@ -2580,6 +2751,11 @@ void launch_belief_update(const Problem& P, const DeviceState& D, hipStream_t st
     if (P.cheat) {  // rejectSample on the correct-graph filter first (CheatingReinvigoration.cpp:111)
         if (P.dirichlet_regular) hipLaunchKernelGGL((reject_kernel<true, 0>), dim3(P.E), dim3(REJECT_BLOCK), 0, st, P, D, 1);
         else hipLaunchKernelGGL((reject_kernel<false, 0>), dim3(P.E), dim3(REJECT_BLOCK), 0, st, P, D, 1);
+    }
+    if (P.hist == 2) {   // tabular history particles: the update is always the multi-launch one (is_multi_tab_step_kernel), one slot or many
+        if (D.single_rec) for_each_chunk(P, D, st, [&](const DeviceState& Dc, int cnt) { launch_importance_multi(P, Dc, cnt, st); }, D.need_update);
+        else launch_importance_multi(P, D, P.E, st);
+        return;
     }
     if (!D.is_multi) {
         if (D.single_rec)

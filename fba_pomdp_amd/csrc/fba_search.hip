@@ -847,13 +847,22 @@ __global__ void __launch_bounds__(1024) search_order_kernel(Problem P, DeviceSta
 template <int K, bool LROWS>
 __global__ void __launch_bounds__(H2_BLOCK) __attribute__((amdgpu_waves_per_eu(FBA_HIST2_WAVES, FBA_HIST2_WAVES))) search_hist2_kernel(Problem P, DeviceState D)
 {
-    constexpr bool FLAT = false;
+    constexpr bool FLAT = false, TAB = false;
 #include "fba_search_hist2.inc"
 }
 template <int K, bool LROWS>
 __global__ void __launch_bounds__(H2_BLOCK) __attribute__((amdgpu_waves_per_eu(FBA_HIST2_WAVES, FBA_HIST2_WAVES))) hist2_flat_search(Problem P, DeviceState D)
 {
-    constexpr bool FLAT = true;
+    constexpr bool FLAT = true, TAB = false;
+#include "fba_search_hist2.inc"
+}
+// The same search on the records of the tabular gridworld BA-POMDP (Problem::hist == 2), for the two root samples.  K and LROWS name no rows
+// here: the step reads the prior's sparse rows (TabRows) from L2, and the workgroup stages no shared tables.
+template <bool FLATV>
+__global__ void __launch_bounds__(H2_BLOCK) __attribute__((amdgpu_waves_per_eu(FBA_HIST2_WAVES, FBA_HIST2_WAVES))) search_tabhist_kernel(Problem P, DeviceState D)
+{
+    constexpr bool FLAT = FLATV, TAB = true, LROWS = false;
+    constexpr int K = 8;
 #include "fba_search_hist2.inc"
 }
 
@@ -898,6 +907,19 @@ void launch_search(const Problem& P, const DeviceState& D, hipStream_t st)
     if (P.hist) {  // history particles (gridworld FBA-POMDP): four lanes per tree
         lds = (size_t)depth_cap * HIST_TREES * (sizeof(double) + sizeof(int32_t) + sizeof(float) + sizeof(int32_t)) + (size_t)P.Cs * HIST_TREES * sizeof(float);
         const dim3 qgrid(ceil_div(P.E, HIST_TREES));
+        if (D.bkt && P.hist == 2) {   // tabular records (fba_create gives them the bucket tree only)
+            int nw = H2_WAVES;
+            while (nw > 1 && (size_t)nw * h2_wave_bytes(P) > 64 * 1024) nw >>= 1;
+            const size_t lds2 = (size_t)nw * h2_wave_bytes(P);
+            const dim3 grid2(ceil_div(P.E, HIST_TREES * nw)), block2(64 * nw);
+            if (D.ab_lockstep) hipLaunchKernelGGL(search_order_kernel, dim3(1), dim3(1024), 0, st, P, D);
+            const void* kfn = P.belief == FBA_BELIEF_REJECTION ? reinterpret_cast<const void*>(&search_tabhist_kernel<true>)
+                                                               : reinterpret_cast<const void*>(&search_tabhist_kernel<false>);
+            if (lds2 > 64 * 1024) (void)hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
+            if (P.belief == FBA_BELIEF_REJECTION) hipLaunchKernelGGL(search_tabhist_kernel<true>, grid2, block2, lds2, st, P, D);
+            else hipLaunchKernelGGL(search_tabhist_kernel<false>, grid2, block2, lds2, st, P, D);
+            return;
+        }
         if (D.bkt) {   // the tree as one table of buckets, trips to memory requested an iteration ahead
             const bool no_lrows = D.ab_rows_hbm != 0;   // A/B: transition rows from the padded tables
             const bool lrows = P.hist_lds != nullptr && !no_lrows;

@@ -1,11 +1,13 @@
 // fba_search_hist2.inc -- the body of search_hist2_kernel and hist2_flat_search (fba_search.hip), which include it inside their braces
-// with `constexpr bool FLAT` set (true: the root particle of a plain rejection filter).  Not a header: it is only valid there.
+// with `constexpr bool FLAT` set (true: the root particle of a plain rejection filter), and of search_tabhist_kernel / tabhist_flat_search
+// with `constexpr bool TAB` set (the tabular model's records, Problem::hist == 2: one step per iteration, gridworld_tab_hist_step, on
+// every lane of the quad; no shared tables).  Not a header: it is only valid there.
     constexpr int AMAX = 4;
-    P.model = FBA_MODEL_BA_FACTORED; P.domain = FBA_DOM_GRIDWORLD; P.A = 4; P.belief = FLAT ? FBA_BELIEF_REJECTION : FBA_BELIEF_IMPORTANCE;
+    P.model = TAB ? FBA_MODEL_BA_TABLE : FBA_MODEL_BA_FACTORED; P.domain = FBA_DOM_GRIDWORLD; P.A = 4; P.belief = FLAT ? FBA_BELIEF_REJECTION : FBA_BELIEF_IMPORTANCE;
     extern __shared__ double lds_all[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, tl = lane >> 2;
     const int depth_cap = P.max_depth > 0 ? P.max_depth : 1;
-    const size_t shared_bytes = h2_shared_bytes(P, LROWS);
+    const size_t shared_bytes = TAB ? 0 : h2_shared_bytes(P, LROWS);
     double* lds = reinterpret_cast<double*>(reinterpret_cast<char*>(lds_all) + shared_bytes + (size_t)wave * h2_wave_bytes(P));   // this wave's paths and staging area
     double* path_q   = lds + tl;                                                                                  // [depth][trees]: the chosen action's Q as the descent saw it
     int32_t* path_n  = reinterpret_cast<int32_t*>(path_q - tl + (size_t)depth_cap * HIST_TREES) + tl;            // ... and its count
@@ -163,7 +165,7 @@
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // the other lanes' pieces (LDS operations of one wave complete in order)
             hist_mask = stage[1 * HIST_TREES];
-            sp        = (hist_mask >> 16) & 0x3ffu;
+            sp        = TAB ? stage[0] : (hist_mask >> 16) & 0x3ffu;   // (tabular records: the state index of word 0)
             node = ROOT; dtg = max_tree_depth; plen = 0; mode = 1; pend = false;
         } else if (mode == 1 && pend) {
             // traverseChanceNode's child lookup (POUCT.cpp:224-246), answered by the line requested an iteration ago
@@ -285,6 +287,45 @@
         PROF_MARK(1)
         if (do_step) {
 #endif
+          if constexpr (TAB) {
+            // BAPOMDP::step over BAFlatModel (sim_step's tabular branch) on the staged record, the same on the four lanes: T(s, a, .) with the
+            // step's first draw, O(a, s', .) with its second.  A rollout never looks at an observation (POUCT.cpp:273-303): its row is not walked,
+            // its draw is skipped.
+            const uint32_t* listA = stage + (size_t)(2 + hist_offset(hist_cnt, a)) * HIST_TREES;
+            const int nA = hist_count(hist_cnt, a), NW = P.gw_N, GW = P.gw_G, s = (int)sp;
+            const TabRows T(P);
+            const int ns = tab_row_sample<HIST_TREES>(T, s * 4 + a, listA, nA, (uint32_t)s, 0, 10, u01_of(g.at(g.draw)), P.S);
+            const bool found = gridworld_on_goal(P, (s / (NW * GW)) * NW + (s / GW) % NW, s % GW);  // terminal and reward from the OLD state
+            if (mode == 1) {  // traverseChanceNode
+                o    = tab_row_sample<HIST_TREES>(T, 4 * P.S + a * P.S + ns, listA, nA, (uint32_t)ns, 10, 20, u01_of(g.at(g.draw + 1u)), P.O);
+                r    = found ? 1 : 0;
+                term = found;
+                g.draw += 2;
+                ++steps;
+                sp = (uint32_t)ns;
+                path_r[(size_t)plen * HIST_TREES]  = (float)r;
+                path_na[(size_t)plen * HIST_TREES] = (node << 5) | a;
+                ++plen;
+                if (term) finish = true;
+                else {   // ask for the child's line; it is looked at when this loop comes round again
+                    const uint32_t code = ((uint32_t)node * 4u + (uint32_t)a) * (uint32_t)P.O + (uint32_t)o;
+                    pk    = ekey | code;
+                    pline = h2_home_line(code, nlines);
+                    const uint4* lp = tab + (size_t)pline * 8;
+                    pf[0] = lp[g.q];
+                    pf[1] = lp[4 + g.q];
+                    pend  = true;
+                }
+            } else {          // a rollout step
+                rret += (found ? 1.0 : 0.0) * rdisc;
+                rdisc *= P.gamma;
+                --rdepth;
+                ++steps;
+                g.draw += 2;
+                sp = (uint32_t)ns;
+                if (rdepth == 0 || found) { delayed = rret; finish = true; }
+            }
+          } else {
             // BAPOMDP::step over BABNModel (BAPOMDP.cpp:111-143, BABNModel.cpp:292-325) as two passes of hist_row_pass.  Pass A: the transition rows
             // of (state, a) for every lane.  Pass B: the observation rows of (a, s') for the trees that are in their tree -- and, for the trees that are
             // in a rollout, the transition rows of the NEXT step: a rollout never looks at an observation (POUCT.cpp:273-303 uses reward and terminal
@@ -371,6 +412,7 @@
                 sp = hist_pack(v0, v1, v2);
                 if (rdepth == 0 || found2) { delayed = rret; finish = true; }
             }
+          }
         }
         PROF_MARK(2)
         PROF_MARK(3)

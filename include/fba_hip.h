@@ -201,8 +201,10 @@ int fba_particle_bytes(const fba_ctx* ctx); /* HBM bytes of one particle record.
                                              * prior allows it exactly.  Gridworld FBA-POMDP particles are stored as histories of
                                              * their own steps over the shared prior (8 B + 4 B per real step instead of 191 KB at
                                              * --size 7) under the importance filter, and under the plain rejection filter where
-                                             * the planner is po-uct or random with at most 65 536 simulations; such contexts refuse
-                                             * fba_belief_set of states or counts.  FBA_DENSE_PARTICLES=1 in the environment forces
+                                             * the planner is po-uct or random with at most 65 536 simulations.  The tabular gridworld
+                                             * BA-POMDP stores them the same way (8 B + 4 B per real step instead of 7.68 MB at
+                                             * --size 7) under both filters where the planner is po-uct or random with at most 65 536
+                                             * simulations.  Such contexts refuse fba_belief_set of states or counts.  FBA_DENSE_PARTICLES=1 in the environment forces
                                              * fp32 counts.  fba_belief_get / fba_belief_set always speak fp32 counts. */
 int fba_slots(const fba_ctx* ctx);      /* slots actually resident (cfg.slots, or the library's choice) */
 
