@@ -330,6 +330,8 @@ struct Problem {
                         // 4-byte entry per real step over the shared prior tables (HistView below); C = 0 then, hist_cap entries per record.
                         // 2 = the same records for the TABULAR gridworld BA-POMDP (TabRows below): entries of state indices, and
                         // hist_base points at the prior's sparse rows instead (hist_alt, hist_lds unused)
+                        // 3 = records of the collision-avoidance FBA-POMDP in the prior's own graph (CaTables below): hist_base is the dense
+                        // prior table, hist_lds its inexact-cell ids and sequence table, hist_row the number of its cells
     int32_t hist_cap;
     int32_t hist_compact;   // records of short histories stand closer than Cs words (hist_stride below)
     int32_t gw_N, gw_G;          // gridworld: N, number of goals (copies of GridDesc's, as kernel arguments)
@@ -1547,6 +1549,162 @@ __device__ __forceinline__ bool gridworld_tab_hist_step(const Problem& P, const 
     entry = hist_entry((uint32_t)s, (uint32_t)ns, (uint32_t)o);
     s     = ns;
     return found;
+}
+
+// ---- history particles of the collision-avoidance FBA-POMDP in the prior's own graph (Problem::hist == 3) ---------
+// The record is the one above -- word 0 the domain state, word 1 not read, words 2.. one entry per real step, grouped by action
+// through DeviceState::hist_cnt (A = 3) -- and an entry holds what ca_fact_step's 4 + 2n increments need, 3 bits a field
+// (W, H <= 8, n <= 2 obstacles: 12 + 9n <= 30 bits):
+//   x | x' << 3 | y << 6 | y' << 9 | per obstacle k: b_k << (12 + 9k) | b'_k << (15 + 9k) | o_k << (18 + 9k)
+// T(x) is incremented at row x, cell x'; T(y) and T(obstacle k) likewise; O(a, k) at the row of the OLD position b_k, cell o_k (the
+// observation the step drew).  The whole dense prior (ncounts floats, at most 1152: 4.5 KB) sits in LDS in every kernel that steps.
+// Unlike the gridworld formats this one does not need prior + (float)j to be the float that j additions of 1.0f reach: the tails
+// of the rounded-normal observation rows (0.0002, 0.0338, 0.034 at H = 7) are not such values.  The host tabulates, for every
+// distinct prior value v that fails the test, seq[j] = v after j additions of 1.0f, j <= hist_cap + 1; a cell holds in `sid` 0
+// (exact: prior + j) or 1 + the row of that table.  At most CA_HIST_MAX_SEQ such values (4 KB of LDS at the longest record); a prior
+// with more stays dense.
+//   Problem::hist_base  the dense prior table [ncounts]
+//   Problem::hist_lds   [hist_rid_bytes] one byte per cell (sid), then [hist_distinct][hist_cap + 2] floats (seq)
+constexpr int CA_HIST_MAX_SEQ = 8;
+__host__ __device__ __forceinline__ int ca_hist_ncounts(int A, int W, int H, int n) { return A * (W * W + H * H * (1 + n)) + A * n * H * H; }
+struct CaTables {
+    const float* prior; const uint8_t* sid; const float* seq; int seqlen;
+    // the count of cell k after m increments
+    __device__ __forceinline__ float at(int k, int m) const
+    {
+        const int id = sid[k];
+        return id ? seq[(id - 1) * seqlen + m] : prior[k] + (float)m;
+    }
+};
+// the tables staged at `lds` (16-byte aligned) by every thread of a workgroup of `nthreads`; returns the bytes they take
+__device__ __forceinline__ int ca_hist_stage_tables(const Problem& P, int ncounts, void* lds, int tid, int nthreads, CaTables& T)
+{
+    const int nc4 = (ncounts + 3) & ~3, blob = P.hist_rid_bytes + ((P.hist_distinct * (P.hist_cap + 2) * 4 + 15) & ~15);
+    uint4* dst = reinterpret_cast<uint4*>(lds);
+    const uint4* pr = reinterpret_cast<const uint4*>(P.hist_base);
+    const uint4* bl = reinterpret_cast<const uint4*>(P.hist_lds);
+    for (int i = tid; i < nc4 / 4; i += nthreads) dst[i] = pr[i];
+    for (int i = tid; i < blob / 16; i += nthreads) dst[nc4 / 4 + i] = bl[i];
+    T.prior  = reinterpret_cast<const float*>(lds);
+    T.sid    = reinterpret_cast<const uint8_t*>(T.prior + nc4);
+    T.seq    = reinterpret_cast<const float*>(T.sid + P.hist_rid_bytes);
+    T.seqlen = P.hist_cap + 2;
+    return nc4 * 4 + blob;
+}
+__host__ __device__ __forceinline__ size_t ca_hist_table_bytes(int ncounts, int rid_bytes, int distinct, int cap)
+{
+    return (size_t)((ncounts + 3) & ~3) * 4 + (size_t)rid_bytes + (size_t)((distinct * (cap + 2) * 4 + 15) & ~15);
+}
+template <int STRIDE>
+struct StridedEntries {
+    const uint32_t* p;
+    __device__ __forceinline__ uint32_t at(int t) const { return p[t * STRIDE]; }
+};
+// a Dirichlet row of at most 8 cells in registers: cell i = the prior's cell off + i after its 8-bit field of `hits` increments
+struct CaRow {
+    float r[8];
+    __device__ __forceinline__ CaRow(const CaTables& T, int off, int len, uint64_t hits)
+    {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) r[i] = i < len ? T.at(off + i, (int)((hits >> (8 * i)) & 0xffull)) : 0.f;
+    }
+    // sampleFromExpectedMult (random.cpp:244-255): double total, float CDF against u * total, fall-through to the last cell
+    __device__ __forceinline__ int sample(double u, int len) const
+    {
+        double total = (double)r[0];
+#pragma unroll
+        for (int i = 1; i < 8; ++i)
+            if (i < len) total += (double)r[i];
+        const double p = u * total;
+        float sum = r[0];
+        int pick  = len - 1;
+        bool done = false;
+#pragma unroll
+        for (int i = 1; i < 8; ++i)
+            if (i < len && !done) {
+                if (p < (double)sum) { pick = i - 1; done = true; }
+                else sum += r[i];
+            }
+        return pick;
+    }
+    // expectedMult(row)[o]: float sum, float division (fact_obs_prob)
+    __device__ __forceinline__ float prob(int len, int o) const
+    {
+        float sum = r[0], mine = o == 0 ? r[0] : 0.f;
+#pragma unroll
+        for (int i = 1; i < 8; ++i)
+            if (i < len) { sum += r[i]; mine = (i == o) ? r[i] : mine; }
+        return ((double)sum <= 1e-300) ? 0.0f : mine / sum;
+    }
+};
+__device__ __forceinline__ uint64_t ca_hit(bool hit, uint32_t cell) { return (uint64_t)(hit ? 1u : 0u) << (8 * cell); }
+// BAPOMDP::step over BABNModel for the collision-avoidance FBA-POMDP on a history particle, one lane: the draws, their order and
+// every row value are those of ca_fact_step on the dense table through sample_expected_mult.  `ent` = the particle's n_ent entries
+// of action a; returns the step's entry and, with PROB, P(real_o | a, s') from the counts after the step's own increments
+// (fact_obs_prob over PendingIncView).
+template <bool PROB, class ENT>
+__device__ __forceinline__ bool ca_hist_step(const Problem& P, Rng& g, const CaTables& T, const ENT& ent, int n_ent, int& s, int a, int& o, double& r,
+                                             uint32_t& entry, int real_o, double& prob)
+{
+    const CADesc* ca = P.ca;
+    const int W = ca->W, H = ca->H, n = ca->n, Hn = ca->Hn, A = P.A;
+    const int tsize = W * W + H * H * (1 + n), tbase = a * tsize, obase = A * tsize + a * n * H * H;
+    const int x = s / (H * Hn), y = (s / Hn) % H, packed = s % Hn;
+    const bool two = n == 2;
+    const int b0 = two ? packed / H : packed, b1 = two ? packed % H : 0;
+    // pass 1: the increments this particle has made to the rows T(a, .)(own value)
+    uint64_t hx = 0, hy = 0, h0 = 0, h1 = 0;
+    for (int j = 0; j < n_ent; ++j) {
+        const uint32_t en = ent.at(j);
+        hx += ca_hit((int)(en & 7u) == x, (en >> 3) & 7u);
+        hy += ca_hit((int)((en >> 6) & 7u) == y, (en >> 9) & 7u);
+        h0 += ca_hit((int)((en >> 12) & 7u) == b0, (en >> 15) & 7u);
+        h1 += ca_hit(two && (int)((en >> 21) & 7u) == b1, (en >> 24) & 7u);
+    }
+    const int nx  = CaRow(T, tbase + x * W, W, hx).sample(g.u01(), W);
+    const int ny  = CaRow(T, tbase + W * W + y * H, H, hy).sample(g.u01(), H);
+    const int nb0 = CaRow(T, tbase + W * W + H * H + b0 * H, H, h0).sample(g.u01(), H);
+    int nb1 = 0;
+    if (two) nb1 = CaRow(T, tbase + W * W + 2 * H * H + b1 * H, H, h1).sample(g.u01(), H);
+    const int ns = (nx * H + ny) * Hn + (two ? nb0 * H + nb1 : nb0);
+    // pass 2: the increments to the rows O(a, k)(new position); a step increments them at the row of the position it STARTED from
+    uint64_t q0 = 0, q1 = 0;
+    for (int j = 0; j < n_ent; ++j) {
+        const uint32_t en = ent.at(j);
+        q0 += ca_hit((int)((en >> 12) & 7u) == nb0, (en >> 18) & 7u);
+        q1 += ca_hit(two && (int)((en >> 21) & 7u) == nb1, (en >> 27) & 7u);
+    }
+    const int ob0 = CaRow(T, obase + nb0 * H, H, q0).sample(g.u01(), H);
+    int ob1 = 0;
+    if (two) ob1 = CaRow(T, obase + H * H + nb1 * H, H, q1).sample(g.u01(), H);
+    o = two ? ob0 * H + ob1 : ob0;
+    if (PROB) {
+        // the step's own observation increments are part of the rows read here only where the obstacle kept its position
+        q0 += ca_hit(b0 == nb0, (uint32_t)ob0);
+        q1 += ca_hit(two && b1 == nb1, (uint32_t)ob1);
+        double pr = 1;
+        pr *= CaRow(T, obase + nb0 * H, H, q0).prob(H, two ? real_o / H : real_o);
+        if (two) pr *= CaRow(T, obase + H * H + nb1 * H, H, q1).prob(H, real_o % H);
+        prob = pr;
+    }
+    entry = (uint32_t)x | ((uint32_t)nx << 3) | ((uint32_t)y << 6) | ((uint32_t)ny << 9) | ((uint32_t)b0 << 12) | ((uint32_t)nb0 << 15) |
+            ((uint32_t)ob0 << 18) | (two ? ((uint32_t)b1 << 21) | ((uint32_t)nb1 << 24) | ((uint32_t)ob1 << 27) : 0u);
+    const bool t = ext_terminal(P, s, a, ns);
+    r            = ext_reward(P, s, a, ns);
+    s            = ns;
+    return t;
+}
+// the 4 + 2n dense cells entry `en` of action a incremented (host: fba_belief_get; device: the belief checksum)
+__host__ __device__ __forceinline__ void ca_hist_cells(int A, int W, int H, int n, int a, uint32_t en, int (&c)[6])
+{
+    const int tsize = W * W + H * H * (1 + n), tbase = a * tsize, obase = A * tsize + a * n * H * H;
+    c[0] = tbase + (int)(en & 7u) * W + (int)((en >> 3) & 7u);
+    c[1] = tbase + W * W + (int)((en >> 6) & 7u) * H + (int)((en >> 9) & 7u);
+    for (int k = 0; k < 2; ++k) {
+        const uint32_t f = en >> (12 + 9 * k);
+        c[2 + k] = k < n ? tbase + W * W + H * H * (1 + k) + (int)(f & 7u) * H + (int)((f >> 3) & 7u) : -1;
+        c[4 + k] = k < n ? obase + k * H * H + (int)(f & 7u) * H + (int)((f >> 6) & 7u) : -1;
+    }
 }
 
 // ---- the same step shared by the four lanes of a quad (search_hist_kernel) ---------------------------------------

@@ -848,6 +848,31 @@ bool increments_exact(const std::vector<float>& table, int most)
     return true;
 }
 
+// Collision-avoidance history particles (CaTables, fba_device.h): which cells of the prior are not exact under prior + (float)j, j <= most,
+// and for every distinct value among them the floats that j additions of 1.0f reach.  sid[k] = 0 (exact) or 1 + the row of `seq`
+// ([rows][most + 1]).  False when a count is negative or more than CA_HIST_MAX_SEQ distinct values need a row.
+bool ca_hist_sequences(const std::vector<float>& table, int ncounts, int most, std::vector<uint8_t>& sid, std::vector<float>& seq)
+{
+    sid.assign((size_t)ncounts, 0);
+    seq.clear();
+    std::vector<float> values;
+    for (int k = 0; k < ncounts; ++k) {
+        const float v = table[(size_t)k];
+        if (!(v >= 0.f)) return false;
+        if (increments_exact(std::vector<float>{v}, most)) continue;
+        size_t id = 0;
+        while (id < values.size() && std::memcmp(&values[id], &v, 4) != 0) ++id;
+        if (id == values.size()) {
+            if (values.size() >= (size_t)CA_HIST_MAX_SEQ) return false;
+            values.push_back(v);
+            float run = v;
+            for (int j = 0; j <= most; ++j) { seq.push_back(run); run += 1.0f; }
+        }
+        sid[(size_t)k] = (uint8_t)(id + 1);
+    }
+    return true;
+}
+
 // The sparse rows of a tabular prior (TabRows, fba_device.h): row offsets, then {column, fp32 count} pairs of the nonzero columns, ascending
 std::vector<uint32_t> tab_sparse_rows(const Problem& P, const std::vector<float>& prior)
 {
@@ -889,6 +914,26 @@ int upload_prior(fba_ctx* c)
         HIPCHK(c, hipMemcpyAsync(c->d_prior_dense, c->prior.data(), c->prior.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));   // (rows is a local)
         c->P.hist_base = reinterpret_cast<const float*>(c->d_tab_rows);
+    } else if (c->P.hist == 3) {
+        // collision-avoidance records: the dense prior table (staged in LDS by every kernel that steps; fba_belief_get and the belief
+        // checksum read it too) and, beside it, which of its cells are inexact under prior + j and their sequences (CaTables)
+        std::vector<uint8_t> sid;
+        std::vector<float> seq;
+        const int nc = c->fdesc.ncounts;
+        if (!ca_hist_sequences(c->prior, nc, c->P.hist_cap + 1, sid, seq))
+            return fail(c, FBA_EINVAL, "this context stores particles as histories over the prior table, which holds at most %d distinct counts c for which "
+                                       "c + j is not exact in fp32; create it with FBA_DENSE_PARTICLES=1 in the environment for other tables", CA_HIST_MAX_SEQ);
+        const int rid_bytes = (nc + 15) & ~15;
+        std::vector<uint8_t> blob((size_t)rid_bytes + (size_t)CA_HIST_MAX_SEQ * (c->P.hist_cap + 2) * sizeof(float) + 16, 0);
+        std::copy(sid.begin(), sid.end(), blob.begin());
+        if (!seq.empty()) std::memcpy(blob.data() + rid_bytes, seq.data(), seq.size() * sizeof(float));
+        HIPCHK(c, hipMemcpyAsync(c->d_hist_lds, blob.data(), blob.size(), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->d_prior_dense, c->prior.data(), (size_t)nc * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // (blob is a local)
+        c->P.hist_base      = c->d_prior_dense;
+        c->P.hist_lds       = c->d_hist_lds;
+        c->P.hist_rid_bytes = rid_bytes;
+        c->P.hist_distinct  = (int)(seq.size() / (size_t)(c->P.hist_cap + 2));
     } else if (c->P.hist) {  // records carry no counts: the tables sit beside them, rows padded to 16 bytes (HistLayout, fba_device.h)
         const HistLayout L(c->gdesc.N, c->gdesc.G, c->P.A);
         const int N = L.N, G = L.G, A = L.A, XYd = N * N * G * N, GGd = N * N * G * G, NNd = N * N;
@@ -1552,6 +1597,34 @@ int fba_create(const fba_config* cfg, fba_ctx** out)
             P.C        = 0;  // word 0 = state, word 1 = structure bits, words 2.. = entries
         }
     }
+    // The collision-avoidance FBA-POMDP in the prior's own graph (no structure prior: ca_fact_step's contexts) stores them too under the plain
+    // importance filter where that filter is the multi-launch one (P.hist = 3: entries of 12 + 9n bits, the whole prior in LDS -- 328 B instead of
+    // 3.5 KB at 7 x 7 with two obstacles and 80 steps), where the planner is po-uct or random, the grid fits 3-bit fields (W, H <= 8, n <= 2), the
+    // run fits the record and the search's LDS (tables, path, one staged record per lane) fits a workgroup.  The prior need not be exact under
+    // "+ j": cells that are not read their count from a table of sequential sums (ca_hist_sequences), at most CA_HIST_MAX_SEQ distinct values;
+    // other priors stay dense.  Their update exists as the multi-launch filter only (is_multi_ca_step_kernel and the launches behind it), so the
+    // format is used exactly where the dense records take that filter too (D.is_multi below: more than IS_MAX_CHUNKS * 256 particles, or from
+    // FBA_IS_MULTI_MIN up where that is set).  Up to 65 536 particles the records stay dense on the one-launch importance_kernel, as before.
+    const int ca_hist_min = std::getenv("FBA_IS_MULTI_MIN") ? std::max(1, std::atoi(std::getenv("FBA_IS_MULTI_MIN"))) : IS_MAX_CHUNKS * 256 + 1;
+    if (cfg->model == FBA_MODEL_BA_FACTORED && is_ca(cfg->domain) && cfg->belief == FBA_BELIEF_IMPORTANCE && !point && cfg->particles >= ca_hist_min &&
+        (cfg->planner == FBA_PLANNER_POUCT || cfg->planner == FBA_PLANNER_RANDOM) && !cfg->dirichlet_regular && !std::getenv("FBA_DENSE_PARTICLES") &&
+        c->fdesc.nvar == 0 && c->fdesc.nodes[2].nmax == 1 && !P.nested && !P.mh && !P.cheat && !P.incub && !P.reinvig &&
+        (long long)cfg->episodes * cfg->horizon <= HIST_MAX_CAP && (long long)cfg->episodes * cfg->horizon >= 1 &&
+        c->cadesc.W <= 8 && c->cadesc.H <= 8 && c->cadesc.n >= 1 && c->cadesc.n <= 2 && P.A == 3) {
+        const int cap = cfg->episodes * cfg->horizon, nc = c->fdesc.ncounts;
+        std::vector<uint8_t> sid;
+        std::vector<float> seq;
+        Problem Q = P;
+        Q.hist_row = nc; Q.hist_rid_bytes = (nc + 15) & ~15; Q.hist_distinct = CA_HIST_MAX_SEQ; Q.hist_cap = cap; Q.Cs = (2 + cap + 3) & ~3;
+        if (nc == ca_hist_ncounts(P.A, c->cadesc.W, c->cadesc.H, c->cadesc.n) && ca_hist_sequences(c->prior, nc, cap + 1, sid, seq) &&
+            ca_hist_search_lds(Q) <= 64 * 1024) {
+            P.hist     = 3;
+            P.hist_cap = cap;
+            P.hist_row = nc;   // (for these records: the cells of the prior table)
+            P.gw_N = 1; P.gw_G = 1;   // (init_kernel / reset_kernel pack the state into word 1 with these; nothing reads that word here)
+            P.C        = 0;    // word 0 = state, word 1 unused, words 2.. = entries
+        }
+    }
     P.hist_compact = P.hist && !(std::getenv("FBA_HIST_STRIDE") && !std::strcmp(std::getenv("FBA_HIST_STRIDE"), "full")) ? 1 : 0;   // (A/B switch: every record at the full stride)
     if (P.hist) P.Cs = (2 + P.hist_cap + 3) & ~3;
     else if (P.ft_packed) P.Cs = (P.C + 1 + 3) & ~3;   // 36 words at --size 3: the point is the bytes, not a power of two
@@ -1632,7 +1705,7 @@ int fba_create(const fba_config* cfg, fba_ctx** out)
     D.bkt = nullptr; D.bkt_lines = 0; D.s_root = nullptr; D.search_order = nullptr;
     size_t bkt_lines = 0;
     const bool force_records = hist_records_tree;
-    if (P.hist && P.sims <= 65536 && !force_records) {
+    if (P.hist && P.hist != 3 && P.sims <= 65536 && !force_records) {   // (collision-avoidance records: search_kernel's node records)
         long long buckets = cfg->tree_buckets > 0 ? cfg->tree_buckets : 2ll * (P.sims + 2);
         buckets = std::max(buckets, 8ll);
         const long long fit = (1ll << 28) / (4ll * P.O) - 2;   // ((buckets * 4 + 3) * O + O - 1 < 2^28: the root's "bucket" is index `buckets`)
@@ -1641,7 +1714,7 @@ int fba_create(const fba_config* cfg, fba_ctx** out)
             bkt_lines = (size_t)((buckets + 1) / 2);
         }
     }
-    if (cfg->tree_buckets < 0 || (cfg->tree_buckets > 0 && !bkt_lines && P.hist && !force_records)) {
+    if (cfg->tree_buckets < 0 || (cfg->tree_buckets > 0 && !bkt_lines && P.hist && P.hist != 3 && !force_records)) {
         fail(nullptr, FBA_EINVAL, "tree_buckets = %d: not a size this context's search can use (history-particle searches of at most 65536 "
              "simulations, keys of 28 bits)", cfg->tree_buckets);
         fba_destroy(c);
@@ -1818,7 +1891,7 @@ int fba_create(const fba_config* cfg, fba_ctx** out)
     CHK(dev_alloc(c, &c->d_n_active, 1));
     CHK(dev_alloc(c, &D.fault, 1));
     CHK(dev_alloc(c, &D.lazy_reset, E));
-    P.search_budget = (P.hist && cfg->search_budget > 0) ? cfg->search_budget : 0;   // (only search_hist_kernel parks and resumes)
+    P.search_budget = (P.hist && P.hist != 3 && cfg->search_budget > 0) ? cfg->search_budget : 0;   // (only search_hist_kernel parks and resumes)
     if (P.search_budget > 0) {
         CHK(dev_alloc(c, &D.s_sim, E));
         CHK(dev_alloc(c, &D.s_nodes, E));
@@ -1835,7 +1908,7 @@ int fba_create(const fba_config* cfg, fba_ctx** out)
     if (D.bkt && D.ab_lockstep) CHK(dev_alloc(c, &D.search_order, (size_t)E));
     if (!D.search_order) D.ab_lockstep = 0;   // (lock-step waves exist on the bucket tree only: search_hist2_kernel)
     CHK(dev_alloc(c, &c->d_prior, P.Cs));
-    CHK(dev_alloc(c, &c->d_prior_dense, std::max(c->dense_C, 1)));
+    CHK(dev_alloc(c, &c->d_prior_dense, std::max(c->dense_C, 1) + 4));   // (+4: staged in 16-byte pieces)
     if (P.hist == 1) {
         const HistLayout L(c->gdesc.N, c->gdesc.G, P.A);
         CHK(dev_alloc(c, &c->d_hist_base, (size_t)L.total + 16));   // (+16: a row fetch may run up to a row width past the last row)
@@ -1844,6 +1917,7 @@ int fba_create(const fba_config* cfg, fba_ctx** out)
         P.hist_base = c->d_hist_base;
         P.hist_alt  = c->d_hist_alt;
     }
+    if (P.hist == 3) CHK(dev_alloc(c, &c->d_hist_lds, (size_t)((P.hist_row + 15) & ~15) + (size_t)CA_HIST_MAX_SEQ * (P.hist_cap + 2) * sizeof(float) + 16));
     CHK(dev_alloc(c, &c->d_uni_scan, (size_t)P.N + 1));
     CHK(dev_alloc(c, &c->d_log1p, (size_t)P.sims + 2));
     D.prior     = c->d_prior;
@@ -2026,7 +2100,8 @@ int fba_set_model_factored(fba_ctx* c, const fba_factored_layout* layout, const 
         return fail(c, FBA_EINVAL, "this context stores factored-tiger particles packed over the built-in prior; create it with "
                                    "FBA_DENSE_PARTICLES=1 in the environment to replace the prior");
     }
-    if (c->P.hist) {  // history particles read rows as prior + j: the new table must keep that exact (fba_create checked the built-in one)
+    if (c->P.hist && c->P.hist != 3) {  // history particles read rows as prior + j: the new table must keep that exact (fba_create checked the built-in one;
+                                        // collision-avoidance records: upload_prior rebuilds their sequence table or refuses)
         std::vector<float> only(c->prior.begin(), c->prior.begin() + mine.n_counts);
         if (!increments_exact(only, c->P.hist_cap + 1)) {
             c->prior = keep;
@@ -2151,6 +2226,19 @@ static void hist_materialize(const fba_ctx* c, const uint32_t* rec, uint32_t cnt
                 const uint32_t en = rec[2 + j], s0 = en & 0x3ffu, s1 = (en >> 10) & 0x3ffu, ob = en >> 20;
                 counts[((size_t)s0 * A + a) * S + s1] += 1.0f;
                 counts[(size_t)c->P.phi_len + ((size_t)a * S + s1) * O + ob] += 1.0f;
+            }
+        return;
+    }
+    if (c->P.hist == 3) {   // collision-avoidance records: 1.0f at each of the entry's 4 + 2n cells (ca_hist_cells), one addition at a time
+        const CADesc& ca = c->cadesc;
+        std::copy(c->prior.begin(), c->prior.begin() + c->fdesc.ncounts, counts);
+        int j = 0;
+        for (int a = 0; a < c->P.A; ++a)
+            for (int q = 0; q < hist_count(cnt, a); ++q, ++j) {
+                int cells[6];
+                ca_hist_cells(c->P.A, ca.W, ca.H, ca.n, a, rec[2 + j], cells);
+                for (int k = 0; k < 6; ++k)
+                    if (cells[k] >= 0) counts[cells[k]] += 1.0f;
             }
         return;
     }
@@ -2505,6 +2593,12 @@ int fba_get_kernel_times(fba_ctx* c, fba_kernel_time* out)
         // resample source, written once with its new entry (+4); the Dirichlet rows come from the shared tables
         // (tabular records, is_multi_tab_step_kernel: the same formula; their sparse prior rows are L2-resident and not counted)
         if (P.hist) out[FBA_K_BELIEF_IS].bytes = particles * 44 + entries * 12;
+        // collision-avoidance records (is_multi_ca_step_kernel and the launches behind it, at every filter size): per particle the weight read
+        // and written by the step (16), read by the normalisation (8), read again and its prefix sum written by the scan (16), one prefix sum
+        // read per draw at least and the new weight written (16), the side row {state, entry} written and read (16) = 72; the record -- 8
+        // bytes + 4 per entry -- read by the step, read as a resample source, written with its new entry (3 * 8 + 4 = 28 + 12 per entry).
+        // The prior and its sequence table sit in LDS and are not counted.
+        if (P.hist == 3) out[FBA_K_BELIEF_IS].bytes = particles * 100 + entries * 12;
         // packed tiger particles (64-byte records): the same formula on the bytes a packed particle has -- the update reads
         // state + weight + its two rows and writes state + weight + two counts (32 + Rt + Ro = 48), the resample reads the
         // weight and moves a record in and out (8 + 2 * 64)

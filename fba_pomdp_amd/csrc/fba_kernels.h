@@ -23,6 +23,13 @@ constexpr int MH_LDS_HEAD = MH_TERMS * 8 + 2 * MH_MAXVAR * 4 + 64 * 4;  // those
 inline bool mh_scratch_in_lds(int scratch_words) { return MH_LDS_HEAD + (size_t)scratch_words * 4 <= 64 * 1024; }  // else [E][words] in HBM
 constexpr int IS_LDS_MAX_N  = 8192;  // importance filters up to this many particles keep their weights and prefix sums in LDS (64 KB)
 
+// dynamic LDS of one search_ca_hist_kernel workgroup: the prior and sequence tables, then per lane the path and one staged record
+inline size_t ca_hist_search_lds(const Problem& P)
+{
+    const int depth_cap = P.max_depth > 0 ? P.max_depth : 1;
+    return ca_hist_table_bytes(P.hist_row, P.hist_rid_bytes, P.hist_distinct, P.hist_cap) + ((size_t)2 * depth_cap + P.Cs) * SEARCH_BLOCK * sizeof(uint32_t);
+}
+
 void launch_search(const Problem& P, const DeviceState& D, hipStream_t st);
 void launch_start(const Problem& P, const DeviceState& D, hipStream_t st);
 void launch_env(const Problem& P, const DeviceState& D, int32_t* n_active, hipStream_t st);

@@ -2011,6 +2011,48 @@ __global__ void __launch_bounds__(256) is_multi_tab_step_kernel(Problem P, Devic
     if (lane == 63) D.ctot[(size_t)e * D.ctot_stride + c + 1] = incl;
 }
 
+// The same update pass on history particles of the collision-avoidance FBA-POMDP (Problem::hist == 3): ca_hist_step with the whole
+// prior table and the sequence table of its inexact cells in LDS (ca_hist_stage_tables), the state from word 0, the entries
+// straight from the record.  The rest of the update is is_multi_step_kernel<false, true>'s launches (fba_create gives these records to
+// filters that take the multi-launch update: more than IS_MAX_CHUNKS * 256 particles).
+__global__ void __launch_bounds__(256) is_multi_ca_step_kernel(Problem P, DeviceState D)
+{
+    extern __shared__ uint4 s_ca_tables[];
+    const int e = chunk_slot(D, blockIdx.y), tid = threadIdx.x, lane = tid & 63;
+    if (!D.need_update[e] || hist_update_refused(P, D, e)) return;
+    CaTables T;
+    ca_hist_stage_tables(P, P.hist_row, s_ca_tables, tid, 256, T);   // every thread, before any wave leaves
+    __syncthreads();
+    const int c = blockIdx.x * 4 + (tid >> 6), N = P.N;
+    if (c * 256 >= N) return;
+    const int a = D.action[e], o = D.obs[e];
+    double* sw = D.p_weight + pbase(P, e, D.bufsel[e]);
+    const float* scn = D.p_rec + rec_base(P, D, e, D.bufsel[e]) * (size_t)P.Cs;
+    const uint32_t hist_cnt = D.hist_cnt[e];
+    const int rs = hist_stride(P, hist_total(hist_cnt)), off = 2 + hist_offset(hist_cnt, a), n_ent = hist_count(hist_cnt, a);
+    Rng g = slot_rng(P, D, e);
+    const int i0 = c * 256 + lane * 4;
+    double sum = 0;
+    for (int k = 0; k < 4; ++k) {
+        const int i = i0 + k;
+        double v = 0.0;
+        if (i < N) {
+            g.stream(FBA_PHASE_IS_UPDATE, (uint32_t)i);
+            const uint32_t* rec = reinterpret_cast<const uint32_t*>(scn + (size_t)i * rs);
+            int s = (int)rec[0], so;
+            uint32_t entry;
+            double r, prob;
+            ca_hist_step<true>(P, g, T, GlobalEntries{rec + off}, n_ent, s, a, so, r, entry, o, prob);
+            *reinterpret_cast<int2*>(D.p_side + ((size_t)e * N + i) * 2) = make_int2(s, (int)entry);
+            v     = sw[i] * prob;
+            sw[i] = v;
+        }
+        sum = (k == 0) ? v : sum + v;
+    }
+    const double incl = wave_inclusive_scan(sum, lane);
+    if (lane == 63) D.ctot[(size_t)e * D.ctot_stride + c + 1] = incl;
+}
+
 __global__ void __launch_bounds__(256) is_multi_norm_kernel(Problem P, DeviceState D)
 {
     const int e = chunk_slot(D, blockIdx.y), lane = threadIdx.x & 63;
@@ -2454,6 +2496,40 @@ __device__ uint64_t tab_hist_hash_counts(const Problem& P, const float* prior, c
     return h;
 }
 
+// The same for the collision-avoidance records (Problem::hist == 3): the 4 + 2n cells per entry (ca_hist_cells) over the dense prior;
+// a cell's value is the prior's after `mult` additions of 1.0f, one at a time (not every prior value is exact under prior + mult).
+__device__ void ca_hist_next_cell(const Problem& P, const uint32_t* rec, uint32_t cnt, int kmin, int& nxt, int& mult)
+{
+    const CADesc* ca = P.ca;
+    nxt = 0x7fffffff; mult = 0;
+    int j = 0;
+    for (int a = 0; a < P.A; ++a)
+        for (int q = 0; q < hist_count(cnt, a); ++q, ++j) {
+            int c[6];
+            ca_hist_cells(P.A, ca->W, ca->H, ca->n, a, rec[2 + j], c);
+#pragma unroll
+            for (int k = 0; k < 6; ++k)
+                if (c[k] >= kmin) {
+                    if (c[k] < nxt) { nxt = c[k]; mult = 1; }
+                    else if (c[k] == nxt) ++mult;
+                }
+        }
+}
+__device__ uint64_t ca_hist_hash_counts(const Problem& P, const float* prior, const uint32_t* rec, uint32_t len, uint64_t h)
+{
+    int nxt, mult;
+    ca_hist_next_cell(P, rec, len, 0, nxt, mult);
+    for (int k = 0; k < P.hist_row; ++k) {
+        float v = prior[k];
+        if (k == nxt) {
+            for (int q = 0; q < mult; ++q) v += 1.0f;
+            ca_hist_next_cell(P, rec, len, k + 1, nxt, mult);
+        }
+        h = mix64(h ^ ((uint64_t)__float_as_uint(v) + ((uint64_t)k << 32)));
+    }
+    return h;
+}
+
 __global__ void __launch_bounds__(256) flush_kernel(Problem P, DeviceState D)
 {
     __shared__ unsigned long long s_sum;
@@ -2484,7 +2560,8 @@ __global__ void __launch_bounds__(256) flush_kernel(Problem P, DeviceState D)
                 else v = packed_ftiger_view<4>(P, GlobalView{cnt}).at(k);
                 h = mix64(h ^ ((uint64_t)__float_as_uint(v) + ((uint64_t)k << 32)));
             }
-        } else if (P.hist == 2) h = tab_hist_hash_counts(P, D.prior_dense, reinterpret_cast<const uint32_t*>(cnt), D.hist_cnt[e], h);
+        } else if (P.hist == 3) h = ca_hist_hash_counts(P, D.prior_dense, reinterpret_cast<const uint32_t*>(cnt), D.hist_cnt[e], h);
+        else if (P.hist == 2) h = tab_hist_hash_counts(P, D.prior_dense, reinterpret_cast<const uint32_t*>(cnt), D.hist_cnt[e], h);
         else if (P.hist) h = hist_hash_counts(P, reinterpret_cast<const uint32_t*>(cnt), D.hist_cnt[e], h);
         else if (P.packed) {  // the checksum is over the counts themselves, whatever the storage (PackedView)
             const PackedView<GlobalView> pv{GlobalView{cnt}, D.prior_dense};
@@ -2662,6 +2739,8 @@ static void launch_importance_multi(const Problem& P, const DeviceState& D, int 
     const dim3 cgrid(ceil_div(nchunks, 4), count), eg(ceil_div(count, 64));
     const int32_t* list = D.use_list ? D.slot_list : nullptr;
     if (P.hist == 2) hipLaunchKernelGGL(is_multi_tab_step_kernel, cgrid, dim3(256), 0, st, P, D);   // (tabular records: sparse prior rows from L2)
+    else if (P.hist == 3)   // (collision-avoidance records: the whole prior and its sequence table in LDS)
+        hipLaunchKernelGGL(is_multi_ca_step_kernel, cgrid, dim3(256), ca_hist_table_bytes(P.hist_row, P.hist_rid_bytes, P.hist_distinct, P.hist_cap), st, P, D);
     else if (P.hist) {
         // the prior's rows from LDS where the deduplicated blob exists (rows of K floats, K as upload_prior chose it) -- FBA_HIST_ROWS=hbm: from L2
         const bool rows_hbm = D.ab_rows_hbm != 0;
@@ -2752,7 +2831,8 @@ void launch_belief_update(const Problem& P, const DeviceState& D, hipStream_t st
         if (P.dirichlet_regular) hipLaunchKernelGGL((reject_kernel<true, 0>), dim3(P.E), dim3(REJECT_BLOCK), 0, st, P, D, 1);
         else hipLaunchKernelGGL((reject_kernel<false, 0>), dim3(P.E), dim3(REJECT_BLOCK), 0, st, P, D, 1);
     }
-    if (P.hist == 2) {   // tabular history particles: the update is always the multi-launch one (is_multi_tab_step_kernel), one slot or many
+    if (P.hist >= 2) {   // tabular / collision-avoidance history particles: the update is always the multi-launch one (is_multi_tab_step_kernel,
+                         // is_multi_ca_step_kernel), one slot or many, 65 536 particles or a million
         if (D.single_rec) for_each_chunk(P, D, st, [&](const DeviceState& Dc, int cnt) { launch_importance_multi(P, Dc, cnt, st); }, D.need_update);
         else launch_importance_multi(P, D, P.E, st);
         return;

@@ -867,6 +867,175 @@ __global__ void __launch_bounds__(H2_BLOCK) __attribute__((amdgpu_waves_per_eu(F
 }
 
 // ---------------------------------------------------------------------------------------------
+// search_ca_hist_kernel: search_kernel's search -- one lane = one slot = one tree, the same state machine, node records and
+// child table, the same streams and draws -- on history particles of the collision-avoidance FBA-POMDP (Problem::hist == 3).
+// The workgroup keeps the whole prior table and its sequence table in LDS (ca_hist_stage_tables); a simulation root-samples
+// through the weighted filter (uniform weights: the filter was resampled by its last update), stages the chosen record --
+// 8 + 4 * entries bytes instead of the dense 3.5 KB -- as [word][lane] and steps with ca_hist_step over it.
+// LDS: the tables, then per lane the path [depth] {reward, node << 5 | action} and the record [Cs].
+// ---------------------------------------------------------------------------------------------
+template <int AMAX>
+__global__ void __launch_bounds__(SEARCH_BLOCK) search_ca_hist_kernel(Problem P, DeviceState D)
+{
+    extern __shared__ uint4 lds4[];
+    const int lane = threadIdx.x;
+    const int e    = blockIdx.x * SEARCH_BLOCK + lane;
+    CaTables T;
+    const int tbytes = ca_hist_stage_tables(P, P.hist_row, lds4, lane, SEARCH_BLOCK, T);
+    __syncthreads();
+    if (e >= P.E || !D.active[e]) return;
+
+    const int depth_cap = P.max_depth > 0 ? P.max_depth : 1;
+    float* path_r    = reinterpret_cast<float*>(reinterpret_cast<char*>(lds4) + tbytes) + lane;                      // [depth][block]
+    int32_t* path_na = reinterpret_cast<int32_t*>(path_r - lane + (size_t)depth_cap * SEARCH_BLOCK) + lane;          // [depth][block]
+    uint32_t* stage  = reinterpret_cast<uint32_t*>(path_na - lane + (size_t)depth_cap * SEARCH_BLOCK) + lane;        // [Cs][block]
+
+    Rng g               = slot_rng(P, D, e);
+    const int hist_len  = D.t[e];
+    const int max_tree_depth = min(P.horizon - hist_len, P.max_depth);
+    const int W         = D.node_words;
+    int32_t* tree       = D.nodes + (size_t)e * D.max_nodes * W;
+    const uint32_t hist_cnt = D.hist_cnt[e];
+    const int total     = hist_total(hist_cnt), rs = hist_stride(P, total);
+    const uint32_t* prec = reinterpret_cast<const uint32_t*>(D.p_rec + rec_base(P, D, e, D.bufsel[e]) * (size_t)P.Cs);
+
+    if (P.planner == FBA_PLANNER_RANDOM) {  // RandomPlanner::selectAction RandomPlanner.cpp:14-24
+        g.stream(FBA_PHASE_SEARCH, (uint32_t)P.sims);
+        const int src = belief_sample_uniform(P, D, g);
+        D.action[e]   = domain_random_action(P, g, (int)prec[(size_t)src * rs]);
+        return;
+    }
+    node_init(D, tree, P.A, P.O);
+    int n_nodes = 1, tree_depth = 0;
+    unsigned long long steps = 0;
+    // the root's visit counts and Q values live in registers for the whole search (search_kernel)
+    int r_vis = 0, r_cn[AMAX];
+    double r_cq[AMAX];
+#pragma unroll
+    for (int a = 0; a < AMAX; ++a) { r_cn[a] = 0; r_cq[a] = 0.0; }
+    int4* tab            = hash_table(D, e);
+    const uint32_t epoch = D.hash ? hash_begin_search(D, e, tab, 0, 1) : 0;
+    const int n4         = (2 + total + 3) >> 2;   // 16-byte pieces of a record that are alive
+
+    int sim = 0, mode = 0;  // 0 = start a simulation, 1 = in the tree, 2 = rollout
+    int s = 0, node = 0, dtg = 0, plen = 0, rdepth = 0;
+    double rret = 0, rdisc = 1;
+    while (true) {
+        if (mode == 0) {
+            if (sim >= P.sims) break;
+            g.stream(FBA_PHASE_SEARCH, (uint32_t)sim);
+            const int src   = belief_sample_uniform(P, D, g);
+            const uint4* rp = reinterpret_cast<const uint4*>(prec + (size_t)src * rs);
+            constexpr int NB = 8;   // 16-byte loads in flight before the first is waited for
+            for (int k0 = 0; k0 < n4; k0 += NB) {
+                uint4 v[NB];
+#pragma unroll
+                for (int q = 0; q < NB; ++q) v[q] = rp[min(k0 + q, n4 - 1)];
+#pragma unroll
+                for (int q = 0; q < NB; ++q) {
+                    const int k = k0 + q;
+                    if (k < n4) {
+                        stage[(4 * k + 0) * SEARCH_BLOCK] = v[q].x;
+                        stage[(4 * k + 1) * SEARCH_BLOCK] = v[q].y;
+                        stage[(4 * k + 2) * SEARCH_BLOCK] = v[q].z;
+                        stage[(4 * k + 3) * SEARCH_BLOCK] = v[q].w;
+                    }
+                }
+            }
+            s = (int)stage[0];
+            node = 0; dtg = max_tree_depth; plen = 0; mode = 1;
+        }
+        bool finish = false, do_step = true;
+        double delayed = 0;
+        int a = 0;
+        if (mode == 1) {  // traverseActionNode
+            tree_depth = max(tree_depth, max_tree_depth - dtg);
+            if (dtg == 0) { finish = true; do_step = false; }
+            else if (node == 0) a = ucb_pick<AMAX>(P, g, D.log1p_tab, r_vis, r_cn, r_cq, true);
+            else a = ucb_select<AMAX>(P, D, g, tree + (size_t)node * W, true);
+        } else {          // rollout: uniformly random action
+            a = domain_random_action(P, g, s);
+        }
+        if (do_step) {
+            int o;
+            double r, unused_prob;
+            uint32_t unused_entry;
+            const bool term = ca_hist_step<false>(P, g, T, StridedEntries<SEARCH_BLOCK>{stage + (size_t)(2 + hist_offset(hist_cnt, a)) * SEARCH_BLOCK},
+                                                  hist_count(hist_cnt, a), s, a, o, r, unused_entry, 0, unused_prob);
+            ++steps;
+            if (mode == 1) {  // traverseChanceNode
+                path_r[(size_t)plen * SEARCH_BLOCK]  = (float)r;
+                path_na[(size_t)plen * SEARCH_BLOCK] = (node << 5) | a;
+                ++plen;
+                if (term) finish = true;
+                else {
+                    const int c = child_get(P, D, tree, tab, epoch, node, a, o);
+                    if (c >= 0) { node = c; --dtg; }
+                    else {  // expand: new leaf, then rollout(depth_to_go - 1); never past the slot's records (search_kernel)
+                        const int nn = min(n_nodes, D.max_nodes - 1);
+                        ++n_nodes;
+                        node_init(D, tree + (size_t)nn * W, P.A, P.O);
+                        child_set(P, D, tree, tab, epoch, node, a, o, nn);
+                        mode = 2; rdepth = dtg - 1; rret = 0; rdisc = 1;
+                        if (rdepth == 0) finish = true;
+                    }
+                }
+            } else {
+                rret += r * rdisc;
+                rdisc *= P.gamma;
+                --rdepth;
+                if (rdepth == 0 || term) { delayed = rret; finish = true; }
+            }
+        }
+        if (finish) {
+            // back-up, leaf to root: ret = r + gamma * delayed; ChanceNode::addVisit(ret), ActionNode::addVisit() (search_kernel)
+            double del = delayed;
+            for (int k = plen - 1; k >= 1; --k) {
+                const int na     = path_na[(size_t)k * SEARCH_BLOCK];
+                const double ret = (double)path_r[(size_t)k * SEARCH_BLOCK] + P.gamma * del;
+                const int act    = na & 31;
+                int32_t* rec = tree + (size_t)(na >> 5) * W;
+                double* q    = reinterpret_cast<double*>(rec + D.cq_off) + act;
+                const int nv = ++rec[D.cn_off + act];
+                if (D.cn_off) ++rec[0];
+                *q += (ret - *q) / (double)nv;
+                del = ret;
+            }
+            if (plen > 0) {
+                const double ret = (double)path_r[0] + P.gamma * del;
+                const int act    = path_na[0] & 31;
+                int nv = 0;
+                double q = 0.0;
+#pragma unroll
+                for (int a2 = 0; a2 < AMAX; ++a2)
+                    if (a2 == act) { nv = r_cn[a2]; q = r_cq[a2]; }
+                ++nv;
+                q += (ret - q) / (double)nv;
+#pragma unroll
+                for (int a2 = 0; a2 < AMAX; ++a2)
+                    if (a2 == act) { r_cn[a2] = nv; r_cq[a2] = q; }
+                ++r_vis;
+            }
+            ++sim;
+            mode = 0;
+        }
+    }
+    g.stream(FBA_PHASE_SEARCH, (uint32_t)P.sims + 1u);
+    if (n_nodes > D.max_nodes) atomicCAS(D.fault, 0, -(1 + e));  // -> FBA_ESTATE on the host
+    const int best = ucb_pick<AMAX>(P, g, D.log1p_tab, 0, r_cn, r_cq, false);
+    D.action[e]    = best;
+    D.sim_steps[e] += steps;
+    fba_trace_rec& rec = D.cur[e];
+    rec.n_nodes    = n_nodes;
+    rec.tree_depth = tree_depth;
+#pragma unroll
+    for (int a = 0; a < FBA_MAX_ACTIONS; ++a) {
+        rec.root_n[a] = a < AMAX && a < P.A ? r_cn[a < AMAX ? a : 0] : 0;
+        rec.root_q[a] = a < AMAX && a < P.A ? r_cq[a < AMAX ? a : 0] : 0.0;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // host launcher
 // ---------------------------------------------------------------------------------------------
 void launch_search(const Problem& P, const DeviceState& D, hipStream_t st)
@@ -904,6 +1073,11 @@ void launch_search(const Problem& P, const DeviceState& D, hipStream_t st)
         else if (P.model == FBA_MODEL_BA_TABLE) FBA_LAUNCH_SEARCH_M(STG, AM, FBA_MODEL_BA_TABLE);   \
         else FBA_LAUNCH_SEARCH_M(false, AM, FBA_MODEL_POMDP);                                       \
     } while (0)
+    if (P.hist == 3) {  // history particles of the collision-avoidance FBA-POMDP: one lane per tree, node records (A = 3)
+        const size_t lds3 = ca_hist_search_lds(P);   // (at most 64 KB: fba_create keeps other contexts dense)
+        hipLaunchKernelGGL(search_ca_hist_kernel<4>, grid, block, lds3, st, P, D);
+        return;
+    }
     if (P.hist) {  // history particles (gridworld FBA-POMDP): four lanes per tree
         lds = (size_t)depth_cap * HIST_TREES * (sizeof(double) + sizeof(int32_t) + sizeof(float) + sizeof(int32_t)) + (size_t)P.Cs * HIST_TREES * sizeof(float);
         const dim3 qgrid(ceil_div(P.E, HIST_TREES));

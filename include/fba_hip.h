@@ -179,7 +179,10 @@ typedef struct fba_kernel_time {
     double ms;          /* sum of HIP-event durations */
     uint64_t launches;
     uint64_t units;     /* particles written (belief kernels) / simulated steps (search) */
-    uint64_t bytes;     /* algorithmic bytes, SURVEY.md section 8(d) formulas            */
+    uint64_t bytes;     /* algorithmic bytes, SURVEY.md section 8(d) formulas.  History records have formulas of their own
+                         * (DESIGN.md section 5a); collision-avoidance records under the importance filter:
+                         * particles * 100 + entries * 12 (weights, prefix sums and side rows 72, the record's 8-byte header
+                         * read twice and written once with the new entry 28, every older 4-byte entry moved three times) */
 } fba_kernel_time;
 
 typedef struct fba_ctx fba_ctx;
@@ -204,7 +207,12 @@ int fba_particle_bytes(const fba_ctx* ctx); /* HBM bytes of one particle record.
                                              * the planner is po-uct or random with at most 65 536 simulations.  The tabular gridworld
                                              * BA-POMDP stores them the same way (8 B + 4 B per real step instead of 7.68 MB at
                                              * --size 7) under both filters where the planner is po-uct or random with at most 65 536
-                                             * simulations.  Such contexts refuse fba_belief_set of states or counts.  FBA_DENSE_PARTICLES=1 in the environment forces
+                                             * simulations.  The collision-avoidance FBA-POMDP without a structure prior stores them too
+                                             * under the plain importance filter above 65 536 particles, where the filter is the multi-launch one (smaller filters stay dense; 8 B + 4 B per real step instead of
+                                             * 3.5 KB at 7 x 7 with two obstacles), for po-uct or random, width and height <= 8, at most
+                                             * two obstacles, episodes * horizon <= 126, a search whose LDS (prior tables, 512 B per level of
+                                             * max_depth, 256 B per record word) fits 64 KB, and a prior with at most 8 distinct counts c for
+                                             * which c + j is inexact in fp32.  Such contexts refuse fba_belief_set of states or counts.  FBA_DENSE_PARTICLES=1 in the environment forces
                                              * fp32 counts.  fba_belief_get / fba_belief_set always speak fp32 counts. */
 int fba_slots(const fba_ctx* ctx);      /* slots actually resident (cfg.slots, or the library's choice) */
 
