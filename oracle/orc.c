@@ -126,6 +126,7 @@ struct orc_ctx {
     uint64_t* step_counter; /* which counter sim_step bumps */
     /* trace */
     orc_trace_rec* trace;
+    uint64_t* trace_steps; /* per trace record: the simulator.step calls its selectAction and its belief update made */
     int32_t n_trace, cap_trace;
     /* per-selectAction outputs */
     int32_t last_update_count;
@@ -2959,7 +2960,9 @@ static orc_trace_rec* trace_push(orc_ctx* c)
     if (c->n_trace == c->cap_trace) {
         c->cap_trace = c->cap_trace ? 2 * c->cap_trace : 1024;
         c->trace     = (orc_trace_rec*)realloc(c->trace, sizeof(orc_trace_rec) * c->cap_trace);
+        c->trace_steps = (uint64_t*)realloc(c->trace_steps, sizeof(uint64_t) * 2 * (size_t)c->cap_trace);
     }
+    c->trace_steps[2 * c->n_trace] = c->trace_steps[2 * c->n_trace + 1] = 0;
     memset(&c->trace[c->n_trace], 0, sizeof(orc_trace_rec));
     return &c->trace[c->n_trace++];
 }
@@ -2977,6 +2980,7 @@ static double episode_run(orc_ctx* c, int run, int episode, int* length)
     for (t = 0; t < c->cfg.horizon && !term; ++t) {
         orc_trace_rec* rec = trace_push(c);
         int32_t a;
+        const uint64_t sim0 = c->sim_steps, bel0 = c->belief_steps;
         orc_rng_episode(&c->rng, R, (uint32_t)episode, (uint32_t)t);
         a = select_action(c, t, rec);
         orc_rng_stream(&c->rng, ORC_PH_ENV, 0);
@@ -2992,6 +2996,8 @@ static double episode_run(orc_ctx* c, int run, int episode, int* length)
             rec->update_count = term ? -1 : c->last_update_count;
             rec->weight_total = c->last_weight_total;
             rec->belief_hash  = belief_hash(c);
+            c->trace_steps[2 * (rec - c->trace)]     = c->sim_steps - sim0;
+            c->trace_steps[2 * (rec - c->trace) + 1] = c->belief_steps - bel0;
         }
         ret += r * disc;
         disc *= c->cfg.discount;
@@ -3299,12 +3305,13 @@ void orc_destroy(orc_ctx* c)
     free(c->tr.hkey); free(c->tr.hval);
     free(c->P); free(c->Pnew); free(c->pool); free(c->pool_new);
     free(c->F); free(c->Fnew); free(c->fpool); free(c->fpool_new); free(c->breed_tmp);
-    free(c->wscratch); free(c->wscan); free(c->trace);
+    free(c->wscratch); free(c->wscan); free(c->trace); free(c->trace_steps);
     free(c);
 }
 
 const char* orc_error(const orc_ctx* c) { return c->err[0] ? c->err : NULL; }
 const orc_trace_rec* orc_trace(const orc_ctx* c) { return c->trace; }
+const uint64_t* orc_trace_steps(const orc_ctx* c) { return c->trace_steps; }
 orc_rng* orc_ctx_rng(orc_ctx* c) { return &c->rng; }
 
 int orc_domain_sizes(const orc_ctx* c, int32_t* S, int32_t* A, int32_t* O)

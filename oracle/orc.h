@@ -129,6 +129,8 @@ int orc_run_planning(orc_ctx* c, orc_stat* stats, orc_result* res);
 int orc_run_bapomdp(orc_ctx* c, orc_stat* stats, orc_result* res);
 
 const orc_trace_rec* orc_trace(const orc_ctx* c);
+/* beside every trace record: {sim_steps, belief_steps} of that one real step (orc_result holds their sums) */
+const uint64_t* orc_trace_steps(const orc_ctx* c);
 
 /* model introspection (prior tables), for fixtures and for feeding fba_set_model_* */
 int orc_domain_sizes(const orc_ctx* c, int32_t* S, int32_t* A, int32_t* O);

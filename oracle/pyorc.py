@@ -102,6 +102,8 @@ def lib():
         L.orc_run_bapomdp.argtypes = [C.c_void_p, P(Stat), P(Result)]
         L.orc_trace.restype = C.c_void_p
         L.orc_trace.argtypes = [C.c_void_p]
+        L.orc_trace_steps.restype = C.c_void_p
+        L.orc_trace_steps.argtypes = [C.c_void_p]
         L.orc_domain_sizes.argtypes = [C.c_void_p, P(C.c_int32), P(C.c_int32), P(C.c_int32)]
         L.orc_counts_len.argtypes = [C.c_void_p]
         L.orc_prior_counts.argtypes = [C.c_void_p, C.c_void_p]
@@ -263,6 +265,13 @@ class Oracle:
         ptr = self.L.orc_trace(self.h)
         buf = (C.c_char * (n * TRACE_DTYPE.itemsize)).from_address(ptr)
         return np.frombuffer(buf, dtype=TRACE_DTYPE, count=n).copy()
+
+    def trace_steps(self, n):
+        """beside trace(n): the simulated steps of every record's search and of its belief update, [n][2]"""
+        if n == 0:
+            return np.zeros((0, 2), np.uint64)
+        buf = (C.c_uint64 * (2 * n)).from_address(self.L.orc_trace_steps(self.h))
+        return np.frombuffer(buf, dtype=np.uint64, count=2 * n).reshape(n, 2).copy()
 
     def prior_counts(self):
         out = np.zeros(self.ncnt, np.float32)

@@ -196,7 +196,7 @@ def min_distinct_lengths(c):
     return 3
 
 
-def _oracle(c, **over):
+def make_oracle(c, **over):
     kw = {k: v for k, v in c["kw"].items() if k not in ENGINE_ONLY and k != "seed"}
     if "planner" in kw:
         kw["planner"] = PLANNER[kw["planner"]]
@@ -235,10 +235,10 @@ def oracle_side(c, whole=False):
     whole experiment, field for field) and has no statistics; `whole` runs everything all the same (for measuring, without a GPU)."""
     ba = c["model"] != POMDP
     if c["sample"] and not whole:
-        traces = [_run(_oracle(c, runs=1, run_offset=r), ba)[0] for r in sample_runs(c)]
+        traces = [_run(make_oracle(c, runs=1, run_offset=r), ba)[0] for r in sample_runs(c)]
         tr, stats, counters = np.concatenate(traces), None, None
     else:
-        tr, stats, counters = _run(_oracle(c, runs=c["runs"]), ba)
+        tr, stats, counters = _run(make_oracle(c, runs=c["runs"]), ba)
     cfg = orc.make_config(**{k: v for k, v in c["kw"].items() if k in ("episodes", "discount")})
     ret, ln = returns_of_trace(tr, c["runs"], cfg.episodes, cfg.discount)
     return dict(trace=tr, stats=stats, counters=counters, returns=ret, lengths=ln)
