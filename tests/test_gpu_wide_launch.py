@@ -13,24 +13,6 @@ import wide_launch_cases as W
 pytestmark = pytest.mark.gpu
 
 
-def _assert_same_experiment(c, got, ref):
-    tr, otr = got["trace"], ref["trace"]
-    if c["sample"]:
-        runs = W.sample_runs(c)
-        tr = tr[np.isin(tr["run"], runs)]
-    else:
-        runs = np.arange(c["runs"])
-    assert len(tr) == len(otr) > 0
-    for name in tr.dtype.names:
-        bad = np.nonzero(~np.all((tr[name] == otr[name]).reshape(len(tr), -1), axis=1))[0]
-        assert bad.size == 0, f"{name}: first mismatch at record {bad[0]}: {tr[bad[0]]} vs {otr[bad[0]]}"
-    if not c["sample"]:
-        assert got["stats"] == ref["stats"]
-        assert got["counters"] == ref["counters"]
-    assert np.array_equal(got["lengths"][runs], ref["lengths"][runs])
-    assert np.array_equal(got["returns"][runs].view(np.uint64), ref["returns"][runs].view(np.uint64))
-
-
 @pytest.mark.parametrize("name", [c["name"] for c in W.CASES])
 def test_wide_launch_equals_the_oracle(name, monkeypatch):
     c = W.BY_NAME[name]
@@ -41,7 +23,7 @@ def test_wide_launch_equals_the_oracle(name, monkeypatch):
     distinct = np.unique(got["lengths"])
     print(f"{name}: {len(got['trace'])} records, episode lengths {distinct.tolist()}")
     assert len(distinct) >= W.min_distinct_lengths(c), f"episodes of lengths {distinct.tolist()} only: the slots sit at the same t"
-    _assert_same_experiment(c, got, W.oracle_side(c))
+    W.assert_same_experiment(c, got, W.oracle_side(c))
 
 
 def test_the_case_table_covers_what_it_says():

@@ -256,3 +256,22 @@ def engine_side(c, fba):
                returns=ret, lengths=ln)
     eng.close()
     return out
+
+
+def assert_same_experiment(c, got, ref):
+    """every trace field, statistic, counter and per-run return and length of the engine's experiment is the oracle's, bit for bit"""
+    tr, otr = got["trace"], ref["trace"]
+    if c["sample"]:
+        runs = sample_runs(c)
+        tr = tr[np.isin(tr["run"], runs)]
+    else:
+        runs = np.arange(c["runs"])
+    assert len(tr) == len(otr) > 0
+    for name in tr.dtype.names:
+        bad = np.nonzero(~np.all((tr[name] == otr[name]).reshape(len(tr), -1), axis=1))[0]
+        assert bad.size == 0, f"{name}: first mismatch at record {bad[0]}: {tr[bad[0]]} vs {otr[bad[0]]}"
+    if not c["sample"]:
+        assert got["stats"] == ref["stats"]
+        assert got["counters"] == ref["counters"]
+    assert np.array_equal(got["lengths"][runs], ref["lengths"][runs])
+    assert np.array_equal(got["returns"][runs].view(np.uint64), ref["returns"][runs].view(np.uint64))
