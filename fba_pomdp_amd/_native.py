@@ -12,7 +12,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB_PATH = os.environ.get("FBA_LIB") or os.path.join(HERE, "libfba_hip.so")   # (FBA_LIB: an instrumented build of the same sources, scripts/search_regions.py)
-SOURCES = [os.path.join(HERE, "csrc", f) for f in ("fba_search.hip", "fba_kernels.hip", "fba_engine.hip")]
+SOURCES = [os.path.join(HERE, "csrc", f) for f in ("fba_search.hip", "fba_kernels.hip", "fba_summary.hip", "fba_engine.hip")]
 HEADERS = [os.path.join(HERE, "csrc", f) for f in ("fba_device.h", "fba_state.h", "fba_kernels.h", "fba_kernels_common.h", "fba_search_hist2.inc")] + [
     os.path.join(ROOT, "include", "fba_hip.h")]
 OBJ_DIR = os.path.join(HERE, "build")   # per-source objects (git-ignored): a change to one translation unit recompiles that one
@@ -110,12 +110,19 @@ class KernelTime(C.Structure):
     _fields_ = [("ms", C.c_double), ("launches", C.c_uint64), ("units", C.c_uint64), ("bytes", C.c_uint64)]
 
 
+class BeliefSummaryHead(C.Structure):   # fba_belief_summary_head
+    _fields_ = [("weight_total", C.c_double), ("weight_sq_total", C.c_double), ("particles", C.c_int32), ("weighted", C.c_int32)]
+
+
+SUMMARY_HEAD_DTYPE = np.dtype([("weight_total", "<f8"), ("weight_sq_total", "<f8"), ("particles", "<i4"), ("weighted", "<i4")], align=True)
+
+
 # every symbol include/fba_hip.h declares
 EXPORTS = [
     "fba_abi_version", "fba_default_config", "fba_create", "fba_destroy", "fba_last_error",
     "fba_domain_sizes", "fba_counts_len", "fba_slots", "fba_particle_bytes", "fba_set_model_tabular", "fba_set_model_factored", "fba_log_bd_score", "fba_selftest_lgamma", "fba_get_prior", "fba_get_factored_layout",
     "fba_set_position", "fba_belief_init", "fba_belief_reset_domain_state", "fba_select_action",
-    "fba_belief_update", "fba_belief_get", "fba_belief_get_particle", "fba_belief_set", "fba_belief_get_fully_connected", "fba_belief_get_nested", "fba_belief_get_shadow", "fba_last_step_info",
+    "fba_belief_update", "fba_belief_get", "fba_belief_get_particle", "fba_belief_set", "fba_belief_get_fully_connected", "fba_belief_get_nested", "fba_belief_get_shadow", "fba_belief_summary", "fba_last_step_info",
     "fba_run_planning", "fba_run_bapomdp", "fba_run_ticks", "fba_get_returns", "fba_get_counters", "fba_get_return_sums",
     "fba_get_kernel_times", "fba_reset_kernel_times", "fba_trace_count", "fba_get_trace", "fba_get_trace_hist",
     "fba_selftest_ucb", "fba_stat_add", "fba_stat_var", "fba_stat_stder",
@@ -208,6 +215,8 @@ def load():
     if not os.environ.get("FBA_LIB") or hasattr(L, "fba_belief_get_nested"):   # (FBA_LIB may name an older build for an A/B run)
         L.fba_belief_get_nested.argtypes = [vp, C.c_int32, vp]
         L.fba_belief_get_shadow.argtypes = [vp, C.c_int32, vp, vp, vp]
+    if not os.environ.get("FBA_LIB") or hasattr(L, "fba_belief_summary"):
+        L.fba_belief_summary.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp]   # head: BeliefSummaryHead[count]; three double arrays
     L.fba_last_step_info.argtypes = [vp, vp]
     L.fba_run_planning.argtypes = [vp, P(Stat)]
     L.fba_run_bapomdp.argtypes = [vp, P(Stat)]

@@ -2382,6 +2382,66 @@ int fba_belief_get_nested(fba_ctx* c, int32_t slot, int32_t* states)
     return FBA_OK;
 }
 
+// The posterior of slots [first, first + count) reduced on the device (fba_summary.hip), a chunk of slots at a time so that the
+// fp64 tables of a chunk stay below 256 MB.  Reads the context only: no flag, buffer index, counter or stream position moves,
+// and a lazily reset filter stays lazy (the kernel derives the states as every other reader does).
+int fba_belief_summary(fba_ctx* c, int32_t first, int32_t count, fba_belief_summary_head* head, double* state_mass, double* mean_counts,
+                       double* edge_prob)
+{
+    if (!c) return FBA_EINVAL;
+    const Problem& P = c->P;
+    if (first < 0 || count < 0 || (long long)first + count > P.E)
+        return fail(c, FBA_EINVAL, "fba_belief_summary: slots [%d, %lld) are not within the context's %d", first, (long long)first + count, P.E);
+    if (P.nested)
+        return fail(c, FBA_EINVAL, "fba_belief_summary: the nested belief's particles are (model, state filter) pairs; read them with "
+                                   "fba_belief_get and fba_belief_get_nested");
+    if (P.model == FBA_MODEL_POMDP && (mean_counts || edge_prob))
+        return fail(c, FBA_EINVAL, "fba_belief_summary: a plain POMDP belief has no counts (fba_counts_len is 0); only head and state_mass are served");
+    if (count == 0 || (!head && !state_mass && !mean_counts && !edge_prob)) return FBA_OK;
+    const bool factored = P.model == FBA_MODEL_BA_FACTORED;
+    const int S = P.S, dense_C = c->dense_C, ncounts = factored ? c->fdesc.ncounts : dense_C, nvar = factored ? c->fdesc.nvar : 0;
+    if (P.hist == 1 && nvar != 2 * P.A) return fail(c, FBA_ESTATE, "fba_belief_summary: gridworld records without their %d parent-set words", 2 * P.A);
+    const bool want_edge = nvar > 0 && (edge_prob || (P.hist == 1 && mean_counts));
+    size_t per_slot = 2 + (size_t)S + (mean_counts ? (size_t)dense_C : 0) + (size_t)nvar * 17;
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>({(size_t)count, (size_t)32768, ((size_t)256 << 20) / (per_slot * 8)}));
+    ScratchBuf<double> d_head, d_state, d_mean, d_emass, d_eprob;
+    HIPCHK(c, d_head.alloc((size_t)chunk * 2));
+    if (state_mass) HIPCHK(c, d_state.alloc((size_t)chunk * S));
+    if (mean_counts) HIPCHK(c, d_mean.alloc((size_t)chunk * dense_C));
+    if (want_edge) {
+        HIPCHK(c, d_emass.alloc((size_t)chunk * nvar * 9));
+        if (edge_prob) HIPCHK(c, d_eprob.alloc((size_t)chunk * nvar * MAXF));
+    }
+    std::vector<double> h_head((size_t)chunk * 2);
+    for (int done = 0; done < count; done += chunk) {
+        const int n = std::min(chunk, count - done);
+        BeliefSummaryArgs a{};
+        a.first = first + done; a.count = n;
+        a.head = d_head.p; a.state_mass = d_state.p; a.mean_counts = d_mean.p; a.edge_mass = d_emass.p; a.edge_prob = d_eprob.p;
+        a.dense_C = dense_C; a.ncounts = ncounts; a.nvar = nvar;
+        a.cb = 256;
+        if (dense_C < 256) { a.cb = 1; while (a.cb < dense_C) a.cb <<= 1; }
+        a.lds_states = S <= 4096 ? 1 : 0;
+        a.ft_FS = factored ? c->fdesc.FS : 0;
+        if (state_mass && !a.lds_states) HIPCHK(c, hipMemsetAsync(d_state.p, 0, (size_t)n * S * 8, c->stream));
+        if (mean_counts && P.hist) HIPCHK(c, hipMemsetAsync(d_mean.p, 0, (size_t)n * dense_C * 8, c->stream));
+        launch_belief_summary(P, c->D, a, c->stream);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(h_head.data(), d_head.p, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
+        if (state_mass) HIPCHK(c, hipMemcpyAsync(state_mass + (size_t)done * S, d_state.p, (size_t)n * S * 8, hipMemcpyDeviceToHost, c->stream));
+        if (mean_counts) HIPCHK(c, hipMemcpyAsync(mean_counts + (size_t)done * dense_C, d_mean.p, (size_t)n * dense_C * 8, hipMemcpyDeviceToHost, c->stream));
+        if (edge_prob && nvar) HIPCHK(c, hipMemcpyAsync(edge_prob + (size_t)done * nvar * MAXF, d_eprob.p, (size_t)n * nvar * MAXF * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (head)
+            for (int i = 0; i < n; ++i) {
+                fba_belief_summary_head& h = head[done + i];
+                h.weight_total = h_head[(size_t)i * 2]; h.weight_sq_total = h_head[(size_t)i * 2 + 1];
+                h.particles = P.N; h.weighted = P.belief == FBA_BELIEF_IMPORTANCE ? 1 : 0;
+            }
+    }
+    return check_fault(c);
+}
+
 int fba_belief_set(fba_ctx* c, int32_t slot, const int32_t* state, const double* weight, const float* counts)
 {
     if (!c || slot < 0 || slot >= c->P.E) return FBA_EINVAL;

@@ -43,6 +43,21 @@ void launch_selftest_lgamma(const double* x, int count, double* out, hipStream_t
 void launch_selftest_bd(const Problem& P, const float* cnt, const float* prior, double* out, hipStream_t st);
 void launch_selftest_ucb(const double* L, const int32_t* n, int count, double u, double* out, hipStream_t st);
 hipError_t launch_take_error();   // a HIP error a launch_* function met on its way (and clears it); hipSuccess if none
+// fba_belief_summary (fba_summary.hip): slots [first, first + count) reduced into device buffers of the caller's; a null pointer = that
+// output is not wanted.  The caller zeroes the two the kernels accumulate into: state_mass where !lds_states, mean_counts of history records
+struct BeliefSummaryArgs {
+    int32_t first, count;
+    double* head;         // [count][2] sum of weights, sum of squared weights
+    double* state_mass;   // [count][S]
+    double* mean_counts;  // [count][dense_C]
+    double* edge_mass;    // [count][nvar * 9]: mass per (mask word, bit), then per word the mass of the gridworld records without the goal parent
+    double* edge_prob;    // [count][nvar][MAXF]
+    int32_t dense_C, ncounts, nvar;   // floats of a particle's table as the API speaks of it; the counts among them; the mask words behind those
+    int32_t cb;           // dense / packed records: cells per workgroup (a power of two, at most 256)
+    int32_t lds_states;   // the state histogram fits LDS
+    int32_t ft_FS;        // packed factored tiger: state features
+};
+void launch_belief_summary(const Problem& P, const DeviceState& D, const BeliefSummaryArgs& a, hipStream_t st);
 void launch_uniform_scan(int n, double* w_tmp, double* out, double* total, double* ctot, hipStream_t st);
 
 }  // namespace fba

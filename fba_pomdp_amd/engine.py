@@ -25,6 +25,22 @@ def _enum(value, table, what):
     return int(value)
 
 
+class BeliefSummary:
+    """What Engine.belief_summary returns: numpy arrays with one row per slot of the range (None where not asked for)."""
+
+    def __init__(self, head, state_mass, mean_counts, edge_prob):
+        self.head = head                                  # fba_belief_summary_head per slot
+        self.weight_total = head["weight_total"]
+        self.weight_sq_total = head["weight_sq_total"]
+        self.particles = head["particles"]
+        self.weighted = head["weighted"]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            self.ess = self.weight_total ** 2 / self.weight_sq_total   # effective sample size
+        self.state_mass = state_mass                      # [slots][S]
+        self.mean_counts = mean_counts                    # [slots][fba_counts_len]
+        self.edge_prob = edge_prob                        # [slots][n_mask_words][FBA_MAX_FEATURES]
+
+
 class Engine:
     """One fba_ctx: `slots` independent (planner, belief) pairs resident on one MI355X."""
 
@@ -201,6 +217,27 @@ class Engine:
         self._chk(self.L.fba_belief_get(self.h, slot, s.ctypes.data, w.ctypes.data if want_w else None,
                                         cnt.ctypes.data if counts and self.ncnt else None))
         return s, w, cnt
+
+    def belief_summary(self, first=0, count=None, state_mass=True, mean_counts=True, edge_prob=True):
+        """The posterior of slots [first, first + count) reduced on the device (fba_belief_summary): per slot the weight totals,
+        `ess`, the mass per domain state, the weighted mean of the count tables belief_get would return and, per parent-set word
+        of a factored model, the weighted fraction of particles that use each candidate parent.  No table is built anywhere, so
+        this is the way to read a filter of history records.  `edge_prob` of a model without parent-set words is None; a plain
+        POMDP context serves `state_mass` only (ask with mean_counts=False, edge_prob=False); cells of a factored node compare across particles only where `edge_prob` of
+        that node's word is 0 or 1.  Outside the parity contract: the last bits may differ from call to call."""
+        count = self.slots - first if count is None else count
+        n = max(count, 0)
+        if not hasattr(self, "_n_mask_words"):
+            self._n_mask_words = self.factored_layout().n_mask_words if self.cfg.model == N.MODEL_BA_FACTORED else 0
+        head = np.zeros(n, N.SUMMARY_HEAD_DTYPE)
+        sm = np.zeros((n, self.S), np.float64) if state_mass else None
+        mc = np.zeros((n, self.ncnt), np.float64) if mean_counts and self.ncnt else None
+        ep = np.zeros((n, self._n_mask_words, N.MAX_FEATURES), np.float64) if edge_prob and self._n_mask_words else None
+        if self.cfg.model == N.MODEL_POMDP and (mean_counts or edge_prob):   # (the library says what a plain POMDP context serves)
+            mc = np.zeros((n, 1), np.float64)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        self._chk(self.L.fba_belief_summary(self.h, first, count, ptr(head), ptr(sm), ptr(mc), ptr(ep)))
+        return BeliefSummary(head, sm, mc, ep)
 
     def belief_get_fully_connected(self, slot=0):
         """The second filter of the reinvigoration (fully connected) / cheating (correct graph) belief."""

@@ -290,6 +290,29 @@ int fba_belief_get_fully_connected(fba_ctx* ctx, int32_t slot, int32_t* state, f
 int fba_belief_get_nested(fba_ctx* ctx, int32_t slot, int32_t* states);
 /* the incubator belief's shadow filter (StructureIncubatorSampling.hpp: _shadow_belief), for tests */
 int fba_belief_get_shadow(fba_ctx* ctx, int32_t slot, int32_t* state, double* weight, float* counts);
+/* Posterior summary of slots [first, first + count), reduced on the device from whatever record format the context stores
+ * (fba_particle_bytes) -- no particle's count table is built, on the device or on the host.  Any output pointer may be NULL.
+ *   head       [count]
+ *   state_mass [count][S]              sum of w_i over the particles whose domain state is s
+ *   mean_counts[count][fba_counts_len] sum_i w_i * c_i[k] / weight_total, where c_i is the fp32 table fba_belief_get returns
+ *                                      for particle i.  Entries at the mask-word positions of a factored blob (k >= n_counts) are 0.0.
+ *   edge_prob  [count][n_mask_words][FBA_MAX_FEATURES]
+ *                                      weighted fraction of particles whose mask word m has bit j set; 0.0 for j >= 32 or unused.
+ * Serves the main filter of every belief but the nested one (FBA_EINVAL there: its particles are pairs, fba_belief_get_nested), not
+ * the second or shadow filters; a plain POMDP context has head and state_mass only.  Read-only: no buffer, flag, counter or Philox
+ * position of the context changes, so the call may stand between any two others, after fba_run_*, and on inactive slots.
+ * The call is OUTSIDE the parity contract: the order of its fp64 additions is the engine's choice and need not repeat bit for bit
+ * from call to call; nothing of it enters the trace or belief_hash.  Every entry is within 8 * particles * 2^-53 relative of the
+ * exact sum, and exactly 0.0 where every term is.  Cells of a factored node compare across particles only where the particles share
+ * that node's parent set: edge_prob of 0 or 1 says where that is so. */
+typedef struct fba_belief_summary_head {
+    double  weight_total;     /* sum of w_i; a flat (rejection) filter counts every particle with w_i = 1.0, so this is N exactly */
+    double  weight_sq_total;  /* sum of w_i^2 (effective sample size = weight_total^2 / weight_sq_total)                           */
+    int32_t particles;        /* N                                                                                                */
+    int32_t weighted;         /* 1: importance filter, 0: flat filter                                                             */
+} fba_belief_summary_head;
+int fba_belief_summary(fba_ctx* ctx, int32_t first, int32_t count, fba_belief_summary_head* head,
+                       double* state_mass, double* mean_counts, double* edge_prob);
 /* per-slot record of the last select_action / belief_update (root statistics, rejection count,
  * belief checksum) */
 int fba_last_step_info(fba_ctx* ctx, fba_trace_rec* recs /* [slots] */);
