@@ -419,7 +419,7 @@ __global__ void __launch_bounds__(BLK) reject_kernel(Problem P, DeviceState D, i
         g.stream(phase, (uint32_t)k);
         const int src = P.point ? 0 : g.uniform_int(N);         // FlatFilter::sample; the point estimate copies its one state
         const float* rec = scn + (size_t)src * P.Cs;
-        int s = (!fc && lazy) ? lazy_state(P, D, e, src) : rec_state(rec, P.C), so;
+        int s = (!fc && lazy) ? lazy_state(P, g, src) : rec_state(rec, P.C), so;
         double r;
         // UpdateCounts: the +1s land in the copy
         if (FTIGER > 0 && FTP) ftiger_step_packed<(FTIGER > 0 ? FTIGER : 1)>(P, g, GlobalView{rec}, s, a, so, r, LdsInc<BLK>{s_inc + tid});
@@ -709,17 +709,17 @@ __global__ void __launch_bounds__(BLK) reject_tiger_lds_kernel(Problem P, Device
     uint8_t* s_st    = reinterpret_cast<uint8_t*>(s_tab + 3 * (size_t)N);
     if (tid < 24) s_prior[tid] = D.prior_dense[tid];
     const bool lazy = slot_lazy(D, e);
+    Rng g = slot_rng(P, D, e);
     for (int i = tid; i < N; i += BLK) {
         const uint32_t* rec = reinterpret_cast<const uint32_t*>(scn) + (size_t)i * 16;
         const uint32_t w0 = rec[a], w1 = rec[3 + a], wo0 = rec[6 + 2 * a], wo1 = rec[7 + 2 * a];  // cell pairs (0,a,.) (1,a,.) | (a,0,.) (a,1,.)
-        const int st = lazy ? lazy_state(P, D, e, i) : (int)rec[12];
+        const int st = lazy ? lazy_state(P, g, i) : (int)rec[12];
         s_tab[3 * i + 0] = st ? w1 : w0;
         s_tab[3 * i + 1] = wo0;
         s_tab[3 * i + 2] = wo1;
         s_st[i]          = (uint8_t)st;
     }
     __syncthreads();
-    Rng g = slot_rng(P, D, e);
     int acc = 0, base = 0;
     while (acc < N) {
         if (base >= REJECT_MAX_ATTEMPTS) {  // see reject_kernel

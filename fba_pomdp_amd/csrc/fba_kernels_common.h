@@ -49,6 +49,17 @@ __device__ __forceinline__ int lazy_state(const Problem& P, const DeviceState& D
     g.stream(FBA_PHASE_RESET, (uint32_t)i);
     return domain_start(P, g);
 }
+// The same draw for a caller that already holds the slot's generator (slot_rng: c3 = run, the episode in the top half of c2): the stream
+// (run, episode, 0, RESET, i) is addressed from those registers -- no load, and the caller's own stream is left where it is.  (In the search
+// the loads of run / episode sat behind the wait for the particle record: a dependent trip to memory per simulation.)
+__device__ __forceinline__ int lazy_state(const Problem& P, const Rng& g, int i)
+{
+    Rng h;
+    h.k0 = g.k0; h.k1 = g.k1; h.c3 = g.c3;
+    h.c2 = (g.c2 & 0xffff0000u) | FBA_PHASE_RESET;   // t = 0
+    h.c1 = (uint32_t)i; h.draw = 0; h.keep_lo = 0; h.keep_hi = 0;
+    return domain_start(P, h);
+}
 
 // WeightedFilter::sample (WeightedFilter.cpp:163-191) in device order: the largest i >= 1 whose
 // exclusive prefix sum is below the threshold, else 0.  `incl` holds inclusive prefix sums.

@@ -224,7 +224,7 @@ __global__ void __launch_bounds__(SEARCH_BLOCK) search_kernel(Problem P, DeviceS
             } else {
                 s = rec_state(cnt, P.C);
             }
-            if (lazy) s = lazy_state(P, D, e, src);
+            if (lazy) s = lazy_state(P, g, src);   // (from g's own registers: no load behind the record's)
             if (nested) s = nest_state;
             node = 0; dtg = max_tree_depth; plen = 0; mode = 1;
         }
