@@ -2442,6 +2442,183 @@ int fba_belief_summary(fba_ctx* c, int32_t first, int32_t count, fba_belief_summ
     return check_fault(c);
 }
 
+int fba_predict_lens(const fba_ctx* c, int32_t* TL, int32_t* OL)
+{
+    if (!c) return FBA_EINVAL;
+    int tl = 0, ol = 0;
+    if (c->P.model == FBA_MODEL_BA_FACTORED) {
+        for (int f = 0; f < c->fdesc.FS; ++f) tl += c->fdesc.Ssz[f];
+        for (int f = 0; f < c->fdesc.FO; ++f) ol += c->fdesc.Osz[f];
+    } else if (c->P.model == FBA_MODEL_BA_TABLE) {
+        tl = c->P.S; ol = c->P.O;
+    }
+    if (TL) *TL = tl;
+    if (OL) *OL = ol;
+    return FBA_OK;
+}
+
+namespace {
+// pack_features and node_row of fba_device.h on the host: the features of an index, 8 bits each, and DBNNode::cptIndex
+uint64_t predict_features(int v, const int32_t* step, int n)
+{
+    if (n == 1) return (uint64_t)v;
+    uint64_t p = 0;
+    for (int i = 0; i < n; ++i) { p |= (uint64_t)(v / step[i]) << (8 * i); v = v % step[i]; }
+    return p;
+}
+int predict_node_row(const FNode& nd, uint32_t mask, uint64_t fv)
+{
+    int idx = 0;
+    for (int j = 0; j < nd.nmax; ++j)
+        if ((mask >> j) & 1u) idx = idx * nd.psz[j] + (int)((fv >> (8 * nd.maxp[j])) & 0xffu);
+    return nd.off + idx * nd.out;
+}
+}  // namespace
+
+// The posterior-predictive model of slots [first, first + count) at nq queries, reduced on the device (fba_predict.hip), a chunk of slots at
+// a time so that the fp64 buffers of a chunk stay below 256 MB.  Reads the context only, as fba_belief_summary does.
+int fba_belief_predict(fba_ctx* c, int32_t first, int32_t count, int32_t nq, const int32_t* state, const int32_t* action, const int32_t* next_state,
+                       const int32_t* obs, double* trans, double* obsp, double* joint)
+{
+    if (!c) return FBA_EINVAL;
+    const Problem& P = c->P;
+    if (P.nested)
+        return fail(c, FBA_EINVAL, "fba_belief_predict: the nested belief's particles are (model, state filter) pairs; read them with "
+                                   "fba_belief_get and fba_belief_get_nested");
+    if (P.model == FBA_MODEL_POMDP) return fail(c, FBA_EINVAL, "fba_belief_predict: a plain POMDP belief has no counts (fba_counts_len is 0)");
+    if (first < 0 || count < 0 || (long long)first + count > P.E)
+        return fail(c, FBA_EINVAL, "fba_belief_predict: slots [%d, %lld) are not within the context's %d", first, (long long)first + count, P.E);
+    if (nq < 1 || nq > (1 << 24)) return fail(c, FBA_EINVAL, "fba_belief_predict: %d queries (1 to 16 777 216 are served)", nq);
+    if (!state || !action || !next_state || !obs) return fail(c, FBA_EINVAL, "fba_belief_predict: a query array is missing");
+    for (int q = 0; q < nq; ++q)
+        if (state[q] < 0 || state[q] >= P.S || action[q] < 0 || action[q] >= P.A || next_state[q] < 0 || next_state[q] >= P.S || obs[q] < 0 || obs[q] >= P.O)
+            return fail(c, FBA_EINVAL, "fba_belief_predict: query %d (state %d, action %d, next_state %d, obs %d) is outside the model's %d states, %d actions, "
+                                       "%d observations", q, state[q], action[q], next_state[q], obs[q], P.S, P.A, P.O);
+    if (count == 0 || (!trans && !obsp && !joint)) return FBA_OK;
+    const bool factored = P.model == FBA_MODEL_BA_FACTORED;
+    const FDesc& fd = c->fdesc;
+    const int S = P.S, A = P.A, O = P.O, FS = factored ? fd.FS : 1, FO = factored ? fd.FO : 1, nn = FS + FO;
+    int32_t TL = 0, OL = 0;
+    fba_predict_lens(c, &TL, &OL);
+    const int TLOL = TL + OL, hw = TLOL + 2 * PREDICT_SLOTS + 1;
+    if (nn > PREDICT_MAXQN) return fail(c, FBA_ESTATE, "fba_belief_predict: %d nodes per action (at most %d are served)", nn, PREDICT_MAXQN);
+    std::vector<int32_t> seg((size_t)nn, 0);
+    int longest = 1;
+    for (int j = 0, t = 0, o = 0; j < nn; ++j) {
+        const int len = !factored ? (j == 0 ? S : O) : (j < FS ? fd.Ssz[j] : fd.Osz[j - FS]);
+        seg[(size_t)j] = j < FS ? t : o;
+        (j < FS ? t : o) += len;
+        longest = std::max(longest, len);
+    }
+    ScratchBuf<int32_t> d_query, d_seg, d_slot;
+    ScratchBuf<PredictSlotNode> d_qn;
+    ScratchBuf<float> d_qprior;
+    HIPCHK(c, d_query.alloc((size_t)nq * 4));
+    HIPCHK(c, d_seg.alloc((size_t)nn));
+    HIPCHK(c, hipMemcpyAsync(d_query.p, state, (size_t)nq * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_query.p + nq, action, (size_t)nq * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_query.p + (size_t)2 * nq, next_state, (size_t)nq * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_query.p + (size_t)3 * nq, obs, (size_t)nq * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_seg.p, seg.data(), (size_t)nn * 4, hipMemcpyHostToDevice, c->stream));
+    // history records: what the shared prior contributes to each query -- per entry-cell slot the queried row per prior form
+    std::vector<PredictSlotNode> qn;
+    std::vector<float> qprior;
+    std::vector<int32_t> ent_slot;
+    if (P.hist) {
+        if (hw * (int)sizeof(double) > 64 * 1024) return fail(c, FBA_ESTATE, "fba_belief_predict: an answer of %d entries does not fit the kernel's LDS", TLOL);
+        if (P.hist == 1 && (FS != 3 || FO != 3 || fd.nvar != 2 * A))
+            return fail(c, FBA_ESTATE, "fba_belief_predict: gridworld records without their %d parent-set words", 2 * A);
+        if (P.hist == 3 && (FS > 4 || FO > 2)) return fail(c, FBA_ESTATE, "fba_belief_predict: collision-avoidance records of %d + %d nodes", FS, FO);
+        const int XYd = P.hist == 1 ? c->gdesc.N * c->gdesc.N * c->gdesc.G * c->gdesc.N : 0;
+        auto slot_node = [&](int k) { return P.hist == 3 ? (k < 4 ? (k < FS ? k : -1) : (k - 4 < FO ? FS + k - 4 : -1)) : (k < nn ? k : -1); };
+        qn.assign((size_t)nq * PREDICT_SLOTS, PredictSlotNode{});
+        qprior.assign((size_t)nq * 2 * TLOL, 0.f);
+        ent_slot.assign((size_t)TLOL, 0);
+        for (int k = 0; k < PREDICT_SLOTS; ++k) {
+            const int j = slot_node(k);
+            if (j < 0) continue;
+            const int len = !factored ? (j == 0 ? S : O) : (j < FS ? fd.Ssz[j] : fd.Osz[j - FS]);
+            for (int i = 0; i < len; ++i) ent_slot[(size_t)(j < FS ? 0 : TL) + seg[(size_t)j] + i] = k;
+        }
+        for (int q = 0; q < nq; ++q) {
+            const int s = state[q], a = action[q], ns = next_state[q], ob = obs[q];
+            for (int k = 0; k < PREDICT_SLOTS; ++k) {
+                PredictSlotNode& n = qn[(size_t)q * PREDICT_SLOTS + k];
+                n.var = -1;
+                const int j = slot_node(k);
+                if (j < 0) continue;
+                const bool T = j < FS;
+                const int f  = T ? j : j - FS;
+                n.seg = (T ? 0 : TL) + seg[(size_t)j];
+                const float* alt = nullptr;   // the row of form 1 where there is one
+                if (!factored) {
+                    n.rb0 = n.rb1 = T ? (s * A + a) * S : P.phi_len + (a * S + ns) * O;
+                    n.out = T ? S : O;
+                    n.val = T ? ns : ob;
+                } else {
+                    const FNode& nd   = fd.nodes[T ? a * FS + f : A * FS + a * FO + f];
+                    const uint64_t fv = predict_features(T ? s : ns, fd.Sstep, FS);
+                    n.out = nd.out;
+                    n.val = T ? (int)((predict_features(ns, fd.Sstep, FS) >> (8 * f)) & 0xffu) : (int)((predict_features(ob, fd.Ostep, FO) >> (8 * f)) & 0xffu);
+                    if (P.hist == 1 && nd.var >= 0) {   // an x / y node: with (7) or without (3) the goal parent, as fba_belief_get writes the word
+                        if (nd.var != 2 * a + f || f > 1) return fail(c, FBA_ESTATE, "fba_belief_predict: parent-set word %d at node T(%d, %d)", nd.var, a, f);
+                        n.var = nd.var;
+                        n.rb0 = predict_node_row(nd, 3u, fv);
+                        n.rb1 = predict_node_row(nd, 7u, fv);
+                        alt   = c->prior_alt.data() + (size_t)(a * 2 + f) * XYd + (n.rb1 - nd.off);
+                    } else
+                        n.rb0 = n.rb1 = predict_node_row(nd, nd.fixed_mask, fv);
+                }
+                if (n.val < 0 || n.val >= n.out || (size_t)n.seg + n.out > (size_t)TLOL || n.rb0 < 0 || (size_t)n.rb0 + n.out > c->prior.size())
+                    return fail(c, FBA_ESTATE, "fba_belief_predict: query %d does not fit the layout at slot %d", q, k);
+                float* p0 = &qprior[((size_t)q * 2) * TLOL + n.seg];
+                float* p1 = p0 + TLOL;
+                for (int i = 0; i < n.out; ++i) {
+                    p0[i] = c->prior[(size_t)n.rb0 + i];
+                    p1[i] = alt ? alt[i] : 0.f;
+                    n.prs0 += (double)p0[i];
+                    n.prs1 += (double)p1[i];
+                }
+            }
+        }
+        HIPCHK(c, d_qn.alloc(qn.size()));
+        HIPCHK(c, d_qprior.alloc(qprior.size()));
+        HIPCHK(c, d_slot.alloc(ent_slot.size()));
+        HIPCHK(c, hipMemcpyAsync(d_qn.p, qn.data(), qn.size() * sizeof(PredictSlotNode), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_qprior.p, qprior.data(), qprior.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_slot.p, ent_slot.data(), ent_slot.size() * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    const size_t per_slot = (size_t)nq * ((trans ? (size_t)TL : 0) + (obsp ? (size_t)OL : 0) + 1 + (P.hist ? (size_t)hw : 0)) + 1;
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>({(size_t)count, (size_t)32768, ((size_t)256 << 20) / (per_slot * 8)}));
+    ScratchBuf<double> d_trans, d_obsp, d_joint, d_wtot, d_hacc;
+    HIPCHK(c, d_wtot.alloc((size_t)chunk));
+    if (trans) HIPCHK(c, d_trans.alloc((size_t)chunk * nq * TL));
+    if (obsp) HIPCHK(c, d_obsp.alloc((size_t)chunk * nq * OL));
+    if (joint) HIPCHK(c, d_joint.alloc((size_t)chunk * nq));
+    if (P.hist) HIPCHK(c, d_hacc.alloc((size_t)chunk * nq * hw));
+    for (int done = 0; done < count; done += chunk) {
+        const int n = std::min(chunk, count - done);
+        BeliefPredictArgs a{};
+        a.first = first + done; a.count = n; a.nq = nq;
+        a.state = d_query.p; a.action = d_query.p + nq; a.next_state = d_query.p + (size_t)2 * nq; a.obs = d_query.p + (size_t)3 * nq;
+        a.trans = d_trans.p; a.obsp = d_obsp.p; a.joint = d_joint.p; a.wtot = d_wtot.p;
+        a.TL = TL; a.OL = OL; a.nn = nn; a.nT = FS;
+        a.ncounts = factored ? fd.ncounts : c->dense_C;
+        a.jw = 1;
+        while (a.jw < longest && a.jw < 64) a.jw <<= 1;
+        a.ft_FS = factored ? fd.FS : 0;
+        a.seg = d_seg.p; a.qn = d_qn.p; a.qprior = d_qprior.p; a.ent_slot = d_slot.p; a.hacc = d_hacc.p;
+        if (P.hist) HIPCHK(c, hipMemsetAsync(d_hacc.p, 0, (size_t)n * nq * hw * 8, c->stream));
+        launch_belief_predict(P, c->D, a, c->stream);
+        HIPCHK(c, hipGetLastError());
+        if (trans) HIPCHK(c, hipMemcpyAsync(trans + (size_t)done * nq * TL, d_trans.p, (size_t)n * nq * TL * 8, hipMemcpyDeviceToHost, c->stream));
+        if (obsp) HIPCHK(c, hipMemcpyAsync(obsp + (size_t)done * nq * OL, d_obsp.p, (size_t)n * nq * OL * 8, hipMemcpyDeviceToHost, c->stream));
+        if (joint) HIPCHK(c, hipMemcpyAsync(joint + (size_t)done * nq, d_joint.p, (size_t)n * nq * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return check_fault(c);
+}
+
 int fba_belief_set(fba_ctx* c, int32_t slot, const int32_t* state, const double* weight, const float* counts)
 {
     if (!c || slot < 0 || slot >= c->P.E) return FBA_EINVAL;

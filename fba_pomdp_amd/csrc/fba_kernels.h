@@ -58,6 +58,29 @@ struct BeliefSummaryArgs {
     int32_t ft_FS;        // packed factored tiger: state features
 };
 void launch_belief_summary(const Problem& P, const DeviceState& D, const BeliefSummaryArgs& a, hipStream_t st);
+// fba_belief_predict (fba_predict.hip): nq queries (s, a, s', o) answered for slots [first, first + count) into device buffers of the caller's;
+// a null output = not wanted.  History records: the caller zeroes hacc and supplies what the prior contributes (qn, qprior, ent_slot)
+constexpr int PREDICT_MAXQN = 16;   // nodes of one query: FS + FO
+constexpr int PREDICT_SLOTS = 6;    // entry-cell slots of a history record (summary_entry_cells)
+struct PredictSlotNode {            // the node whose cell an entry holds in slot k, for one query; out = 0: the slot is unused
+    int32_t rb0, rb1;               // dense index where the queried row starts, per prior form (form 1: the parent-set bit `var` of the record is set)
+    int32_t out, seg, val, var;     // row length; where the row's entries start in [trans | obsp]; the query's own value; parent-set bit or -1
+    double prs0, prs1;              // fp64 sum of the prior row, per form
+};
+struct BeliefPredictArgs {
+    int32_t first, count, nq;
+    const int32_t *state, *action, *next_state, *obs;   // [nq]
+    double *trans, *obsp, *joint;                       // [count][nq][TL], [count][nq][OL], [count][nq]
+    double* wtot;                                       // [count] weight totals (written first)
+    int32_t TL, OL, nn, nT;     // entries of a query's answer; nodes of a query, the transition nodes among them
+    int32_t ncounts, jw, ft_FS; // counts of a particle's table; lanes that share one particle in a joint item (a power of two); packed factored tiger: state features
+    const int32_t* seg;         // [nn] where node j's entries start in trans (j < nT) or obsp
+    const PredictSlotNode* qn;  // history records: [nq][PREDICT_SLOTS]
+    const float* qprior;        // history records: [nq][2][TL + OL] the prior rows of the query per form
+    const int32_t* ent_slot;    // history records: [TL + OL] slot of the node an entry belongs to
+    double* hacc;               // history records: [count][nq][TL + OL + 2 * PREDICT_SLOTS + 1] raised terms, sum w / R per (slot, form), joint sum
+};
+void launch_belief_predict(const Problem& P, const DeviceState& D, const BeliefPredictArgs& a, hipStream_t st);
 void launch_uniform_scan(int n, double* w_tmp, double* out, double* total, double* ctot, hipStream_t st);
 
 }  // namespace fba

@@ -25,6 +25,18 @@ def _enum(value, table, what):
     return int(value)
 
 
+class BeliefPrediction:
+    """What Engine.belief_predict returns: numpy arrays [slot, query, ...] (None where not asked for) and, for a factored model, where
+    each feature's segment starts: feature f of `trans` is trans[..., trans_offsets[f]:trans_offsets[f + 1]], likewise `obsp`."""
+
+    def __init__(self, trans, obsp, joint, trans_offsets, obs_offsets):
+        self.trans = trans
+        self.obsp = obsp
+        self.joint = joint
+        self.trans_offsets = trans_offsets   # None for a tabular model
+        self.obs_offsets = obs_offsets
+
+
 class BeliefSummary:
     """What Engine.belief_summary returns: numpy arrays with one row per slot of the range (None where not asked for)."""
 
@@ -238,6 +250,39 @@ class Engine:
         ptr = lambda a: None if a is None else a.ctypes.data
         self._chk(self.L.fba_belief_summary(self.h, first, count, ptr(head), ptr(sm), ptr(mc), ptr(ep)))
         return BeliefSummary(head, sm, mc, ep)
+
+    def predict_lens(self):
+        """(TL, OL): entries of one query's `trans` and `obsp` answer (fba_predict_lens)."""
+        tl, ol = C.c_int32(), C.c_int32()
+        self._chk(self.L.fba_predict_lens(self.h, C.byref(tl), C.byref(ol)))
+        return tl.value, ol.value
+
+    def belief_predict(self, state, action, next_state, obs, first=0, count=None, trans=True, obsp=True, joint=True):
+        """The posterior-predictive model of slots [first, first + count) at the queries (state, action, next_state, obs), evaluated
+        on the device (fba_belief_predict): `trans[slot, q]` = the filter's mean of each particle's expected Dirichlet row of (state, action)
+        under that particle's own parent sets, `obsp[slot, q]` the same for the observation row of (action, next_state), `joint[slot, q]`
+        the mean probability of the whole transition.  For a factored model trans / obsp hold one segment per feature -- marginals of a
+        mixture, which is not their product; `joint` is the structure-aware quantity.  Returns a BeliefPrediction; outputs not asked for
+        are None.  Outside the parity contract: the last bits may differ from call to call."""
+        count = self.slots - first if count is None else count
+        n = max(count, 0)
+        q = [np.ascontiguousarray(np.atleast_1d(x), np.int32) for x in (state, action, next_state, obs)]
+        nq = len(q[0])
+        if any(x.ndim != 1 or len(x) != nq for x in q):
+            raise ValueError("belief_predict: state, action, next_state and obs are one-dimensional arrays of one length")
+        tl, ol = self.predict_lens()
+        tr = np.zeros((n, nq, tl), np.float64) if trans else None
+        ob = np.zeros((n, nq, ol), np.float64) if obsp else None
+        jt = np.zeros((n, nq), np.float64) if joint else None
+        ptr = lambda a: None if a is None else a.ctypes.data
+        self._chk(self.L.fba_belief_predict(self.h, first, count, nq, q[0].ctypes.data, q[1].ctypes.data, q[2].ctypes.data, q[3].ctypes.data,
+                                            ptr(tr), ptr(ob), ptr(jt)))
+        t_off = o_off = None
+        if self.cfg.model == N.MODEL_BA_FACTORED:
+            lay = self.factored_layout()
+            t_off = np.concatenate(([0], np.cumsum(lay.state_feature_size[:lay.n_state_features]))).astype(np.int64)
+            o_off = np.concatenate(([0], np.cumsum(lay.obs_feature_size[:lay.n_obs_features]))).astype(np.int64)
+        return BeliefPrediction(tr, ob, jt, t_off, o_off)
 
     def belief_get_fully_connected(self, slot=0):
         """The second filter of the reinvigoration (fully connected) / cheating (correct graph) belief."""

@@ -313,6 +313,35 @@ typedef struct fba_belief_summary_head {
 } fba_belief_summary_head;
 int fba_belief_summary(fba_ctx* ctx, int32_t first, int32_t count, fba_belief_summary_head* head,
                        double* state_mass, double* mean_counts, double* edge_prob);
+/* Posterior-predictive model queries on the device: under the posterior of each slot in [first, first + count), what happens when action[q]
+ * is taken in state[q], and how probable is the transition to next_state[q] under observation obs[q]?  The nq queries (1 to 2^24) are shared
+ * by the slots.  With c_i the fp32 table fba_belief_get returns for particle i, w_i its weight (1.0 in a flat filter), W = sum w_i and
+ * theta_i(row)[k] = c_i[row + k] / sum_k c_i[row + k] in fp64 (a row whose counts sum to 0 contributes 0 to every entry):
+ *   tabular   trans[slot][q][s'] = sum_i w_i theta_i(phi row (s_q, a_q))[s'] / W                       TL = S
+ *             obsp [slot][q][o]  = sum_i w_i theta_i(psi row (a_q, s'_q))[o] / W                       OL = O
+ *             joint[slot][q]     = sum_i w_i theta_i(phi)[s'_q] * theta_i(psi)[o_q] / W
+ *   factored  segment f of trans (TL = sum of state_feature_size) is the same mean for node T(a_q, f), the row chosen by particle i's OWN
+ *             parent set from the features of s_q exactly as the layout comment above states it (DBNNode::cptIndex); segment f of obsp
+ *             (OL = sum of obs_feature_size) the same for node O(a_q, f), the row chosen from the features of s'_q;
+ *             joint = sum_i w_i prod_f theta_i,T(a,f)[s'_q,f] * prod_g theta_i,O(a,g)[o_q,g] / W.
+ *             trans and obsp hold PER-FEATURE MARGINALS OF A MIXTURE over particles and structures: the mixture itself is not the product of
+ *             them; joint is the structure-aware quantity.
+ * Any output pointer may be NULL (all three: FBA_OK, nothing is done).  Evaluated from whatever record format the context stores, without
+ * building a particle's table anywhere.  Serves the main filter of every belief but the nested one (FBA_EINVAL there: its particles are
+ * pairs, fba_belief_get_nested), in either Dirichlet mode (the Dirichlet's expectation is the same row); FBA_EINVAL for a plain POMDP
+ * context (no counts), a slot range outside the context, nq < 1 and any query index out of range (the message names the query).
+ * Read-only: no buffer, flag, counter or Philox position of the context changes, so the call may stand between any two others, after
+ * fba_run_*, and on inactive slots.  It does not depend on the particles' domain states, so a lazily reset filter needs no special case.
+ * The call is OUTSIDE the parity contract: it is not the simulator's float sum and float division (expected_mult_at, fact_obs_prob), the
+ * order of its fp64 additions is the engine's choice and need not repeat bit for bit from call to call, and nothing of it enters the
+ * trace or belief_hash.  Every entry is within 8 * (particles + F * (L + 2)) * 2^-53 relative of the exact value (L the longest row, F = 1
+ * for trans / obsp and the number of nodes for joint), and exactly 0.0 where every term is. */
+int fba_predict_lens(const fba_ctx* ctx, int32_t* TL, int32_t* OL); /* lengths of one query's answer (0, 0 for a plain POMDP) */
+int fba_belief_predict(fba_ctx* ctx, int32_t first, int32_t count, int32_t nq,
+                       const int32_t* state, const int32_t* action, const int32_t* next_state, const int32_t* obs, /* [nq] each */
+                       double* trans,  /* [count][nq][TL] */
+                       double* obsp,   /* [count][nq][OL] */
+                       double* joint); /* [count][nq]     */
 /* per-slot record of the last select_action / belief_update (root statistics, rejection count,
  * belief checksum) */
 int fba_last_step_info(fba_ctx* ctx, fba_trace_rec* recs /* [slots] */);
