@@ -1694,7 +1694,7 @@ __device__ __forceinline__ bool ca_hist_step(const Problem& P, Rng& g, const CaT
     s            = ns;
     return t;
 }
-// the 4 + 2n dense cells entry `en` of action a incremented (host: fba_belief_get; device: the belief checksum)
+// the 4 + 2n dense cells entry `en` of action a incremented
 __host__ __device__ __forceinline__ void ca_hist_cells(int A, int W, int H, int n, int a, uint32_t en, int (&c)[6])
 {
     const int tsize = W * W + H * H * (1 + n), tbase = a * tsize, obase = A * tsize + a * n * H * H;
@@ -1704,6 +1704,95 @@ __host__ __device__ __forceinline__ void ca_hist_cells(int A, int W, int H, int 
         const uint32_t f = en >> (12 + 9 * k);
         c[2 + k] = k < n ? tbase + W * W + H * H * (1 + k) + (int)(f & 7u) * H + (int)((f >> 3) & 7u) : -1;
         c[4 + k] = k < n ? obase + k * H * H + (int)(f & 7u) * H + (int)((f >> 6) & 7u) : -1;
+    }
+}
+
+// ---- reading history records: which dense cells an entry raised ---------------------------------------------------
+// The one definition of the rule for everything that reads records without stepping them: the belief checksum (hist_next_cell),
+// fba_belief_get (hist_materialize), fba_belief_summary and fba_belief_predict.  The sizes arrive as plain integers, since the host
+// cannot dereference Problem::ca: the device passes hist_dims that pointer, the host its own copy of the descriptor.
+constexpr int HIST_ENTRY_CELLS = 6;   // cells an entry names at most
+struct HistDims {
+    int A;               // actions
+    int N, G;            // HIST 1, gridworld FBA-POMDP: side, goals
+    int S, O, phi_len;   // HIST 2, tabular gridworld BA-POMDP
+    int W, H, n;         // HIST 3, collision avoidance: grid, obstacles
+};
+template <int HIST>
+__host__ __device__ __forceinline__ HistDims hist_dims(const Problem& P, const CADesc* ca)
+{
+    HistDims d{};
+    d.A = P.A;
+    if (HIST == 1) { d.N = P.gw_N; d.G = P.gw_G; }
+    if (HIST == 2) { d.S = P.S; d.O = P.O; d.phi_len = P.phi_len; }
+    if (HIST == 3) { d.W = ca->W; d.H = ca->H; d.n = ca->n; }
+    return d;
+}
+// the dense cells entry `en` of action `act` raised in a record of structure word `mask` (Problem::hist = HIST): 6 (gridworld FBA-POMDP),
+// 2 (tabular), 4 + 2n (collision avoidance); -1 = unused.  A tabular cell fits an int: fba_create stores these records for the gridworld
+// at size <= HIST_MAX_N only (S = O = N * N * G <= 8 * 8 * 10, four actions), so the table ends below 2^22.
+template <int HIST>
+__host__ __device__ __forceinline__ void hist_entry_cells(const HistDims& d, uint32_t mask, int act, uint32_t en, int (&c)[HIST_ENTRY_CELLS])
+{
+    if (HIST == 3) {
+        ca_hist_cells(d.A, d.W, d.H, d.n, act, en, c);
+        return;
+    }
+    const uint32_t s0 = en & 0x3ffu, s1 = (en >> 10) & 0x3ffu, ob = en >> 20;
+    if (HIST == 2) {   // T(s, a, s') and O(a, s', o) (BAFlatModel.cpp:126-139)
+        c[0] = ((int)s0 * d.A + act) * d.S + (int)s1;
+        c[1] = d.phi_len + (act * d.S + (int)s1) * d.O + (int)ob;
+        c[2] = c[3] = c[4] = c[5] = -1;
+        return;
+    }
+    // the x, y and goal nodes of T(act) and of O(act) (BABNModel::incrementCountsOf BABNModel.cpp:354-382); an x / y node's row is that of
+    // (cell, goal) where the record's structure bit gives it the goal parent, of the cell alone where not
+    const int N = d.N, G = d.G;
+    const int XY = N * N * G * N, GG = N * N * G * G, NN = N * N;
+    const int tbase = act * (2 * XY + GG), obase = d.A * (2 * XY + GG) + act * (2 * NN + G * G);
+    const bool mx = (mask >> (2 * act)) & 1u, my = (mask >> (2 * act + 1)) & 1u;
+    const int x = hist_x(s0), y = hist_y(s0), gl = hist_g(s0), cell = x * N + y;
+    c[0] = tbase + (mx ? cell * G + gl : cell) * N + hist_x(s1);
+    c[1] = tbase + XY + (my ? cell * G + gl : cell) * N + hist_y(s1);
+    c[2] = tbase + 2 * XY + (cell * G + gl) * G + hist_g(s1);
+    c[3] = obase + x * N + hist_x(ob);
+    c[4] = obase + NN + y * N + hist_y(ob);
+    c[5] = obase + 2 * NN + gl * G + hist_g(ob);
+}
+// visit(k, rel, mult): every distinct cell of the entries rec[2 + j0 .. j0 + na) of action `act` that lies in the row [rb[k], rb[k] + len[k])
+// of cell slot k, once, with the number of entries that name it.  (Cells of two slots, or of two actions, never coincide, so a cell is
+// compared with the same slot of the other entries of its action only.)
+template <int HIST, int NC, class F>
+__device__ __forceinline__ void hist_distinct_cells(const HistDims& d, const uint32_t* rec, uint32_t mask, int act, int j0, int na, const int (&rb)[NC],
+                                                    const int (&len)[NC], F visit)
+{
+    for (int j = j0; j < j0 + na; ++j) {
+        int c[HIST_ENTRY_CELLS], rel[NC];
+        hist_entry_cells<HIST>(d, mask, act, rec[2 + j], c);
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+            rel[k] = c[k] - rb[k];
+            any    = any || (unsigned)rel[k] < (unsigned)len[k];   // (also drops the -1 of an unused cell: rb[k] >= 0)
+        }
+        if (!any) continue;
+        int mult[NC];
+        bool first[NC];
+#pragma unroll
+        for (int k = 0; k < NC; ++k) { mult[k] = 0; first[k] = true; }
+        for (int j2 = j0; j2 < j0 + na; ++j2) {
+            int o[HIST_ENTRY_CELLS];
+            hist_entry_cells<HIST>(d, mask, act, rec[2 + j2], o);
+#pragma unroll
+            for (int k = 0; k < NC; ++k) {
+                const bool same = o[k] == c[k];
+                mult[k] += same ? 1 : 0;
+                first[k] = first[k] && !(same && j2 < j);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < NC; ++k)
+            if ((unsigned)rel[k] < (unsigned)len[k] && first[k]) visit(k, rel[k], mult[k]);
     }
 }
 

@@ -2213,40 +2213,40 @@ int fba_belief_update(fba_ctx* c, const int32_t* action, const int32_t* obs, con
 }
 
 // History particles: the dense count table of one record, as the API speaks of particles -- the prior (the goal-parent
-// form of the x / y nodes the structure bits name) plus 1.0f per entry and incremented cell
-// (BABNModel::incrementCountsOf BABNModel.cpp:354-382 replayed; `cnt` = the slot's entries per action).
+// form of the x / y nodes the structure bits name) plus 1.0f per entry and incremented cell, one addition at a time
+// (BABNModel::incrementCountsOf BABNModel.cpp:354-382, BAFlatModel.cpp:126-139 replayed; `cnt` = the slot's entries per action).
+static void hist_add_entries(const fba_ctx* c, const uint32_t* rec, uint32_t cnt, float* counts)
+{
+    const int hist = c->P.hist;
+    const HistDims dims = hist == 3 ? hist_dims<3>(c->P, &c->cadesc) : (hist == 2 ? hist_dims<2>(c->P, nullptr) : hist_dims<1>(c->P, nullptr));
+    int j = 0;
+    for (int a = 0; a < c->P.A; ++a)
+        for (int q = 0; q < hist_count(cnt, a); ++q, ++j) {
+            int cells[HIST_ENTRY_CELLS];
+            if (hist == 3) hist_entry_cells<3>(dims, rec[1], a, rec[2 + j], cells);
+            else if (hist == 2) hist_entry_cells<2>(dims, rec[1], a, rec[2 + j], cells);
+            else hist_entry_cells<1>(dims, rec[1], a, rec[2 + j], cells);
+            for (int k = 0; k < HIST_ENTRY_CELLS; ++k)
+                if (cells[k] >= 0) counts[cells[k]] += 1.0f;
+        }
+}
 static void hist_materialize(const fba_ctx* c, const uint32_t* rec, uint32_t cnt, float* counts)
 {
-    if (c->P.hist == 2) {   // tabular records: entry (s, s', o) of action a adds 1.0f at T(s, a, s') and at O(a, s', o) (BAFlatModel.cpp:126-139)
-        const int S = c->P.S, A = c->P.A, O = c->P.O;
+    if (c->P.hist == 2) {   // tabular records
         std::copy(c->prior.begin(), c->prior.end(), counts);
-        int j = 0;
-        for (int a = 0; a < A; ++a)
-            for (int q = 0; q < hist_count(cnt, a); ++q, ++j) {
-                const uint32_t en = rec[2 + j], s0 = en & 0x3ffu, s1 = (en >> 10) & 0x3ffu, ob = en >> 20;
-                counts[((size_t)s0 * A + a) * S + s1] += 1.0f;
-                counts[(size_t)c->P.phi_len + ((size_t)a * S + s1) * O + ob] += 1.0f;
-            }
+        hist_add_entries(c, rec, cnt, counts);
         return;
     }
-    if (c->P.hist == 3) {   // collision-avoidance records: 1.0f at each of the entry's 4 + 2n cells (ca_hist_cells), one addition at a time
-        const CADesc& ca = c->cadesc;
-        std::copy(c->prior.begin(), c->prior.begin() + c->fdesc.ncounts, counts);
-        int j = 0;
-        for (int a = 0; a < c->P.A; ++a)
-            for (int q = 0; q < hist_count(cnt, a); ++q, ++j) {
-                int cells[6];
-                ca_hist_cells(c->P.A, ca.W, ca.H, ca.n, a, rec[2 + j], cells);
-                for (int k = 0; k < 6; ++k)
-                    if (cells[k] >= 0) counts[cells[k]] += 1.0f;
-            }
+    const int ncounts = c->fdesc.ncounts;
+    std::copy(c->prior.begin(), c->prior.begin() + ncounts, counts);
+    if (c->P.hist == 3) {   // collision-avoidance records
+        hist_add_entries(c, rec, cnt, counts);
         return;
     }
     const GridDesc& g = c->gdesc;
     const int N = g.N, G = g.G, A = c->P.A;
-    const int XY = N * N * G * N, GG = N * N * G * G, NN = N * N, ncounts = c->fdesc.ncounts;
+    const int XY = N * N * G * N, GG = N * N * G * G;
     const uint32_t mask = rec[1];
-    std::copy(c->prior.begin(), c->prior.begin() + ncounts, counts);
     for (int a = 0; a < A; ++a)
         for (int f = 0; f < 2; ++f) {
             const bool with_goal = (mask >> (2 * a + f)) & 1u;
@@ -2255,21 +2255,7 @@ static void hist_materialize(const fba_ctx* c, const uint32_t* rec, uint32_t cnt
             const uint32_t m = with_goal ? 7u : 3u;
             std::memcpy(&counts[ncounts + 2 * a + f], &m, 4);
         }
-    int j = 0;
-    for (int a = 0; a < A; ++a) {
-        const int tbase = a * (2 * XY + GG), obase = A * (2 * XY + GG) + a * (2 * NN + G * G);
-        const bool mx = (mask >> (2 * a)) & 1u, my = (mask >> (2 * a + 1)) & 1u;
-        for (int q = 0; q < hist_count(cnt, a); ++q, ++j) {
-            const uint32_t en = rec[2 + j], s0 = en & 0x3ffu, s1 = (en >> 10) & 0x3ffu, ob = en >> 20;
-            const int x = hist_x(s0), y = hist_y(s0), gl = hist_g(s0), cell = x * N + y;
-            counts[tbase + (mx ? cell * G + gl : cell) * N + hist_x(s1)] += 1.0f;
-            counts[tbase + XY + (my ? cell * G + gl : cell) * N + hist_y(s1)] += 1.0f;
-            counts[tbase + 2 * XY + (cell * G + gl) * G + hist_g(s1)] += 1.0f;
-            counts[obase + x * N + hist_x(ob)] += 1.0f;
-            counts[obase + NN + y * N + hist_y(ob)] += 1.0f;
-            counts[obase + 2 * NN + gl * G + hist_g(ob)] += 1.0f;
-        }
-    }
+    hist_add_entries(c, rec, cnt, counts);
 }
 
 // particles [first, first + n) of slot `slot`'s filter, as the API speaks of particles (fp32 count tables whatever the record format)

@@ -61,7 +61,7 @@ void launch_belief_summary(const Problem& P, const DeviceState& D, const BeliefS
 // fba_belief_predict (fba_predict.hip): nq queries (s, a, s', o) answered for slots [first, first + count) into device buffers of the caller's;
 // a null output = not wanted.  History records: the caller zeroes hacc and supplies what the prior contributes (qn, qprior, ent_slot)
 constexpr int PREDICT_MAXQN = 16;   // nodes of one query: FS + FO
-constexpr int PREDICT_SLOTS = 6;    // entry-cell slots of a history record (summary_entry_cells)
+constexpr int PREDICT_SLOTS = HIST_ENTRY_CELLS;   // entry-cell slots of a history record (hist_entry_cells, fba_device.h)
 struct PredictSlotNode {            // the node whose cell an entry holds in slot k, for one query; out = 0: the slot is unused
     int32_t rb0, rb1;               // dense index where the queried row starts, per prior form (form 1: the parent-set bit `var` of the record is set)
     int32_t out, seg, val, var;     // row length; where the row's entries start in [trans | obsp]; the query's own value; parent-set bit or -1

@@ -2392,34 +2392,26 @@ __global__ void post_reset_kernel(Problem P, DeviceState D)
 // ---------------------------------------------------------------------------------------------
 // History particles: the same checksum over the particle's whole count table -- walked cell by cell in the dense
 // layout, prior value plus the number of entries that incremented the cell -- without ever building the table.
-// hist_next_cell: the smallest incremented cell index >= kmin and how many entries incremented it.
+// hist_next_cell: the smallest incremented cell index >= kmin (>= 0) and how many entries incremented it, for every record format
+// (the cells of an entry: hist_entry_cells, fba_device.h).
+template <int HIST>
 __device__ void hist_next_cell(const Problem& P, const uint32_t* rec, uint32_t cnt, int kmin, int& nxt, int& mult)
 {
-    const int N = P.gw_N, G = P.gw_G, A = P.A;
-    const int XY = N * N * G * N, GG = N * N * G * G, NN = N * N;
+    const HistDims dims = hist_dims<HIST>(P, P.ca);
     const uint32_t mask = rec[1];
     nxt = 0x7fffffff; mult = 0;
     int j = 0;
-    for (int a = 0; a < A; ++a) {
-        const int tbase = a * (2 * XY + GG), obase = A * (2 * XY + GG) + a * (2 * NN + G * G);
-        const bool mx = (mask >> (2 * a)) & 1u, my = (mask >> (2 * a + 1)) & 1u;
+    for (int a = 0; a < P.A; ++a)
         for (int q = 0; q < hist_count(cnt, a); ++q, ++j) {
-            const uint32_t en = rec[2 + j], s0 = en & 0x3ffu, s1 = (en >> 10) & 0x3ffu, ob = en >> 20;
-            const int x = hist_x(s0), y = hist_y(s0), gl = hist_g(s0), cell = x * N + y;
-            const int c[6] = {tbase + (mx ? cell * G + gl : cell) * N + hist_x(s1),
-                              tbase + XY + (my ? cell * G + gl : cell) * N + hist_y(s1),
-                              tbase + 2 * XY + (cell * G + gl) * G + hist_g(s1),
-                              obase + x * N + hist_x(ob),
-                              obase + NN + y * N + hist_y(ob),
-                              obase + 2 * NN + gl * G + hist_g(ob)};
+            int c[HIST_ENTRY_CELLS];
+            hist_entry_cells<HIST>(dims, mask, a, rec[2 + j], c);
 #pragma unroll
-            for (int k = 0; k < 6; ++k)
-                if (c[k] >= kmin) {
+            for (int k = 0; k < HIST_ENTRY_CELLS; ++k)
+                if (c[k] >= kmin) {   // (an unused cell is -1)
                     if (c[k] < nxt) { nxt = c[k]; mult = 1; }
                     else if (c[k] == nxt) ++mult;
                 }
         }
-    }
 }
 __device__ uint64_t hist_hash_counts(const Problem& P, const uint32_t* rec, uint32_t len, uint64_t h)
 {
@@ -2427,12 +2419,12 @@ __device__ uint64_t hist_hash_counts(const Problem& P, const uint32_t* rec, uint
     const int N = L.N, G = L.G, A = L.A, rows = N * N * G;
     const uint32_t mask = rec[1];
     int k = 0, nxt, mult;  // k: the cell's index in the dense table (the order the checksum is defined in)
-    hist_next_cell(P, rec, len, 0, nxt, mult);
+    hist_next_cell<1>(P, rec, len, 0, nxt, mult);
     auto visit = [&](float prior) {
         float v = prior;
         if (k == nxt) {
             v = prior + (float)mult;
-            hist_next_cell(P, rec, len, k + 1, nxt, mult);
+            hist_next_cell<1>(P, rec, len, k + 1, nxt, mult);
         }
         h = mix64(h ^ ((uint64_t)__float_as_uint(v) + ((uint64_t)k << 32)));
         ++k;
@@ -2461,69 +2453,33 @@ __device__ uint64_t hist_hash_counts(const Problem& P, const uint32_t* rec, uint
 
 // The same for the tabular model's records (Problem::hist == 2): cell (s*A + a)*S + s' of the transition table and phi_len + (a*S + s')*O + o
 // of the observation table per entry, over the dense prior (DeviceState::prior_dense).
-__device__ void tab_hist_next_cell(const Problem& P, const uint32_t* rec, uint32_t cnt, long long kmin, long long& nxt, int& mult)
-{
-    const int S = P.S, A = P.A, O = P.O;
-    nxt = 0x7fffffffffffffffll; mult = 0;
-    int j = 0;
-    for (int a = 0; a < A; ++a)
-        for (int q = 0; q < hist_count(cnt, a); ++q, ++j) {
-            const uint32_t en = rec[2 + j];
-            const int s0 = (int)(en & 0x3ffu), s1 = (int)((en >> 10) & 0x3ffu), ob = (int)(en >> 20);
-            const long long c[2] = {((long long)s0 * A + a) * S + s1, (long long)P.phi_len + ((long long)a * S + s1) * O + ob};
-#pragma unroll
-            for (int k = 0; k < 2; ++k)
-                if (c[k] >= kmin) {
-                    if (c[k] < nxt) { nxt = c[k]; mult = 1; }
-                    else if (c[k] == nxt) ++mult;
-                }
-        }
-}
 __device__ uint64_t tab_hist_hash_counts(const Problem& P, const float* prior, const uint32_t* rec, uint32_t len, uint64_t h)
 {
-    const long long dense = (long long)P.phi_len + (long long)P.A * P.S * P.O;
-    long long nxt;
-    int mult;
-    tab_hist_next_cell(P, rec, len, 0, nxt, mult);
-    for (long long k = 0; k < dense; ++k) {
+    const int dense = P.phi_len + P.A * P.S * P.O;   // (below 2^22 in every context that stores these records: hist_entry_cells)
+    int nxt, mult;
+    hist_next_cell<2>(P, rec, len, 0, nxt, mult);
+    for (int k = 0; k < dense; ++k) {
         float v = prior[k];
         if (k == nxt) {
             v = v + (float)mult;
-            tab_hist_next_cell(P, rec, len, k + 1, nxt, mult);
+            hist_next_cell<2>(P, rec, len, k + 1, nxt, mult);
         }
         h = mix64(h ^ ((uint64_t)__float_as_uint(v) + ((uint64_t)k << 32)));
     }
     return h;
 }
 
-// The same for the collision-avoidance records (Problem::hist == 3): the 4 + 2n cells per entry (ca_hist_cells) over the dense prior;
+// The same for the collision-avoidance records (Problem::hist == 3): the 4 + 2n cells per entry over the dense prior;
 // a cell's value is the prior's after `mult` additions of 1.0f, one at a time (not every prior value is exact under prior + mult).
-__device__ void ca_hist_next_cell(const Problem& P, const uint32_t* rec, uint32_t cnt, int kmin, int& nxt, int& mult)
-{
-    const CADesc* ca = P.ca;
-    nxt = 0x7fffffff; mult = 0;
-    int j = 0;
-    for (int a = 0; a < P.A; ++a)
-        for (int q = 0; q < hist_count(cnt, a); ++q, ++j) {
-            int c[6];
-            ca_hist_cells(P.A, ca->W, ca->H, ca->n, a, rec[2 + j], c);
-#pragma unroll
-            for (int k = 0; k < 6; ++k)
-                if (c[k] >= kmin) {
-                    if (c[k] < nxt) { nxt = c[k]; mult = 1; }
-                    else if (c[k] == nxt) ++mult;
-                }
-        }
-}
 __device__ uint64_t ca_hist_hash_counts(const Problem& P, const float* prior, const uint32_t* rec, uint32_t len, uint64_t h)
 {
     int nxt, mult;
-    ca_hist_next_cell(P, rec, len, 0, nxt, mult);
+    hist_next_cell<3>(P, rec, len, 0, nxt, mult);
     for (int k = 0; k < P.hist_row; ++k) {
         float v = prior[k];
         if (k == nxt) {
             for (int q = 0; q < mult; ++q) v += 1.0f;
-            ca_hist_next_cell(P, rec, len, k + 1, nxt, mult);
+            hist_next_cell<3>(P, rec, len, k + 1, nxt, mult);
         }
         h = mix64(h ^ ((uint64_t)__float_as_uint(v) + ((uint64_t)k << 32)));
     }
@@ -2540,16 +2496,15 @@ __global__ void __launch_bounds__(256) flush_kernel(Problem P, DeviceState D)
     if (tid < FBA_TRACE_HIST_BINS) s_hist[tid] = 0;
     const bool hist_on = D.trace_hist != nullptr && !D.cur[e].terminal;   // (no belief update after a terminal step, Episode.cpp:47-50)
     __syncthreads();
-    const size_t pb = pbase(P, e, D.bufsel[e]);
-    const bool lazy = slot_lazy(D, e);
+    const SlotRecs r = slot_recs(P, D, e);
+    const bool lazy  = slot_lazy(D, e);
     unsigned long long local = 0;
     for (int i = tid; i < P.N; i += 256) {
-        const float* cnt = P.hist ? D.p_rec + rec_base(P, D, e, D.bufsel[e]) * (size_t)P.Cs + (size_t)i * hist_stride(P, hist_total(D.hist_cnt[e]))
-                                  : D.p_rec + (rec_base(P, D, e, D.bufsel[e]) + i) * (size_t)P.Cs;
+        const float* cnt = r.rec + (size_t)i * r.stride;
         const int st = lazy ? lazy_state(P, D, e, i) : rec_state(cnt, P.C);
         if (hist_on && (unsigned)st < (unsigned)FBA_TRACE_HIST_BINS) atomicAdd(&s_hist[st], 1u);
         uint64_t h = mix64((uint64_t)i * 0x9E3779B97F4A7C15ull + (uint64_t)(uint32_t)st);
-        const double w = (P.belief == FBA_BELIEF_IMPORTANCE) ? D.p_weight[pb + i] : 0.0;
+        const double w = (P.belief == FBA_BELIEF_IMPORTANCE) ? D.p_weight[r.wb + i] : 0.0;
         h = mix64(h ^ (uint64_t)__double_as_longlong(w));
         if (P.ft_packed) {  // the counts themselves, then the mask word, as the dense blob has them
             const int FS = P.fd->FS, nc = 8 * FS + 4 + (2 << FS);
@@ -2560,9 +2515,9 @@ __global__ void __launch_bounds__(256) flush_kernel(Problem P, DeviceState D)
                 else v = packed_ftiger_view<4>(P, GlobalView{cnt}).at(k);
                 h = mix64(h ^ ((uint64_t)__float_as_uint(v) + ((uint64_t)k << 32)));
             }
-        } else if (P.hist == 3) h = ca_hist_hash_counts(P, D.prior_dense, reinterpret_cast<const uint32_t*>(cnt), D.hist_cnt[e], h);
-        else if (P.hist == 2) h = tab_hist_hash_counts(P, D.prior_dense, reinterpret_cast<const uint32_t*>(cnt), D.hist_cnt[e], h);
-        else if (P.hist) h = hist_hash_counts(P, reinterpret_cast<const uint32_t*>(cnt), D.hist_cnt[e], h);
+        } else if (P.hist == 3) h = ca_hist_hash_counts(P, D.prior_dense, reinterpret_cast<const uint32_t*>(cnt), r.cnt, h);
+        else if (P.hist == 2) h = tab_hist_hash_counts(P, D.prior_dense, reinterpret_cast<const uint32_t*>(cnt), r.cnt, h);
+        else if (P.hist) h = hist_hash_counts(P, reinterpret_cast<const uint32_t*>(cnt), r.cnt, h);
         else if (P.packed) {  // the checksum is over the counts themselves, whatever the storage (PackedView)
             const PackedView<GlobalView> pv{GlobalView{cnt}, D.prior_dense};
             const int dense = P.phi_len + P.A * P.S * P.O;

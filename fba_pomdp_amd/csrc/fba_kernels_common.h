@@ -1,5 +1,6 @@
-// fba_kernels_common.h -- device helpers shared by the search kernels (fba_search.hip) and the belief / episode kernels
-// (fba_kernels.hip): stream addressing, particle record accessors, filter sampling, tree node records, UCB.
+// fba_kernels_common.h -- device helpers shared by the search kernels (fba_search.hip), the belief / episode kernels
+// (fba_kernels.hip) and the read-only calls (fba_summary.hip, fba_predict.hip): stream addressing, particle record accessors,
+// the slot locator of the readers, filter sampling, tree node records, UCB.
 #pragma once
 
 #include <float.h>
@@ -59,6 +60,45 @@ __device__ __forceinline__ int lazy_state(const Problem& P, const Rng& g, int i)
     h.c2 = (g.c2 & 0xffff0000u) | FBA_PHASE_RESET;   // t = 0
     h.c1 = (uint32_t)i; h.draw = 0; h.keep_lo = 0; h.keep_hi = 0;
     return domain_start(P, h);
+}
+
+// where slot e's current records and weights are, for the kernels that only read a filter: the belief checksum (flush_kernel),
+// fba_belief_summary and fba_belief_predict
+struct SlotRecs {
+    const float* rec;   // first record
+    int stride;         // words between records
+    size_t wb;          // first weight (importance filters)
+    uint32_t cnt;       // history records: entries per action
+};
+__device__ __forceinline__ SlotRecs slot_recs(const Problem& P, const DeviceState& D, int e)
+{
+    SlotRecs r;
+    const int sel = D.bufsel[e];
+    r.cnt    = P.hist ? D.hist_cnt[e] : 0u;
+    r.stride = P.hist ? hist_stride(P, hist_total(r.cnt)) : P.Cs;
+    r.rec    = D.p_rec + rec_base(P, D, e, sel) * (size_t)P.Cs;
+    r.wb     = pbase(P, e, sel);
+    return r;
+}
+__device__ __forceinline__ double particle_weight(const Problem& P, const DeviceState& D, const SlotRecs& r, int i)
+{
+    return P.belief == FBA_BELIEF_IMPORTANCE ? D.p_weight[r.wb + i] : 1.0;
+}
+// cell k of a record's table as fba_belief_get speaks of it.  FMT: 0 fp32 counts, 1 packed tiger (PackedView), 2..4 packed factored tiger of
+// that many state features (PackedFtigerView; there k = the number of counts names the parent-set word)
+template <int FMT>
+__device__ __forceinline__ float record_count(const Problem& P, const DeviceState& D, const float* rec, int k)
+{
+    if (FMT == 0) return rec[k];
+    if (FMT == 1) return PackedView<GlobalView>{GlobalView{rec}, D.prior_dense}.at(k);
+    return packed_ftiger_view<(FMT >= 2 ? FMT : 2)>(P, GlobalView{rec}).at(k);
+}
+// mask word m of a record, as the dense blob has it
+__device__ __forceinline__ uint32_t record_mask_word(const Problem& P, const BeliefSummaryArgs& a, const float* rec, int m)
+{
+    if (P.hist) return ((__float_as_uint(rec[1]) >> m) & 1u) ? 7u : 3u;
+    if (P.ft_packed) return __float_as_uint(rec[a.ncounts / 2]);
+    return __float_as_uint(rec[a.ncounts + m]);
 }
 
 // WeightedFilter::sample (WeightedFilter.cpp:163-191) in device order: the largest i >= 1 whose

@@ -14,37 +14,6 @@
 
 namespace fba {
 
-// where slot e's current records and weights are, as flush_kernel finds them
-struct PredictRecs {
-    const float* rec;   // first record
-    int stride;         // words between records
-    size_t wb;          // first weight (importance filters)
-    uint32_t cnt;       // history records: entries per action
-};
-__device__ __forceinline__ PredictRecs predict_recs(const Problem& P, const DeviceState& D, int e)
-{
-    PredictRecs r;
-    const int sel = D.bufsel[e];
-    r.cnt    = P.hist ? D.hist_cnt[e] : 0u;
-    r.stride = P.hist ? hist_stride(P, hist_total(r.cnt)) : P.Cs;
-    r.rec    = D.p_rec + rec_base(P, D, e, sel) * (size_t)P.Cs;
-    r.wb     = pbase(P, e, sel);
-    return r;
-}
-__device__ __forceinline__ double predict_weight(const Problem& P, const DeviceState& D, const PredictRecs& r, int i)
-{
-    return P.belief == FBA_BELIEF_IMPORTANCE ? D.p_weight[r.wb + i] : 1.0;
-}
-// cell k of a record's table as fba_belief_get speaks of it.  FMT: 0 fp32 counts, 1 packed tiger, 2..4 packed factored tiger of that many
-// state features (there k = the number of counts names the parent-set word)
-template <int FMT>
-__device__ __forceinline__ float predict_count(const Problem& P, const DeviceState& D, const float* rec, int k)
-{
-    if (FMT == 0) return rec[k];
-    if (FMT == 1) return PackedView<GlobalView>{GlobalView{rec}, D.prior_dense}.at(k);
-    return packed_ftiger_view<(FMT >= 2 ? FMT : 2)>(P, GlobalView{rec}).at(k);
-}
-
 __device__ __forceinline__ double group_sum(double v, int width)   // over aligned groups of `width` lanes (a power of two)
 {
     for (int off = 1; off < width; off <<= 1) v += __shfl_xor(v, off);
@@ -60,9 +29,9 @@ __global__ void __launch_bounds__(256) predict_total_kernel(Problem P, DeviceSta
 {
     __shared__ double s_part[256];
     const int b = blockIdx.x, e = a.first + b, tid = threadIdx.x;
-    const PredictRecs r = predict_recs(P, D, e);
+    const SlotRecs r = slot_recs(P, D, e);
     double lw = 0.0;
-    for (int i = tid; i < P.N; i += 256) lw += predict_weight(P, D, r, i);
+    for (int i = tid; i < P.N; i += 256) lw += particle_weight(P, D, r, i);
     s_part[tid] = lw;
     __syncthreads();
     for (int st = 128; st > 0; st >>= 1) {
@@ -107,7 +76,7 @@ __device__ __forceinline__ QueryNode predict_query_node(const Problem& P, const 
 template <int FMT>
 __device__ __forceinline__ int predict_row(const Problem& P, const DeviceState& D, const BeliefPredictArgs& a, const NodeRegs& nd, uint64_t fv, const float* rec)
 {
-    const uint32_t mask = nd.var >= 0 ? __float_as_uint(predict_count<FMT>(P, D, rec, a.ncounts + nd.var)) : nd.fixed_mask;
+    const uint32_t mask = nd.var >= 0 ? __float_as_uint(record_count<FMT>(P, D, rec, a.ncounts + nd.var)) : nd.fixed_mask;
     return node_row(nullptr, nd, mask, fv);
 }
 
@@ -134,7 +103,7 @@ __global__ void __launch_bounds__(64 * PREDICT_WAVES) predict_rows_kernel(Proble
     }
     __syncthreads();
     if (!live) return;
-    const PredictRecs r = predict_recs(P, D, e);
+    const SlotRecs r = slot_recs(P, D, e);
     const size_t oq = (size_t)b * a.nq + q;
     const double W  = a.wtot[b];
     if (is_joint) {
@@ -151,12 +120,12 @@ __global__ void __launch_bounds__(64 * PREDICT_WAVES) predict_rows_kernel(Proble
                 int row       = s_row[wave][n];
                 if (s_nd[wave][n].var >= 0) row = predict_row<FMT>(P, D, a, s_nd[wave][n], s_fv[wave][n], rec);
                 double sum = 0.0;
-                for (int k = kl; k < len; k += Wd) sum += (double)predict_count<FMT>(P, D, rec, row + k);
+                for (int k = kl; k < len; k += Wd) sum += (double)record_count<FMT>(P, D, rec, row + k);
                 sum = group_sum(sum, Wd);
-                const double cv = (double)predict_count<FMT>(P, D, rec, row + s_val[wave][n]);
+                const double cv = (double)record_count<FMT>(P, D, rec, row + s_val[wave][n]);
                 prod *= sum > 0.0 ? cv / sum : 0.0;
             }
-            acc += valid ? predict_weight(P, D, r, i) * prod : 0.0;
+            acc += valid ? particle_weight(P, D, r, i) * prod : 0.0;
         }
         acc = groups_sum(acc, Wd);
         if (lane == 0) a.joint[oq] = acc / W;
@@ -182,13 +151,13 @@ __global__ void __launch_bounds__(64 * PREDICT_WAVES) predict_rows_kernel(Proble
             const float* rec = r.rec + (size_t)i * r.stride;
             const int row    = n.nd.var >= 0 ? predict_row<FMT>(P, D, a, n.nd, n.fv, rec) : row0;
             double sum = 0.0;
-            for (int k = kl; k < len; k += Wd) sum += (double)predict_count<FMT>(P, D, rec, row + k);
+            for (int k = kl; k < len; k += Wd) sum += (double)record_count<FMT>(P, D, rec, row + k);
             sum = group_sum(sum, Wd);
-            const double w = valid ? predict_weight(P, D, r, i) : 0.0;
+            const double w = valid ? particle_weight(P, D, r, i) : 0.0;
 #pragma unroll
             for (int t = 0; t < PREDICT_TILES; ++t) {
                 const int k = c0 + t * Wd + kl;
-                if (k < len && sum > 0.0) acc[t] += w * (double)predict_count<FMT>(P, D, rec, row + k) / sum;
+                if (k < len && sum > 0.0) acc[t] += w * (double)record_count<FMT>(P, D, rec, row + k) / sum;
             }
         }
 #pragma unroll
@@ -206,68 +175,6 @@ __global__ void __launch_bounds__(64 * PREDICT_WAVES) predict_rows_kernel(Proble
 // row sum R and the few raised cells; trans / obsp = (prior row * sum_i w_i / R_i + sum_i w_i delta_i / R_i) / W.  The host hands over, per
 // query and entry-cell slot, where the row starts per form, its prior sum and the prior rows themselves (PredictSlotNode, qprior).
 // ---------------------------------------------------------------------------------------------
-// the dense cells entry `en` of action `act` incremented: 6 (gridworld FBA-POMDP), 2 (tabular), 4 + 2n (collision avoidance; -1 = unused)
-template <int HIST>
-__device__ __forceinline__ void predict_entry_cells(const Problem& P, uint32_t mask, int act, uint32_t en, int (&c)[6])
-{
-    if (HIST == 3) {
-        ca_hist_cells(P.A, P.ca->W, P.ca->H, P.ca->n, act, en, c);
-        return;
-    }
-    const uint32_t s0 = en & 0x3ffu, s1 = (en >> 10) & 0x3ffu, ob = en >> 20;
-    if (HIST == 2) {
-        c[0] = ((int)s0 * P.A + act) * P.S + (int)s1;
-        c[1] = P.phi_len + (act * P.S + (int)s1) * P.O + (int)ob;
-        c[2] = c[3] = c[4] = c[5] = -1;
-        return;
-    }
-    const int N = P.gw_N, G = P.gw_G, A = P.A;
-    const int XY = N * N * G * N, GG = N * N * G * G, NN = N * N;
-    const int tbase = act * (2 * XY + GG), obase = A * (2 * XY + GG) + act * (2 * NN + G * G);
-    const bool mx = (mask >> (2 * act)) & 1u, my = (mask >> (2 * act + 1)) & 1u;
-    const int x = hist_x(s0), y = hist_y(s0), gl = hist_g(s0), cell = x * N + y;
-    c[0] = tbase + (mx ? cell * G + gl : cell) * N + hist_x(s1);
-    c[1] = tbase + XY + (my ? cell * G + gl : cell) * N + hist_y(s1);
-    c[2] = tbase + 2 * XY + (cell * G + gl) * G + hist_g(s1);
-    c[3] = obase + x * N + hist_x(ob);
-    c[4] = obase + NN + y * N + hist_y(ob);
-    c[5] = obase + 2 * NN + gl * G + hist_g(ob);
-}
-// visit(k, rel, mult): every distinct cell of the entries rec[2 + j0 .. j0 + na) that lies in the row [rb[k], rb[k] + len[k]) of slot k, once,
-// with the number of entries that name it
-template <int HIST, int NC, class F>
-__device__ __forceinline__ void predict_walk(const Problem& P, const uint32_t* rec, uint32_t mask, int act, int j0, int na, const int (&rb)[NC],
-                                             const int (&len)[NC], F visit)
-{
-    for (int j = j0; j < j0 + na; ++j) {
-        int c[6], rel[NC];
-        predict_entry_cells<HIST>(P, mask, act, rec[2 + j], c);
-        bool any = false;
-#pragma unroll
-        for (int k = 0; k < NC; ++k) {
-            rel[k] = c[k] - rb[k];
-            any    = any || (unsigned)rel[k] < (unsigned)len[k];
-        }
-        if (!any) continue;
-        int mult[NC];
-        bool first[NC];
-#pragma unroll
-        for (int k = 0; k < NC; ++k) { mult[k] = 0; first[k] = true; }
-        for (int j2 = j0; j2 < j0 + na; ++j2) {
-            int d[6];
-            predict_entry_cells<HIST>(P, mask, act, rec[2 + j2], d);
-#pragma unroll
-            for (int k = 0; k < NC; ++k) {
-                const bool same = d[k] == c[k];
-                mult[k] += same ? 1 : 0;
-                first[k] = first[k] && !(same && j2 < j);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < NC; ++k)
-            if ((unsigned)rel[k] < (unsigned)len[k] && first[k]) visit(k, rel[k], mult[k]);
-    }
-}
 template <int HIST>
 __global__ void __launch_bounds__(256) predict_hist_kernel(Problem P, DeviceState D, BeliefPredictArgs a)
 {
@@ -277,12 +184,13 @@ __global__ void __launch_bounds__(256) predict_hist_kernel(Problem P, DeviceStat
     const int TLOL = a.TL + a.OL, hw = TLOL + 2 * PREDICT_SLOTS + 1;
     for (int k = tid; k < hw; k += 256) s_acc[k] = 0.0;
     __syncthreads();
-    const PredictRecs r = predict_recs(P, D, e);
+    const SlotRecs r = slot_recs(P, D, e);
     // (more entries than a record has room for: the update kernels report that)
     const bool ok       = i < P.N && hist_total(r.cnt) <= P.hist_cap;
     const uint32_t* rec = reinterpret_cast<const uint32_t*>(r.rec + (size_t)(ok ? i : 0) * r.stride);
-    const double w      = ok ? predict_weight(P, D, r, i) : 0.0;
+    const double w      = ok ? particle_weight(P, D, r, i) : 0.0;
     const uint32_t mask = rec[1];
+    const HistDims dims = hist_dims<HIST>(P, P.ca);
     const bool rows     = a.trans || a.obsp;
     double* gacc        = a.hacc + (size_t)b * a.nq * hw;
     for (int q = 0; q < a.nq; ++q) {
@@ -309,20 +217,20 @@ __global__ void __launch_bounds__(256) predict_hist_kernel(Problem P, DeviceStat
             return (double)v - (double)p0;
         };
         if (HIST == 3) {
-            predict_walk<HIST, NC>(P, rec, mask, act, j0, na, rb, len, [&](int k, int rel, int mult) {
+            hist_distinct_cells<HIST, NC>(dims, rec, mask, act, j0, na, rb, len, [&](int k, int rel, int mult) {
                 const double d = delta_of(k, rel, mult);
                 R[k] += d;
                 if (rel == val[k]) hit[k] = d;
             });
             if (rows)
-                predict_walk<HIST, NC>(P, rec, mask, act, j0, na, rb, len, [&](int k, int rel, int mult) {
+                hist_distinct_cells<HIST, NC>(dims, rec, mask, act, j0, na, rb, len, [&](int k, int rel, int mult) {
                     unsafeAtomicAdd(&s_acc[seg[k] + rel], w * delta_of(k, rel, mult) / R[k]);
                 });
         } else {
             // prior + j is exact in these formats: an entry adds 1 to its cell and to its row, whatever the other entries name
             for (int j = j0; j < j0 + na; ++j) {
-                int c[6];
-                predict_entry_cells<HIST>(P, mask, act, rec[2 + j], c);
+                int c[HIST_ENTRY_CELLS];
+                hist_entry_cells<HIST>(dims, mask, act, rec[2 + j], c);
 #pragma unroll
                 for (int k = 0; k < NC; ++k) {
                     const int rel = c[k] - rb[k];
@@ -333,8 +241,8 @@ __global__ void __launch_bounds__(256) predict_hist_kernel(Problem P, DeviceStat
             }
             if (rows)
                 for (int j = j0; j < j0 + na; ++j) {
-                    int c[6];
-                    predict_entry_cells<HIST>(P, mask, act, rec[2 + j], c);
+                    int c[HIST_ENTRY_CELLS];
+                    hist_entry_cells<HIST>(dims, mask, act, rec[2 + j], c);
 #pragma unroll
                     for (int k = 0; k < NC; ++k) {
                         const int rel = c[k] - rb[k];

@@ -12,35 +12,6 @@
 
 namespace fba {
 
-// where slot e's current records and weights are, as flush_kernel finds them
-struct SlotRecs {
-    const float* rec;   // first record
-    int stride;         // words between records
-    size_t wb;          // first weight (importance filters)
-    uint32_t cnt;       // history records: entries per action
-};
-__device__ __forceinline__ SlotRecs slot_recs(const Problem& P, const DeviceState& D, int e)
-{
-    SlotRecs r;
-    const int sel = D.bufsel[e];
-    r.cnt    = P.hist ? D.hist_cnt[e] : 0u;
-    r.stride = P.hist ? hist_stride(P, hist_total(r.cnt)) : P.Cs;
-    r.rec    = D.p_rec + rec_base(P, D, e, sel) * (size_t)P.Cs;
-    r.wb     = pbase(P, e, sel);
-    return r;
-}
-__device__ __forceinline__ double particle_weight(const Problem& P, const DeviceState& D, const SlotRecs& r, int i)
-{
-    return P.belief == FBA_BELIEF_IMPORTANCE ? D.p_weight[r.wb + i] : 1.0;
-}
-// mask word m of a record, as the dense blob has it
-__device__ __forceinline__ uint32_t record_mask_word(const Problem& P, const BeliefSummaryArgs& a, const float* rec, int m)
-{
-    if (P.hist) return ((__float_as_uint(rec[1]) >> m) & 1u) ? 7u : 3u;
-    if (P.ft_packed) return __float_as_uint(rec[a.ncounts / 2]);
-    return __float_as_uint(rec[a.ncounts + m]);
-}
-
 // ---------------------------------------------------------------------------------------------
 // head: sum w, sum w^2, state mass, mass per (mask word, bit) -- and, for the gridworld records, the mass of the particles whose
 // x / y node has NO goal parent (the prior part of such a node is a split of the weight mass, summary_prior_kernel).
@@ -103,13 +74,6 @@ __global__ void __launch_bounds__(256) summary_head_kernel(Problem P, DeviceStat
 // FMT: 0 fp32 counts, 1 packed tiger (PackedView), 2..4 packed factored tiger of that many state features (PackedFtigerView).
 // ---------------------------------------------------------------------------------------------
 template <int FMT>
-__device__ __forceinline__ float record_count(const Problem& P, const DeviceState& D, const float* rec, int k)
-{
-    if (FMT == 0) return rec[k];
-    if (FMT == 1) return PackedView<GlobalView>{GlobalView{rec}, D.prior_dense}.at(k);
-    return packed_ftiger_view<(FMT >= 2 ? FMT : 2)>(P, GlobalView{rec}).at(k);
-}
-template <int FMT>
 __global__ void __launch_bounds__(256) summary_cols_kernel(Problem P, DeviceState D, BeliefSummaryArgs a)
 {
     __shared__ double s_part[256];
@@ -137,36 +101,8 @@ __global__ void __launch_bounds__(256) summary_cols_kernel(Problem P, DeviceStat
 // ---------------------------------------------------------------------------------------------
 // history records: mean = (sum_i w_i prior_i[k] + sum_i w_i delta_i[k]) / W.  delta is non-zero only at the cells a particle's
 // entries name, so a thread walks one particle's entries and adds w * delta to the slot's zeroed table with fp64 atomics --
-// once per distinct cell, with the cell's multiplicity (cells of two nodes, or of two actions, never coincide, so a cell is
-// compared with the same cell of the other entries of its action only).
+// once per distinct cell, with the cell's multiplicity (hist_distinct_cells, fba_device.h).
 // ---------------------------------------------------------------------------------------------
-// the dense cells entry `en` of action `act` incremented: 6 (gridworld FBA-POMDP), 2 (tabular), 4 + 2n (collision avoidance; -1 = unused)
-template <int HIST>
-__device__ __forceinline__ void summary_entry_cells(const Problem& P, uint32_t mask, int act, uint32_t en, int (&c)[6])
-{
-    if (HIST == 3) {
-        ca_hist_cells(P.A, P.ca->W, P.ca->H, P.ca->n, act, en, c);
-        return;
-    }
-    const uint32_t s0 = en & 0x3ffu, s1 = (en >> 10) & 0x3ffu, ob = en >> 20;
-    if (HIST == 2) {   // (10-bit states, four actions, 12-bit observations: below 2^31)
-        c[0] = ((int)s0 * P.A + act) * P.S + (int)s1;
-        c[1] = P.phi_len + (act * P.S + (int)s1) * P.O + (int)ob;
-        c[2] = c[3] = c[4] = c[5] = -1;
-        return;
-    }
-    const int N = P.gw_N, G = P.gw_G, A = P.A;
-    const int XY = N * N * G * N, GG = N * N * G * G, NN = N * N;
-    const int tbase = act * (2 * XY + GG), obase = A * (2 * XY + GG) + act * (2 * NN + G * G);
-    const bool mx = (mask >> (2 * act)) & 1u, my = (mask >> (2 * act + 1)) & 1u;
-    const int x = hist_x(s0), y = hist_y(s0), gl = hist_g(s0), cell = x * N + y;
-    c[0] = tbase + (mx ? cell * G + gl : cell) * N + hist_x(s1);
-    c[1] = tbase + XY + (my ? cell * G + gl : cell) * N + hist_y(s1);
-    c[2] = tbase + 2 * XY + (cell * G + gl) * G + hist_g(s1);
-    c[3] = obase + x * N + hist_x(ob);
-    c[4] = obase + NN + y * N + hist_y(ob);
-    c[5] = obase + 2 * NN + gl * G + hist_g(ob);
-}
 // A workgroup's 256 particles mostly name the same few cells (a filter is resampled after every update, and the slot's particles have
 // taken the same actions), so their terms meet in a small LDS table first -- open addressing, a bounded probe, straight to the global
 // table where that finds no place -- and a workgroup sends one global atomic per distinct cell.  (Measured without the table: 20 entries
@@ -191,7 +127,7 @@ struct SummaryCellTable {
 template <int HIST>
 __global__ void __launch_bounds__(256) summary_scatter_kernel(Problem P, DeviceState D, BeliefSummaryArgs a)
 {
-    constexpr int NC = HIST == 2 ? 2 : 6;
+    constexpr int NC = HIST == 2 ? 2 : HIST_ENTRY_CELLS;
     __shared__ int s_key[SUMMARY_HASH];
     __shared__ double s_val[SUMMARY_HASH];
     const int b = blockIdx.y, e = a.first + b, tid = threadIdx.x, i = blockIdx.x * 256 + tid;
@@ -205,38 +141,23 @@ __global__ void __launch_bounds__(256) summary_scatter_kernel(Problem P, DeviceS
         const uint32_t* rec = reinterpret_cast<const uint32_t*>(r.rec + (size_t)i * r.stride);
         const double w      = particle_weight(P, D, r, i);
         const uint32_t mask = rec[1];
+        const HistDims dims = hist_dims<HIST>(P, P.ca);
+        int rb[NC], len[NC];
+#pragma unroll
+        for (int k = 0; k < NC; ++k) { rb[k] = 0; len[k] = a.ncounts; }   // every cell of the table
         int j0 = 0;
         for (int act = 0; act < P.A && act < 4; ++act) {
             const int na = hist_count(r.cnt, act);
-            for (int j = j0; j < j0 + na; ++j) {
-                int c[6], mult[NC];
-                bool first[NC];
-                summary_entry_cells<HIST>(P, mask, act, rec[2 + j], c);
-#pragma unroll
-                for (int k = 0; k < NC; ++k) { mult[k] = 0; first[k] = true; }
-                for (int j2 = j0; j2 < j0 + na; ++j2) {
-                    int d[6];
-                    summary_entry_cells<HIST>(P, mask, act, rec[2 + j2], d);
-#pragma unroll
-                    for (int k = 0; k < NC; ++k) {
-                        const bool same = d[k] == c[k];
-                        mult[k] += same ? 1 : 0;
-                        first[k] = first[k] && !(same && j2 < j);
-                    }
+            hist_distinct_cells<HIST, NC>(dims, rec, mask, act, j0, na, rb, len, [&](int, int c, int mult) {
+                double delta = (double)mult;
+                if (HIST == 3) {   // the prior's count after `mult` single additions of 1.0f, which need not be prior + mult
+                    const float p0 = D.prior_dense[c];
+                    float v = p0;
+                    for (int q = 0; q < mult; ++q) v += 1.0f;
+                    delta = (double)v - (double)p0;
                 }
-#pragma unroll
-                for (int k = 0; k < NC; ++k)
-                    if (first[k] && (unsigned)c[k] < (unsigned)a.ncounts) {   // (also drops the -1 of an unused cell)
-                        double delta = (double)mult[k];
-                        if (HIST == 3) {   // the prior's count after `mult` single additions of 1.0f, which need not be prior + mult
-                            const float p0 = D.prior_dense[c[k]];
-                            float v = p0;
-                            for (int q = 0; q < mult[k]; ++q) v += 1.0f;
-                            delta = (double)v - (double)p0;
-                        }
-                        tab.add(c[k], w * delta);
-                    }
-            }
+                tab.add(c, w * delta);
+            });
             j0 += na;
         }
     }

@@ -189,6 +189,16 @@ def test_every_record_format(name, kind, domain, model, belief, env, kw, nbytes,
         assert np.all(summ.edge_prob[:, :, 3:] == 0.0)
     if model == TABLE or name.startswith("collision"):
         assert summ.edge_prob is None
+    if "history" in name:       # _drive's two steps of one action: some particle holds a cell that two of its entries raised
+        prior, (nc, _) = eng.prior(), _layout(eng)
+        lo = 0
+        if name.startswith("gridworld3_history"):   # the observation nodes' cells, the last ones: their prior is the same under every parent set
+            lay = eng.factored_layout()
+            lo = nc - eng.A * sum(int(s) ** 2 for s in lay.obs_feature_size[:lay.n_obs_features])
+            assert lo == nc - eng.A * (2 * 3 * 3 + 3 * 3)
+        raised = max(float(np.max(r["counts"][:, lo:nc] - prior[None, lo:nc])) for r in refs.values())
+        print(f"{name}: a cell stands {raised} above the prior")
+        assert raised >= 2.0
     eng.close()
 
 
