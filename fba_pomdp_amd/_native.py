@@ -12,7 +12,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB_PATH = os.environ.get("FBA_LIB") or os.path.join(HERE, "libfba_hip.so")   # (FBA_LIB: an instrumented build of the same sources, scripts/search_regions.py)
-SOURCES = [os.path.join(HERE, "csrc", f) for f in ("fba_search.hip", "fba_kernels.hip", "fba_summary.hip", "fba_predict.hip", "fba_engine.hip")]
+SOURCES = [os.path.join(HERE, "csrc", f) for f in ("fba_search.hip", "fba_kernels.hip", "fba_summary.hip", "fba_predict.hip", "fba_forecast.hip", "fba_engine.hip")]
 HEADERS = [os.path.join(HERE, "csrc", f) for f in ("fba_device.h", "fba_state.h", "fba_kernels.h", "fba_kernels_common.h", "fba_search_hist2.inc")] + [
     os.path.join(ROOT, "include", "fba_hip.h")]
 OBJ_DIR = os.path.join(HERE, "build")   # per-source objects (git-ignored): a change to one translation unit recompiles that one
@@ -122,7 +122,7 @@ EXPORTS = [
     "fba_abi_version", "fba_default_config", "fba_create", "fba_destroy", "fba_last_error",
     "fba_domain_sizes", "fba_counts_len", "fba_slots", "fba_particle_bytes", "fba_set_model_tabular", "fba_set_model_factored", "fba_log_bd_score", "fba_selftest_lgamma", "fba_get_prior", "fba_get_factored_layout",
     "fba_set_position", "fba_belief_init", "fba_belief_reset_domain_state", "fba_select_action",
-    "fba_belief_update", "fba_belief_get", "fba_belief_get_particle", "fba_belief_set", "fba_belief_get_fully_connected", "fba_belief_get_nested", "fba_belief_get_shadow", "fba_belief_summary", "fba_predict_lens", "fba_belief_predict", "fba_last_step_info",
+    "fba_belief_update", "fba_belief_get", "fba_belief_get_particle", "fba_belief_set", "fba_belief_get_fully_connected", "fba_belief_get_nested", "fba_belief_get_shadow", "fba_belief_summary", "fba_predict_lens", "fba_belief_predict", "fba_belief_forecast", "fba_last_step_info",
     "fba_run_planning", "fba_run_bapomdp", "fba_run_ticks", "fba_get_returns", "fba_get_counters", "fba_get_return_sums",
     "fba_get_kernel_times", "fba_reset_kernel_times", "fba_trace_count", "fba_get_trace", "fba_get_trace_hist",
     "fba_selftest_ucb", "fba_stat_add", "fba_stat_var", "fba_stat_stder",
@@ -220,6 +220,8 @@ def load():
     if not os.environ.get("FBA_LIB") or hasattr(L, "fba_belief_predict"):
         L.fba_predict_lens.argtypes = [vp, P(C.c_int32), P(C.c_int32)]
         L.fba_belief_predict.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp]   # four int32 query arrays; trans, obsp, joint
+    if not os.environ.get("FBA_LIB") or hasattr(L, "fba_belief_forecast"):
+        L.fba_belief_forecast.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]   # action, obs (int32); next_mass, post_mass, evidence
     L.fba_last_step_info.argtypes = [vp, vp]
     L.fba_run_planning.argtypes = [vp, P(Stat)]
     L.fba_run_bapomdp.argtypes = [vp, P(Stat)]

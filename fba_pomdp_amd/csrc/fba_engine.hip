@@ -2605,6 +2605,115 @@ int fba_belief_predict(fba_ctx* c, int32_t first, int32_t count, int32_t nq, con
     return check_fault(c);
 }
 
+// The one-step predictive of slots [first, first + count) after action[slot] and under obs[slot], reduced on the device (fba_forecast.hip),
+// a chunk of slots at a time so that the fp64 buffers of a chunk stay below 256 MB.  Reads the context only, as fba_belief_summary does.
+int fba_belief_forecast(fba_ctx* c, int32_t first, int32_t count, const int32_t* action, const int32_t* obs, double* next_mass, double* post_mass,
+                        double* evidence)
+{
+    if (!c) return FBA_EINVAL;
+    const Problem& P = c->P;
+    if (P.nested)
+        return fail(c, FBA_EINVAL, "fba_belief_forecast: the nested belief's particles are (model, state filter) pairs; read them with "
+                                   "fba_belief_get and fba_belief_get_nested");
+    if (P.model == FBA_MODEL_POMDP) return fail(c, FBA_EINVAL, "fba_belief_forecast: a plain POMDP belief has no counts (fba_counts_len is 0)");
+    if (first < 0 || count < 0 || (long long)first + count > P.E)
+        return fail(c, FBA_EINVAL, "fba_belief_forecast: slots [%d, %lld) are not within the context's %d", first, (long long)first + count, P.E);
+    if (!next_mass && !post_mass && !evidence) return FBA_OK;
+    if (!obs && (post_mass || evidence)) return fail(c, FBA_EINVAL, "fba_belief_forecast: post_mass and evidence need the observations (obs is NULL)");
+    if (count == 0) return FBA_OK;
+    if (!action) return fail(c, FBA_EINVAL, "fba_belief_forecast: the action array is missing");
+    for (int b = 0; b < count; ++b) {
+        if (action[b] < 0 || action[b] >= P.A)
+            return fail(c, FBA_EINVAL, "fba_belief_forecast: slot %d: action %d is outside the model's %d actions", first + b, action[b], P.A);
+        if (obs && (obs[b] < 0 || obs[b] >= P.O))
+            return fail(c, FBA_EINVAL, "fba_belief_forecast: slot %d: observation %d is outside the model's %d observations", first + b, obs[b], P.O);
+    }
+    const bool factored = P.model == FBA_MODEL_BA_FACTORED;
+    const FDesc& fd = c->fdesc;
+    const int S = P.S, A = P.A, FS = factored ? fd.FS : 1, FO = factored ? fd.FO : 1, nn = FS + FO;
+    if (FS > MAXF || FO > MAXF || nn > PREDICT_MAXQN) return fail(c, FBA_ESTATE, "fba_belief_forecast: %d + %d nodes per action (at most %d each are served)", FS, FO, MAXF);
+    if (P.hist == 1 && (FS != 3 || FO != 3 || fd.nvar != 2 * A))
+        return fail(c, FBA_ESTATE, "fba_belief_forecast: gridworld records without their %d parent-set words", 2 * A);
+    if (P.hist == 3 && (FS > 4 || FO > 2)) return fail(c, FBA_ESTATE, "fba_belief_forecast: collision-avoidance records of %d + %d nodes", FS, FO);
+    // where node j's entries start in a particle's transition table, its rows in the observation table; the rows of the max layout.  The
+    // sizes are those of action 0's nodes: every action's nodes have them (checked)
+    std::vector<int32_t> seg((size_t)nn, 0), rows((size_t)nn, 1);
+    int TL = 0, RL = 0, longest = 1;
+    for (int j = 0; j < nn; ++j) {
+        int len, nrows;
+        if (!factored) { len = j == 0 ? S : P.O; nrows = j == 0 ? S * A : S; }
+        else {
+            const bool T = j < FS;
+            const FNode& n0 = fd.nodes[T ? j : A * FS + (j - FS)];
+            len = n0.out;
+            nrows = 1;
+            for (int p = 0; p < n0.nmax; ++p)
+                if (n0.var >= 0 || ((n0.fixed_mask >> p) & 1u)) nrows *= n0.psz[p];
+            for (int a = 0; a < A; ++a) {
+                const FNode& nd = fd.nodes[T ? a * FS + j : A * FS + a * FO + (j - FS)];
+                int r = 1;
+                for (int p = 0; p < nd.nmax; ++p)
+                    if (nd.var >= 0 || ((nd.fixed_mask >> p) & 1u)) r *= nd.psz[p];
+                if (nd.out != len || nd.out != (T ? fd.Ssz[j] : fd.Osz[j - FS]) || nd.nmax > MAXF) return fail(c, FBA_ESTATE, "fba_belief_forecast: node %d of action %d does not fit the layout", j, a);
+                if (P.hist == 1 && nd.var >= 0 && (nd.var != 2 * a + j || j > 1)) return fail(c, FBA_ESTATE, "fba_belief_forecast: parent-set word %d at node T(%d, %d)", nd.var, a, j);
+                nrows = std::max(nrows, r);
+            }
+        }
+        rows[(size_t)j] = nrows;
+        if (j < FS) { seg[(size_t)j] = TL; TL += len; }
+        else { seg[(size_t)j] = RL; RL += nrows; }
+        longest = std::max(longest, len);
+    }
+    if (P.hist) {   // a slot whose records hold more entries than they have room for has no readable filter (the update kernels report it)
+        std::vector<uint32_t> cnt((size_t)count);
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpy(cnt.data(), c->D.hist_cnt + first, (size_t)count * 4, hipMemcpyDeviceToHost));
+        for (int b = 0; b < count; ++b)
+            if (hist_total(cnt[(size_t)b]) > P.hist_cap)
+                return fail(c, FBA_ESTATE, "fba_belief_forecast: slot %d: the history records hold %d entries, more than their %d", first + b, hist_total(cnt[(size_t)b]), P.hist_cap);
+    }
+    // particles per workgroup: what fits the LDS
+    const size_t fixed = forecast_lds_bytes(TL, RL, nn, 0, P.hist != 0), per = forecast_lds_bytes(TL, RL, nn, 1, P.hist != 0) - fixed;
+    if (fixed + per > (size_t)FORECAST_LDS)
+        return fail(c, FBA_ESTATE, "fba_belief_forecast: one particle's factor tables (%d transition entries, %d observation rows) do not fit the kernel's LDS", TL, RL);
+    const int wg = (int)std::min<size_t>({(size_t)256, (size_t)P.N, ((size_t)FORECAST_LDS - fixed) / per});
+    ScratchBuf<int32_t> d_in, d_meta;
+    HIPCHK(c, d_in.alloc((size_t)count * 2));
+    HIPCHK(c, d_meta.alloc((size_t)nn * 2));
+    HIPCHK(c, hipMemcpyAsync(d_in.p, action, (size_t)count * 4, hipMemcpyHostToDevice, c->stream));
+    if (obs) HIPCHK(c, hipMemcpyAsync(d_in.p + count, obs, (size_t)count * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_meta.p, seg.data(), (size_t)nn * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_meta.p + nn, rows.data(), (size_t)nn * 4, hipMemcpyHostToDevice, c->stream));
+    const size_t per_slot = (size_t)S * 4 + 1;
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>({(size_t)count, (size_t)32768, ((size_t)256 << 20) / (per_slot * 8)}));
+    ScratchBuf<double> d_acc, d_next, d_post, d_ev;
+    HIPCHK(c, d_acc.alloc((size_t)chunk * 2 * S));
+    if (next_mass) HIPCHK(c, d_next.alloc((size_t)chunk * S));
+    if (post_mass) HIPCHK(c, d_post.alloc((size_t)chunk * S));
+    if (evidence) HIPCHK(c, d_ev.alloc((size_t)chunk));
+    for (int done = 0; done < count; done += chunk) {
+        const int n = std::min(chunk, count - done);
+        BeliefForecastArgs a{};
+        a.first = first + done; a.count = n;
+        a.action = d_in.p + done; a.obs = obs ? d_in.p + count + done : nullptr;
+        a.next_mass = d_next.p; a.post_mass = d_post.p; a.evidence = d_ev.p; a.acc = d_acc.p;
+        a.nT = FS; a.nO = FO; a.TL = TL; a.RL = RL; a.chunk = wg;
+        a.ncounts = factored ? fd.ncounts : c->dense_C;
+        a.jw = 1;
+        while (a.jw < longest && a.jw < 64) a.jw <<= 1;
+        a.ft_FS = factored ? fd.FS : 0;
+        a.seg = d_meta.p; a.rows = d_meta.p + nn;
+        HIPCHK(c, hipMemsetAsync(d_acc.p, 0, (size_t)n * 2 * S * 8, c->stream));
+        launch_belief_forecast(P, c->D, a, c->stream);
+        HIPCHK(c, hipGetLastError());
+        if (next_mass) HIPCHK(c, hipMemcpyAsync(next_mass + (size_t)done * S, d_next.p, (size_t)n * S * 8, hipMemcpyDeviceToHost, c->stream));
+        if (post_mass) HIPCHK(c, hipMemcpyAsync(post_mass + (size_t)done * S, d_post.p, (size_t)n * S * 8, hipMemcpyDeviceToHost, c->stream));
+        if (evidence) HIPCHK(c, hipMemcpyAsync(evidence + (size_t)done, d_ev.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return check_fault(c);
+}
+
 int fba_belief_set(fba_ctx* c, int32_t slot, const int32_t* state, const double* weight, const float* counts)
 {
     if (!c || slot < 0 || slot >= c->P.E) return FBA_EINVAL;

@@ -81,6 +81,28 @@ struct BeliefPredictArgs {
     double* hacc;               // history records: [count][nq][TL + OL + 2 * PREDICT_SLOTS + 1] raised terms, sum w / R per (slot, form), joint sum
 };
 void launch_belief_predict(const Problem& P, const DeviceState& D, const BeliefPredictArgs& a, hipStream_t st);
+// fba_belief_forecast (fba_forecast.hip): the one-step predictive of slots [first, first + count) after action[slot] (and under obs[slot])
+// into device buffers of the caller's; a null output = not wanted, obs may be null where only next_mass is.  The caller zeroes acc
+struct BeliefForecastArgs {
+    int32_t first, count;
+    const int32_t *action, *obs;                 // [count]
+    double *next_mass, *post_mass, *evidence;    // [count][S], [count][S], [count]
+    double* acc;                                 // [count][2][S]: sum_i w_i p_i(s'), sum_i w_i p_i(s') l_i(s')
+    int32_t nT, nO;             // transition / observation nodes of an action (1 / 1 for a tabular model)
+    int32_t TL, RL;             // entries of a particle's transition rows; rows of its observation nodes in the max layout
+    int32_t chunk;              // particles per workgroup (at most 256)
+    int32_t ncounts, jw, ft_FS; // counts of a particle's table; lanes that share one row (a power of two); packed factored tiger: state features
+    const int32_t* seg;         // [nT + nO] where node j's entries start among the TL (j < nT), its rows among the RL
+    const int32_t* rows;        // [nT + nO] rows of node j in the max layout
+};
+constexpr int FORECAST_LDS = 63 * 1024;   // dynamic LDS a forecast workgroup may use (the node descriptions take the rest of 64 KB)
+// dynamic LDS of one forecast_chunk_kernel workgroup: per particle the fp64 factor tables (history records: the observation rows' sums
+// and counts apart), weight, state and a parent-set word per node; history records: the prior's observation row sums and counts once
+inline size_t forecast_lds_bytes(int TL, int RL, int nn, int chunk, bool hist)
+{
+    return ((size_t)chunk * ((size_t)TL + (size_t)RL * (hist ? 2 : 1) + 1) + (hist ? (size_t)2 * RL : 0)) * sizeof(double) + (size_t)chunk * (1 + nn) * 4;
+}
+void launch_belief_forecast(const Problem& P, const DeviceState& D, const BeliefForecastArgs& a, hipStream_t st);
 void launch_uniform_scan(int n, double* w_tmp, double* out, double* total, double* ctot, hipStream_t st);
 
 }  // namespace fba

@@ -37,6 +37,15 @@ class BeliefPrediction:
         self.obs_offsets = obs_offsets
 
 
+class BeliefForecast:
+    """What Engine.belief_forecast returns: numpy arrays with one row per slot of the range (None where not asked for)."""
+
+    def __init__(self, next_mass, post_mass, evidence):
+        self.next_mass = next_mass   # [slots][S] predictive next-state marginal
+        self.post_mass = post_mass   # [slots][S] Rao-Blackwellised posterior, unnormalised: its sum over the states is the evidence
+        self.evidence = evidence     # [slots]    P(obs | belief, action)
+
+
 class BeliefSummary:
     """What Engine.belief_summary returns: numpy arrays with one row per slot of the range (None where not asked for)."""
 
@@ -283,6 +292,24 @@ class Engine:
             t_off = np.concatenate(([0], np.cumsum(lay.state_feature_size[:lay.n_state_features]))).astype(np.int64)
             o_off = np.concatenate(([0], np.cumsum(lay.obs_feature_size[:lay.n_obs_features]))).astype(np.int64)
         return BeliefPrediction(tr, ob, jt, t_off, o_off)
+
+    def belief_forecast(self, action, obs=None, first=0, count=None, next_mass=True, post_mass=True, evidence=True):
+        """The one-step predictive of slots [first, first + count) on the device (fba_belief_forecast): every particle's own domain state
+        propagated through its own model by `action` (a scalar, or one per slot of the range).  `next_mass[slot, s']` is the predictive
+        next-state marginal, `post_mass[slot, s']` the exact (Rao-Blackwellised) domain-state marginal after observing `obs`, unnormalised,
+        and `evidence[slot]` its sum: P(obs | belief, action), the acceptance rate the rejection update is to expect.  `obs` may be None
+        where only `next_mass` is asked for.  Returns a BeliefForecast; outputs not asked for are None.  Read-only and outside the parity
+        contract: the last bits may differ from call to call."""
+        count = self.slots - first if count is None else count
+        n = max(count, 0)
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(action, np.int32), (n,)))
+        o = None if obs is None else np.ascontiguousarray(np.broadcast_to(np.asarray(obs, np.int32), (n,)))
+        nm = np.zeros((n, self.S), np.float64) if next_mass else None
+        pm = np.zeros((n, self.S), np.float64) if post_mass else None
+        ev = np.zeros(n, np.float64) if evidence else None
+        ptr = lambda x: None if x is None else x.ctypes.data
+        self._chk(self.L.fba_belief_forecast(self.h, first, count, ptr(a), ptr(o), ptr(nm), ptr(pm), ptr(ev)))
+        return BeliefForecast(nm, pm, ev)
 
     def belief_get_fully_connected(self, slot=0):
         """The second filter of the reinvigoration (fully connected) / cheating (correct graph) belief."""

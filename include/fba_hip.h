@@ -342,6 +342,42 @@ int fba_belief_predict(fba_ctx* ctx, int32_t first, int32_t count, int32_t nq,
                        double* trans,  /* [count][nq][TL] */
                        double* obsp,   /* [count][nq][OL] */
                        double* joint); /* [count][nq]     */
+/* The filter's one-step predictive on the device: what the posterior of each slot in [first, first + count) says about the step that takes
+ * action[slot - first] and observes obs[slot - first] -- each particle's OWN domain state s_i propagated through its OWN model c_i.  With
+ * s_i the state fba_belief_get returns for particle i (a lazily reset rejection filter included), c_i its fp32 table, w_i its weight (1.0 in
+ * a flat filter), W = sum w_i and theta_i(row)[k] = c_i[row + k] / sum_k c_i[row + k] in fp64 (a row whose counts sum to 0 gives 0), as for
+ * fba_belief_predict:
+ *   tabular   p_i(s') = theta_i(phi row (s_i, a))[s']        l_i(s') = theta_i(psi row (a, s'))[o]
+ *   factored  p_i(s') = prod_f theta_i,T(a,f)(row chosen by particle i's OWN parent set from the features of s_i)[s'_f]
+ *             l_i(s') = prod_g theta_i,O(a,g)(row chosen from the features of s')[o_g]
+ *             rows and features exactly as the layout comment above states them (DBNNode::cptIndex): the observation row is chosen by the
+ *             NEW state.
+ *   next_mass[slot][s'] = sum_i w_i p_i(s') / W              the predictive next-state marginal
+ *   post_mass[slot][s'] = sum_i w_i p_i(s') l_i(s') / W      the Rao-Blackwellised posterior, UNNORMALISED: its sum over s' is the evidence
+ *   evidence [slot]     = sum_i w_i sum_s' p_i(s') l_i(s') / W   P(o | b, a): the expected acceptance rate of the rejection update, the
+ *                                                            expected ratio of the importance filter's weight totals
+ * A particle whose state is outside [0, S) contributes nothing, as in state_mass of fba_belief_summary.  Any output pointer may be NULL (all
+ * three: FBA_OK, nothing is done); obs may be NULL iff post_mass and evidence are.  Evaluated from whatever record format the context stores,
+ * without building a particle's table anywhere.  Serves the main filter of every belief but the nested one, in either Dirichlet mode, the
+ * point-estimate belief's one particle included; FBA_EINVAL for the nested belief, a plain POMDP context, a slot range outside the context,
+ * an action or observation index out of range (the message names the slot) and obs == NULL while post_mass or evidence is asked for.
+ * FBA_ESTATE where the model does not fit the kernels: one particle's fp64 factor tables -- (TL + R + 1) * 8 + (1 + nodes) * 4 bytes, TL the
+ * entries of the transition rows (S for a tabular model) and R the rows of an action's observation nodes (S for a tabular model); history
+ * records: R counted twice, plus R * 16 once -- must fit 63 KB of LDS, so a tabular model of fp32 records is served up to S = 4 030; more than
+ * FBA_MAX_FEATURES transition or observation nodes, a layout whose nodes differ in size between actions, and a slot whose history records
+ * hold more entries than they have room for are refused the same way.  A slot whose weights are all 0 gives 0.0 in every output.
+ * Read-only: no buffer, flag, counter, Philox position, trace record or belief_hash changes, so the call may stand between any two others,
+ * after fba_run_*, and on inactive slots.  The call is OUTSIDE the parity contract: it is not the simulator's float arithmetic
+ * (expected_mult_at, fact_obs_prob), the order of its fp64 additions is the engine's choice and need not repeat bit for bit from call to
+ * call.  Every entry of next_mass and post_mass is within 8 * (particles + F * (L + 2)) * 2^-53 relative of the exact value (L the longest
+ * row; F the transition nodes of an action for next_mass, 1 for a tabular model, and all nodes of a step for post_mass, 2 for a tabular
+ * model), evidence within 8 * (particles + S + F * (L + 2)) * 2^-53, and exactly 0.0 where every term is. */
+int fba_belief_forecast(fba_ctx* ctx, int32_t first, int32_t count,
+                        const int32_t* action,   /* [count], one per slot of the range                  */
+                        const int32_t* obs,      /* [count]; may be NULL iff post_mass and evidence are */
+                        double* next_mass,       /* [count][S] */
+                        double* post_mass,       /* [count][S] */
+                        double* evidence);       /* [count]    */
 /* per-slot record of the last select_action / belief_update (root statistics, rejection count,
  * belief checksum) */
 int fba_last_step_info(fba_ctx* ctx, fba_trace_rec* recs /* [slots] */);
