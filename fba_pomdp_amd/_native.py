@@ -12,7 +12,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB_PATH = os.environ.get("FBA_LIB") or os.path.join(HERE, "libfba_hip.so")   # (FBA_LIB: an instrumented build of the same sources, scripts/search_regions.py)
-SOURCES = [os.path.join(HERE, "csrc", f) for f in ("fba_search.hip", "fba_kernels.hip", "fba_summary.hip", "fba_predict.hip", "fba_forecast.hip", "fba_engine.hip")]
+SOURCES = [os.path.join(HERE, "csrc", f) for f in ("fba_search.hip", "fba_kernels.hip", "fba_summary.hip", "fba_predict.hip", "fba_forecast.hip", "fba_probe.hip", "fba_engine.hip")]
 HEADERS = [os.path.join(HERE, "csrc", f) for f in ("fba_device.h", "fba_state.h", "fba_kernels.h", "fba_kernels_common.h", "fba_search_hist2.inc")] + [
     os.path.join(ROOT, "include", "fba_hip.h")]
 OBJ_DIR = os.path.join(HERE, "build")   # per-source objects (git-ignored): a change to one translation unit recompiles that one
@@ -116,6 +116,13 @@ class BeliefSummaryHead(C.Structure):   # fba_belief_summary_head
 
 SUMMARY_HEAD_DTYPE = np.dtype([("weight_total", "<f8"), ("weight_sq_total", "<f8"), ("particles", "<i4"), ("weighted", "<i4")], align=True)
 
+# fba_probe_rec
+PROBE_DTYPE = np.dtype([
+    ("run", "<i4"), ("episode", "<i4"), ("t", "<i4"), ("slot", "<i4"),
+    ("action", "<i4"), ("obs", "<i4"), ("state", "<i4"), ("reserved", "<i4"),
+    ("evidence", "<f8"), ("next_true", "<f8"), ("post_true", "<f8"),
+], align=True)
+
 
 # every symbol include/fba_hip.h declares
 EXPORTS = [
@@ -125,6 +132,7 @@ EXPORTS = [
     "fba_belief_update", "fba_belief_get", "fba_belief_get_particle", "fba_belief_set", "fba_belief_get_fully_connected", "fba_belief_get_nested", "fba_belief_get_shadow", "fba_belief_summary", "fba_predict_lens", "fba_belief_predict", "fba_belief_forecast", "fba_last_step_info",
     "fba_run_planning", "fba_run_bapomdp", "fba_run_ticks", "fba_get_returns", "fba_get_counters", "fba_get_return_sums",
     "fba_get_kernel_times", "fba_reset_kernel_times", "fba_trace_count", "fba_get_trace", "fba_get_trace_hist",
+    "fba_probe_enable", "fba_probe_count", "fba_get_probe",
     "fba_selftest_ucb", "fba_stat_add", "fba_stat_var", "fba_stat_stder",
 ]
 
@@ -235,6 +243,10 @@ def load():
     L.fba_get_trace.argtypes = [vp, vp, C.c_int32]
     if not os.environ.get("FBA_LIB") or hasattr(L, "fba_get_trace_hist"):
         L.fba_get_trace_hist.argtypes = [vp, vp, C.c_int32]
+    if not os.environ.get("FBA_LIB") or hasattr(L, "fba_probe_enable"):
+        L.fba_probe_enable.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]   # first, count, capacity
+        L.fba_probe_count.argtypes = [vp, P(C.c_int64)]
+        L.fba_get_probe.argtypes = [vp, vp, C.c_int32]
     L.fba_selftest_ucb.argtypes = [vp, vp, vp, C.c_int32, C.c_double, vp]
     L.fba_stat_add.argtypes = [P(Stat), C.c_double]
     L.fba_stat_var.restype = C.c_double

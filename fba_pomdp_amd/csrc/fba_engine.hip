@@ -70,6 +70,9 @@ struct fba_ctx {
     uint64_t k_launches[FBA_K_COUNT]  = {0};
     uint64_t base_sim = 0, base_attempts = 0, base_particles = 0, base_entries = 0;
     std::vector<fba_trace_rec> trace_host;
+    // fba_probe: on while probe.count > 0; the buffers probe points into are the context's (fba_probe_enable)
+    BeliefProbeArgs probe{};
+    int32_t* d_probe_meta = nullptr;   // [2][nodes] seg, rows
 };
 
 namespace {
@@ -1067,6 +1070,7 @@ int tick(fba_ctx* c)
     int rc;
     if ((rc = timed(c, FBA_K_SEARCH, [&] { launch_search(c->P, c->D, c->stream); }))) return rc;
     if ((rc = timed(c, FBA_K_ENV, [&] { launch_env(c->P, c->D, c->d_n_active, c->stream); }))) return rc;
+    if (c->probe.count > 0) launch_belief_probe(c->P, c->D, c->probe, c->stream);   // (the slots env_kernel has just flagged for an update; in no time bucket)
     if ((rc = timed(c, k_update_kind(c), [&] { launch_belief_update(c->P, c->D, c->stream); }))) return rc;
     if (c->D.trace_on) launch_flush(c->P, c->D, c->stream);
     launch_advance(c->P, c->D, c->d_n_active, c->stream);
@@ -2605,6 +2609,68 @@ int fba_belief_predict(fba_ctx* c, int32_t first, int32_t count, int32_t nq, con
     return check_fault(c);
 }
 
+// What the forecast's and the probe's kernels need to know of a model's layout: where node j's entries start in a particle's transition
+// table (TL entries), its rows in the observation table (RL rows), the rows of the max layout, the lanes that share one row and the
+// particles of one workgroup; FBA_ESTATE (named after `who`) where the model does not fit the kernels
+namespace {
+
+struct FactorLayout {
+    int FS = 1, FO = 1, nn = 2, TL = 0, RL = 0, longest = 1, jw = 1, wg = 1;
+    std::vector<int32_t> seg, rows;
+};
+int factor_layout(fba_ctx* c, const char* who, FactorLayout& fl)
+{
+    const Problem& P = c->P;
+    int &FS = fl.FS, &FO = fl.FO, &nn = fl.nn, &TL = fl.TL, &RL = fl.RL, &longest = fl.longest;
+    std::vector<int32_t>&seg = fl.seg, &rows = fl.rows;
+    const bool factored = P.model == FBA_MODEL_BA_FACTORED;
+    const FDesc& fd = c->fdesc;
+    const int S = P.S, A = P.A;
+    FS = factored ? fd.FS : 1; FO = factored ? fd.FO : 1; nn = FS + FO;
+    if (FS > MAXF || FO > MAXF || nn > PREDICT_MAXQN) return fail(c, FBA_ESTATE, "%s: %d + %d nodes per action (at most %d each are served)", who, FS, FO, MAXF);
+    if (P.hist == 1 && (FS != 3 || FO != 3 || fd.nvar != 2 * A))
+        return fail(c, FBA_ESTATE, "%s: gridworld records without their %d parent-set words", who, 2 * A);
+    if (P.hist == 3 && (FS > 4 || FO > 2)) return fail(c, FBA_ESTATE, "%s: collision-avoidance records of %d + %d nodes", who, FS, FO);
+    // where node j's entries start in a particle's transition table, its rows in the observation table; the rows of the max layout.  The
+    // sizes are those of action 0's nodes: every action's nodes have them (checked)
+    seg.assign((size_t)nn, 0); rows.assign((size_t)nn, 1);
+    TL = 0; RL = 0; longest = 1;
+    for (int j = 0; j < nn; ++j) {
+        int len, nrows;
+        if (!factored) { len = j == 0 ? S : P.O; nrows = j == 0 ? S * A : S; }
+        else {
+            const bool T = j < FS;
+            const FNode& n0 = fd.nodes[T ? j : A * FS + (j - FS)];
+            len = n0.out;
+            nrows = 1;
+            for (int p = 0; p < n0.nmax; ++p)
+                if (n0.var >= 0 || ((n0.fixed_mask >> p) & 1u)) nrows *= n0.psz[p];
+            for (int a = 0; a < A; ++a) {
+                const FNode& nd = fd.nodes[T ? a * FS + j : A * FS + a * FO + (j - FS)];
+                int r = 1;
+                for (int p = 0; p < nd.nmax; ++p)
+                    if (nd.var >= 0 || ((nd.fixed_mask >> p) & 1u)) r *= nd.psz[p];
+                if (nd.out != len || nd.out != (T ? fd.Ssz[j] : fd.Osz[j - FS]) || nd.nmax > MAXF) return fail(c, FBA_ESTATE, "%s: node %d of action %d does not fit the layout", who, j, a);
+                if (P.hist == 1 && nd.var >= 0 && (nd.var != 2 * a + j || j > 1)) return fail(c, FBA_ESTATE, "%s: parent-set word %d at node T(%d, %d)", who, nd.var, a, j);
+                nrows = std::max(nrows, r);
+            }
+        }
+        rows[(size_t)j] = nrows;
+        if (j < FS) { seg[(size_t)j] = TL; TL += len; }
+        else { seg[(size_t)j] = RL; RL += nrows; }
+        longest = std::max(longest, len);
+    }
+    // particles per workgroup: what fits the LDS
+    const size_t fixed = forecast_lds_bytes(TL, RL, nn, 0, P.hist != 0), per = forecast_lds_bytes(TL, RL, nn, 1, P.hist != 0) - fixed;
+    if (fixed + per > (size_t)FORECAST_LDS)
+        return fail(c, FBA_ESTATE, "%s: one particle's factor tables (%d transition entries, %d observation rows) do not fit the kernel's LDS", who, TL, RL);
+    fl.wg = (int)std::min<size_t>({(size_t)256, (size_t)P.N, ((size_t)FORECAST_LDS - fixed) / per});
+    while (fl.jw < longest && fl.jw < 64) fl.jw <<= 1;
+    return FBA_OK;
+}
+
+}  // namespace
+
 // The one-step predictive of slots [first, first + count) after action[slot] and under obs[slot], reduced on the device (fba_forecast.hip),
 // a chunk of slots at a time so that the fp64 buffers of a chunk stay below 256 MB.  Reads the context only, as fba_belief_summary does.
 int fba_belief_forecast(fba_ctx* c, int32_t first, int32_t count, const int32_t* action, const int32_t* obs, double* next_mass, double* post_mass,
@@ -2630,40 +2696,10 @@ int fba_belief_forecast(fba_ctx* c, int32_t first, int32_t count, const int32_t*
     }
     const bool factored = P.model == FBA_MODEL_BA_FACTORED;
     const FDesc& fd = c->fdesc;
-    const int S = P.S, A = P.A, FS = factored ? fd.FS : 1, FO = factored ? fd.FO : 1, nn = FS + FO;
-    if (FS > MAXF || FO > MAXF || nn > PREDICT_MAXQN) return fail(c, FBA_ESTATE, "fba_belief_forecast: %d + %d nodes per action (at most %d each are served)", FS, FO, MAXF);
-    if (P.hist == 1 && (FS != 3 || FO != 3 || fd.nvar != 2 * A))
-        return fail(c, FBA_ESTATE, "fba_belief_forecast: gridworld records without their %d parent-set words", 2 * A);
-    if (P.hist == 3 && (FS > 4 || FO > 2)) return fail(c, FBA_ESTATE, "fba_belief_forecast: collision-avoidance records of %d + %d nodes", FS, FO);
-    // where node j's entries start in a particle's transition table, its rows in the observation table; the rows of the max layout.  The
-    // sizes are those of action 0's nodes: every action's nodes have them (checked)
-    std::vector<int32_t> seg((size_t)nn, 0), rows((size_t)nn, 1);
-    int TL = 0, RL = 0, longest = 1;
-    for (int j = 0; j < nn; ++j) {
-        int len, nrows;
-        if (!factored) { len = j == 0 ? S : P.O; nrows = j == 0 ? S * A : S; }
-        else {
-            const bool T = j < FS;
-            const FNode& n0 = fd.nodes[T ? j : A * FS + (j - FS)];
-            len = n0.out;
-            nrows = 1;
-            for (int p = 0; p < n0.nmax; ++p)
-                if (n0.var >= 0 || ((n0.fixed_mask >> p) & 1u)) nrows *= n0.psz[p];
-            for (int a = 0; a < A; ++a) {
-                const FNode& nd = fd.nodes[T ? a * FS + j : A * FS + a * FO + (j - FS)];
-                int r = 1;
-                for (int p = 0; p < nd.nmax; ++p)
-                    if (nd.var >= 0 || ((nd.fixed_mask >> p) & 1u)) r *= nd.psz[p];
-                if (nd.out != len || nd.out != (T ? fd.Ssz[j] : fd.Osz[j - FS]) || nd.nmax > MAXF) return fail(c, FBA_ESTATE, "fba_belief_forecast: node %d of action %d does not fit the layout", j, a);
-                if (P.hist == 1 && nd.var >= 0 && (nd.var != 2 * a + j || j > 1)) return fail(c, FBA_ESTATE, "fba_belief_forecast: parent-set word %d at node T(%d, %d)", nd.var, a, j);
-                nrows = std::max(nrows, r);
-            }
-        }
-        rows[(size_t)j] = nrows;
-        if (j < FS) { seg[(size_t)j] = TL; TL += len; }
-        else { seg[(size_t)j] = RL; RL += nrows; }
-        longest = std::max(longest, len);
-    }
+    FactorLayout fl;
+    if (const int rc = factor_layout(c, "fba_belief_forecast", fl)) return rc;
+    const int S = P.S, FS = fl.FS, FO = fl.FO, nn = fl.nn, TL = fl.TL, RL = fl.RL, wg = fl.wg;
+    const std::vector<int32_t>&seg = fl.seg, &rows = fl.rows;
     if (P.hist) {   // a slot whose records hold more entries than they have room for has no readable filter (the update kernels report it)
         std::vector<uint32_t> cnt((size_t)count);
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2672,11 +2708,6 @@ int fba_belief_forecast(fba_ctx* c, int32_t first, int32_t count, const int32_t*
             if (hist_total(cnt[(size_t)b]) > P.hist_cap)
                 return fail(c, FBA_ESTATE, "fba_belief_forecast: slot %d: the history records hold %d entries, more than their %d", first + b, hist_total(cnt[(size_t)b]), P.hist_cap);
     }
-    // particles per workgroup: what fits the LDS
-    const size_t fixed = forecast_lds_bytes(TL, RL, nn, 0, P.hist != 0), per = forecast_lds_bytes(TL, RL, nn, 1, P.hist != 0) - fixed;
-    if (fixed + per > (size_t)FORECAST_LDS)
-        return fail(c, FBA_ESTATE, "fba_belief_forecast: one particle's factor tables (%d transition entries, %d observation rows) do not fit the kernel's LDS", TL, RL);
-    const int wg = (int)std::min<size_t>({(size_t)256, (size_t)P.N, ((size_t)FORECAST_LDS - fixed) / per});
     ScratchBuf<int32_t> d_in, d_meta;
     HIPCHK(c, d_in.alloc((size_t)count * 2));
     HIPCHK(c, d_meta.alloc((size_t)nn * 2));
@@ -2699,8 +2730,7 @@ int fba_belief_forecast(fba_ctx* c, int32_t first, int32_t count, const int32_t*
         a.next_mass = d_next.p; a.post_mass = d_post.p; a.evidence = d_ev.p; a.acc = d_acc.p;
         a.nT = FS; a.nO = FO; a.TL = TL; a.RL = RL; a.chunk = wg;
         a.ncounts = factored ? fd.ncounts : c->dense_C;
-        a.jw = 1;
-        while (a.jw < longest && a.jw < 64) a.jw <<= 1;
+        a.jw = fl.jw;
         a.ft_FS = factored ? fd.FS : 0;
         a.seg = d_meta.p; a.rows = d_meta.p + nn;
         HIPCHK(c, hipMemsetAsync(d_acc.p, 0, (size_t)n * 2 * S * 8, c->stream));
@@ -2712,6 +2742,77 @@ int fba_belief_forecast(fba_ctx* c, int32_t first, int32_t count, const int32_t*
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     return check_fault(c);
+}
+
+// fba_probe: the buffers and the layout go into c->probe, which tick() hands to launch_belief_probe (fba_probe.hip) while count > 0
+int fba_probe_enable(fba_ctx* c, int32_t first, int32_t count, int32_t capacity)
+{
+    if (!c) return FBA_EINVAL;
+    const Problem& P = c->P;
+    if (P.nested)
+        return fail(c, FBA_EINVAL, "fba_probe_enable: the nested belief's particles are (model, state filter) pairs; read them with "
+                                   "fba_belief_get and fba_belief_get_nested");
+    if (P.model == FBA_MODEL_POMDP) return fail(c, FBA_EINVAL, "fba_probe_enable: a plain POMDP belief has no counts (fba_counts_len is 0)");
+    if (first < 0 || count < 0 || (long long)first + count > P.E)
+        return fail(c, FBA_EINVAL, "fba_probe_enable: slots [%d, %lld) are not within the context's %d", first, (long long)first + count, P.E);
+    if (capacity < 0) return fail(c, FBA_EINVAL, "fba_probe_enable: a capacity of %d records", capacity);
+    FactorLayout fl;
+    if (count > 0)
+        if (const int rc = factor_layout(c, "fba_probe_enable", fl)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // (nothing in flight writes the old buffers)
+    dev_free(c, c->probe.acc);
+    dev_free(c, c->probe.recs);
+    dev_free(c, c->probe.seen);
+    dev_free(c, c->d_probe_meta);
+    c->probe = BeliefProbeArgs{};
+    if (count == 0) return FBA_OK;
+    int rc;
+    BeliefProbeArgs a{};
+    if ((rc = dev_alloc(c, &a.acc, (size_t)count * 3))) return rc;
+    if ((rc = dev_alloc(c, &a.recs, (size_t)capacity))) return rc;
+    if ((rc = dev_alloc(c, &a.seen, 1))) return rc;
+    if ((rc = dev_alloc(c, &c->d_probe_meta, (size_t)fl.nn * 2))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_probe_meta, fl.seg.data(), (size_t)fl.nn * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_probe_meta + fl.nn, fl.rows.data(), (size_t)fl.nn * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // (fl is a local)
+    const bool factored = P.model == FBA_MODEL_BA_FACTORED;
+    a.first = first; a.count = count; a.capacity = capacity;
+    a.nT = fl.FS; a.nO = fl.FO; a.TL = fl.TL; a.RL = fl.RL; a.chunk = std::min(fl.wg, PROBE_CHUNK);
+    if (const char* env = std::getenv("FBA_PROBE_CHUNK"))   // A/B: another number of particles per workgroup, up to what the LDS holds
+        a.chunk = std::max(1, std::min(fl.wg, std::atoi(env)));
+    a.ncounts = factored ? c->fdesc.ncounts : c->dense_C;
+    a.jw = fl.jw;
+    a.ft_FS = factored ? c->fdesc.FS : 0;
+    a.seg = c->d_probe_meta; a.rows = c->d_probe_meta + fl.nn;
+    c->probe = a;
+    return FBA_OK;
+}
+
+int fba_probe_count(const fba_ctx* cc, int64_t* seen)
+{
+    fba_ctx* c = const_cast<fba_ctx*>(cc);
+    if (!c) return FBA_EINVAL;
+    if (seen) *seen = 0;
+    if (c->probe.count <= 0) return 0;
+    unsigned long long n = 0;
+    if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(&n, c->probe.seen, sizeof n, hipMemcpyDeviceToHost) != hipSuccess) return FBA_EHIP;
+    if (seen) *seen = (int64_t)n;
+    return (int)std::min<unsigned long long>(n, (unsigned long long)c->probe.capacity);
+}
+
+int fba_get_probe(const fba_ctx* cc, fba_probe_rec* out, int32_t cap)
+{
+    fba_ctx* c = const_cast<fba_ctx*>(cc);
+    if (!c || !out) return FBA_EINVAL;
+    const int n = std::min(fba_probe_count(c, nullptr), cap);
+    if (n <= 0) return n;
+    HIPCHK(c, hipMemcpy(out, c->probe.recs, (size_t)n * sizeof(fba_probe_rec), hipMemcpyDeviceToHost));
+    std::sort(out, out + n, [](const fba_probe_rec& a, const fba_probe_rec& b) {   // the order of fba_get_trace
+        if (a.run != b.run) return a.run < b.run;
+        if (a.episode != b.episode) return a.episode < b.episode;
+        return a.t < b.t;
+    });
+    return n;
 }
 
 int fba_belief_set(fba_ctx* c, int32_t slot, const int32_t* state, const double* weight, const float* counts)

@@ -103,6 +103,28 @@ inline size_t forecast_lds_bytes(int TL, int RL, int nn, int chunk, bool hist)
     return ((size_t)chunk * ((size_t)TL + (size_t)RL * (hist ? 2 : 1) + 1) + (hist ? (size_t)2 * RL : 0)) * sizeof(double) + (size_t)chunk * (1 + nn) * 4;
 }
 void launch_belief_forecast(const Problem& P, const DeviceState& D, const BeliefForecastArgs& a, hipStream_t st);
+// fba_probe (fba_probe.hip): inside a tick, between the environment step and the belief update -- the evidence of the step that is about to
+// be filtered in, for the slots [first, first + count) that have an update pending, from DeviceState::action / obs / env_state.  All state
+// of the feature is here: buffers of the context's that fba_probe_enable allocates.  acc is zero between launches (the finish kernel
+// leaves it so)
+struct BeliefProbeArgs {
+    int32_t first, count;
+    double* acc;                // [count][3]: sum_i w_i sum_s' p_i(s') l_i(s'), sum_i w_i p_i(s*), sum_i w_i p_i(s*) l_i(s*)
+    fba_probe_rec* recs;        // [capacity]
+    unsigned long long* seen;   // [1] records written or counted since fba_probe_enable
+    int32_t capacity;
+    int32_t nT, nO, TL, RL;     // as BeliefForecastArgs
+    int32_t chunk;              // particles per workgroup (PROBE_CHUNK, or what the LDS holds if that is fewer): one thread per particle in the evidence phase
+    int32_t ncounts, jw, ft_FS;
+    const int32_t* seg;         // [nT + nO]
+    const int32_t* rows;        // [nT + nO]
+};
+// particles per probe workgroup, where the LDS holds more: one wave's worth for the one-thread-per-particle phases, and three to four
+// workgroups on a CU instead of the two that a full LDS leaves (same-box A/B on the shapes of scripts/bench_belief_probe.py, cost per
+// tick: gridworld 7 history records 104 -> 3.68 ms, 64 -> 2.73, 48 -> 2.91, 32 -> 4.05, 16 -> 7.79; collision avoidance fp32 173 -> 1.83,
+// 64 -> 0.75, 32 -> 0.80, 16 -> 0.95)
+constexpr int PROBE_CHUNK = 64;
+void launch_belief_probe(const Problem& P, const DeviceState& D, const BeliefProbeArgs& a, hipStream_t st);
 void launch_uniform_scan(int n, double* w_tmp, double* out, double* total, double* ctot, hipStream_t st);
 
 }  // namespace fba

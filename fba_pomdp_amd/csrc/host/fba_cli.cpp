@@ -12,6 +12,7 @@
 //
 // All --runs execute concurrently on the GPU (--slots at a time); --seed is hashed into the Philox
 // key, so results for a seed differ from the reference's mt19937 stream but not in distribution.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -21,6 +22,7 @@
 #include <fstream>
 #include <iostream>
 #include <map>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -32,7 +34,7 @@ namespace {
 struct Options {
     std::string mode;
     std::string domain, planner = "po-uct", belief = "rejection_sampling", seed, output_file = "results.txt", structure_prior,
-                                dirichlet = "expected", id, belief_option;
+                                dirichlet = "expected", id, belief_option, probe_file, probe_slots;
     int verbose = 0, runs = 1, horizon = 10, sims = 1000, max_depth = -1, particles = 100, size = 0, height = 0, width = 0,
         episodes = 1, slots = 0, device = 0, resample_amount = 0;
     double discount = .95, exploration = 100, threshold = 0;
@@ -73,7 +75,10 @@ void usage()
         "      --noise X                  prior noise (0)\n"
         "  -C, --counts-total X           prior counts (10000)\n"
         "      --structure-prior NAME     (fbapomdp) '', uniform, match-counts, match-uniform, fully-connected\n"
-        "      --slots N  --device N      runs resident at once on the GPU (auto), HIP device (0)");
+        "      --slots N  --device N      runs resident at once on the GPU (auto), HIP device (0)\n"
+        "      --probe-file FILE          (bapomdp, fbapomdp) one line per real step that a belief update follows:\n"
+        "                                 run episode t action obs state evidence next_true post_true (fba_probe)\n"
+        "      --probe-slots FIRST:COUNT  the slots whose steps are probed (all)");
 }
 
 bool parse(int argc, char** argv, Options& o, std::string& err)
@@ -126,6 +131,12 @@ bool parse(int argc, char** argv, Options& o, std::string& err)
             else if (k == "--structure-prior") o.structure_prior = v;
             else if (k == "--slots") o.slots = std::stoi(v);
             else if (k == "--device") o.device = std::stoi(v);
+            else if (k == "--probe-file") o.probe_file = v;
+            else if (k == "--probe-slots") {
+                const size_t colon = v.find(':');
+                if (colon == std::string::npos || std::stoi(v.substr(0, colon)) < 0 || std::stoi(v.substr(colon + 1)) < 1) throw std::invalid_argument(v);
+                o.probe_slots = v;
+            }
             else { err = "unrecognised option '" + k + "'"; return false; }
         } catch (std::exception const&) {
             err = "the argument ('" + v + "') for option '" + k + "' is invalid";
@@ -203,6 +214,26 @@ bool to_config(Options const& o, fba_config& c, std::string& err)
     c.slots = o.slots; c.device = o.device;
     c.trace = o.verbose >= 3 ? 2 : (o.verbose >= 2 ? 1 : 0);   // (2: with the filter's state histogram after every update)
     return true;
+}
+
+// --probe-file: the probe's records, run by run, episode by episode; a final comment line when the buffer was too small for all of them
+bool write_probe(fba_ctx* ctx, const std::string& path)
+{
+    int64_t seen = 0;
+    const int n = fba_probe_count(ctx, &seen);
+    if (n < 0) return false;
+    std::vector<fba_probe_rec> pr((size_t)std::max(n, 1));
+    const int got = n ? fba_get_probe(ctx, pr.data(), n) : 0;
+    if (got < 0) return false;
+    FILE* f = std::fopen(path.c_str(), "w");
+    if (!f) return false;
+    std::fprintf(f, "# run episode t action obs state evidence next_true post_true\n");
+    for (int i = 0; i < got; ++i) {
+        const fba_probe_rec& r = pr[(size_t)i];
+        std::fprintf(f, "%d %d %d %d %d %d %.17g %.17g %.17g\n", r.run, r.episode, r.t, r.action, r.obs, r.state, r.evidence, r.next_true, r.post_true);
+    }
+    if (seen > got) std::fprintf(f, "# %lld steps were probed, %d records were kept\n", (long long)seen, got);
+    return std::fclose(f) == 0;
 }
 
 // -v 1 / 2 / 3 in the reference's own format, "V%vlevel: %fbase\t%msg" (ArgumentParser.cpp:16-20), from the trace the engine kept:
@@ -291,6 +322,25 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "ERROR: %s\n", fba_last_error(nullptr));
         return 1;
     }
+    if (!o.probe_file.empty()) {
+        if (o.mode == "planning") {
+            std::fprintf(stderr, "ERROR: --probe-file needs a Bayes-adaptive experiment (bapomdp or fbapomdp)\n");
+            fba_destroy(ctx);
+            return 1;
+        }
+        int first = 0, count = fba_slots(ctx);
+        if (!o.probe_slots.empty()) {
+            const size_t colon = o.probe_slots.find(':');
+            first = std::stoi(o.probe_slots.substr(0, colon));
+            count = std::stoi(o.probe_slots.substr(colon + 1));
+        }
+        const long long want = (long long)cfg.runs * cfg.episodes * cfg.horizon;
+        if (fba_probe_enable(ctx, first, count, (int32_t)std::min<long long>(want, 1ll << 26)) != FBA_OK) {
+            std::fprintf(stderr, "ERROR: %s\n", fba_last_error(ctx));
+            fba_destroy(ctx);
+            return 1;
+        }
+    }
     std::fprintf(stderr, "INFO: (%s): Starting %s experiment\n", o.id.c_str(), o.mode == "planning" ? "planning" : "BAPOMDP");
     std::vector<fba_stat> stats((size_t)cfg.episodes);
     const auto t0 = std::chrono::steady_clock::now();
@@ -312,6 +362,11 @@ int main(int argc, char** argv)
         int32_t S, A, O;
         fba_domain_sizes(ctx, &S, &A, &O);
         print_trace(ctx, o, cfg, A);
+    }
+    if (!o.probe_file.empty() && !write_probe(ctx, o.probe_file)) {
+        std::fprintf(stderr, "ERROR: the probe's records could not be written to %s: %s\n", o.probe_file.c_str(), fba_last_error(ctx));
+        fba_destroy(ctx);
+        return 1;
     }
     {
         std::ofstream f(o.output_file);

@@ -46,6 +46,12 @@ class BeliefForecast:
         self.evidence = evidence     # [slots]    P(obs | belief, action)
 
 
+class ProbeRecords(np.ndarray):
+    """What Engine.probe returns: the fba_probe_rec records stored, sorted by (run, episode, t); `.seen` counts every step probed, so
+    seen > len(records) says the buffer was too small."""
+    seen = 0
+
+
 class BeliefSummary:
     """What Engine.belief_summary returns: numpy arrays with one row per slot of the range (None where not asked for)."""
 
@@ -162,6 +168,31 @@ class Engine:
         if n < 0:
             self._chk(n)
         return out[:n]
+
+    def probe_enable(self, first=0, count=None, capacity=None):
+        """Record, for every real step of slots [first, first + count) that run_bapomdp / run_ticks make from now on and that a belief
+        update follows, what the filter said about it (fba_probe_enable): the evidence P(obs | belief, action) and the predictive and
+        posterior mass at the true new state.  `capacity` records are kept (default: runs * episodes * horizon), later ones are only
+        counted; count=0 turns the probe off and frees the buffer.  Read-only on everything else."""
+        count = self.slots - first if count is None else count
+        if capacity is None:
+            capacity = max(self.cfg.runs, 1) * max(self.cfg.episodes, 1) * self.cfg.horizon
+        self._chk(self.L.fba_probe_enable(self.h, first, count, capacity))
+
+    def probe(self):
+        """The probe's records as a structured array (N.PROBE_DTYPE) sorted by (run, episode, t), with `.seen`."""
+        seen = C.c_int64()
+        n = self.L.fba_probe_count(self.h, C.byref(seen))
+        if n < 0:
+            self._chk(n)
+        out = np.zeros(max(n, 1), N.PROBE_DTYPE)
+        n = self.L.fba_get_probe(self.h, out.ctypes.data, len(out)) if n else 0
+        if n < 0:
+            self._chk(n)
+        out = out[:n]
+        out = out[np.lexsort((out["t"], out["episode"], out["run"]))].view(ProbeRecords)
+        out.seen = seen.value
+        return out
 
     def belief_get_particle(self, index, slot=0, weight=False):
         """One particle of the filter (Belief::sample() for a host planner that has drawn the index): state, weight, counts."""

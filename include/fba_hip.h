@@ -410,6 +410,42 @@ int fba_get_trace(const fba_ctx* ctx, fba_trace_rec* out, int32_t cap);
  * record without an update (terminal step).  out[cap][FBA_TRACE_HIST_BINS]. */
 #define FBA_TRACE_HIST_BINS 64
 int fba_get_trace_hist(const fba_ctx* ctx, uint32_t* out, int32_t cap);
+/* Per-step evidence recorded while experiments run: what the filter of a slot said about the step that actually happened, evaluated on
+ * the device inside the tick, between the environment step and the belief update -- the one place where the action, the observation and
+ * the true new state s* of a real step exist beside the belief that has not seen them yet.  In the notation of fba_belief_forecast, with
+ * a and o the step's action and observation:
+ *   evidence  = sum_i w_i sum_s' p_i(s') l_i(s') / W   P(o | b, a): its logarithm summed over the steps is the prequential likelihood
+ *   next_true = sum_i w_i p_i(s*) / W                  the predictive probability of the true new state
+ *   post_true = sum_i w_i p_i(s*) l_i(s*) / W          UNNORMALISED: post_true / evidence is the Rao-Blackwellised posterior of s*
+ * fba_probe_enable(first, count, capacity) turns the probe on for slots [first, first + count) with room for `capacity` records and
+ * clears the buffer; count = 0 turns it off and frees the buffer.  Records are written by fba_run_bapomdp and fba_run_ticks, one for every
+ * real step of a slot of the range that is followed by a belief update: a terminal step has no update and no record, and the per-call
+ * interface writes none (its host has the action and the observation: fba_belief_forecast).  A new fba_run_bapomdp does not clear the
+ * buffer.  fba_probe_count returns the records stored; *seen (may be NULL) counts every step probed, so seen > stored says the buffer was
+ * too small.  fba_get_probe copies up to `cap` of the stored records, ordered by (run, episode, t) as fba_get_trace orders its own; which
+ * records of one launch are kept when the buffer runs full is unspecified.  (run, episode, t) identifies a record.
+ * Same coverage as fba_belief_forecast: every record format, either Dirichlet mode, a lazily reset rejection filter, each particle under
+ * its OWN parent sets; a particle whose state is outside [0, S) has weight 0.  Where every observation node of the action has at most one
+ * parent under a particle's parent set (gridworld, collision avoidance, sysadmin) the sum over s' is evaluated in its factorised form,
+ * TL + R operations per particle instead of S * nodes; other particles (the factored tiger's listen) and tabular models enumerate S.
+ * FBA_EINVAL for the nested belief, a plain POMDP context, a slot range outside the context and a negative capacity; FBA_ESTATE where
+ * the model does not fit the kernel's LDS or node limits, under the rule fba_belief_forecast documents.  A slot whose history records
+ * have no room for the step's entry writes no record: the update that follows stops the run as it does without a probe.
+ * Read-only on everything else: with a probe on, every particle, every trace record (belief_hash included), every return and counter
+ * and every Philox position keep their bits; with no probe enabled a tick launches exactly what it launched before.
+ * The values are OUTSIDE the parity contract, as fba_belief_forecast's are: evidence is within 8 * (particles + S + F * (L + 2)) * 2^-53
+ * relative of the exact value, next_true and post_true within the bounds of next_mass and post_mass, an output is exactly 0.0 where
+ * every term is, and a slot whose weights are all 0 gives zeros. */
+typedef struct fba_probe_rec {
+    int32_t run, episode, t;      /* the step's position, as in fba_trace_rec */
+    int32_t slot;
+    int32_t action, obs, state;   /* state: the true environment state after the step */
+    int32_t reserved;
+    double  evidence, next_true, post_true;
+} fba_probe_rec;
+int fba_probe_enable(fba_ctx* ctx, int32_t first, int32_t count, int32_t capacity); /* count = 0: off, the buffer is freed */
+int fba_probe_count(const fba_ctx* ctx, int64_t* seen);  /* returns the records stored; *seen (may be NULL) counts every step probed, so seen > stored says the buffer was too small */
+int fba_get_probe(const fba_ctx* ctx, fba_probe_rec* out, int32_t cap);
 
 /* diagnostic: out[i] = u * sqrt(L[i] / n[i]) evaluated on the device, to check that the
  * engine's fp64 divide and square root round like the host's (they must, for UCB parity) */
