@@ -1766,6 +1766,7 @@ int fba_create(const fba_config* cfg, fba_ctx** out)
     D.ab_rows_hbm   = std::getenv("FBA_HIST_ROWS") && !std::strcmp(std::getenv("FBA_HIST_ROWS"), "hbm") ? 1 : 0;
     D.ab_hist_multi = std::getenv("FBA_HIST_MULTI") ? (std::atoi(std::getenv("FBA_HIST_MULTI")) != 0 ? 2 : 1) : 0;
     D.ab_no_etiger  = std::getenv("FBA_NO_ETIGER") && std::atoi(std::getenv("FBA_NO_ETIGER")) != 0 ? 1 : 0;
+    D.ab_tiger_gather = std::getenv("FBA_TIGER_GATHER") && std::atoi(std::getenv("FBA_TIGER_GATHER")) != 0 ? 1 : 0;
     D.ab_lockstep   = std::getenv("FBA_HIST_LOCKSTEP") ? (std::atoi(std::getenv("FBA_HIST_LOCKSTEP")) != 0 ? 1 : 0) : 1;   // (on; only the bucket tree has it, below)
     D.slot_base = 0;
     D.scratch_slots = D.single_rec ? std::min(E, 1024) : 0;

@@ -688,6 +688,16 @@ struct TigerRowView {   // the counts one step of action a from state s can read
         return prior[k] + (float)((k & 1) ? (w >> 16) : (w & 0xffffu));
     }
 };
+#ifdef FBA_PROFILE_REJECT
+// profiling build only (scripts/reject_regions.py): shader-clock cycles a workgroup spends in the sweep, the attempts and the pass that
+// writes the new filter (its stores waited for), and the number of workgroups
+__device__ unsigned long long g_reject_prof[4];
+#define REJECT_PROF_BEGIN long long rprev_ = clock64();
+#define REJECT_PROF_MARK(r) { __builtin_amdgcn_s_waitcnt(0); __syncthreads(); const long long now_ = clock64(); if (threadIdx.x == 0) atomicAdd(&g_reject_prof[r], (unsigned long long)(now_ - rprev_)); rprev_ = now_; }
+#else
+#define REJECT_PROF_BEGIN
+#define REJECT_PROF_MARK(r)
+#endif
 template <int BLK>
 __global__ void __launch_bounds__(BLK) reject_tiger_lds_kernel(Problem P, DeviceState D)
 {
@@ -710,6 +720,7 @@ __global__ void __launch_bounds__(BLK) reject_tiger_lds_kernel(Problem P, Device
     if (tid < 24) s_prior[tid] = D.prior_dense[tid];
     const bool lazy = slot_lazy(D, e);
     Rng g = slot_rng(P, D, e);
+    REJECT_PROF_BEGIN
     for (int i = tid; i < N; i += BLK) {
         const uint32_t* rec = reinterpret_cast<const uint32_t*>(scn) + (size_t)i * 16;
         const uint32_t w0 = rec[a], w1 = rec[3 + a], wo0 = rec[6 + 2 * a], wo1 = rec[7 + 2 * a];  // cell pairs (0,a,.) (1,a,.) | (a,0,.) (a,1,.)
@@ -720,6 +731,7 @@ __global__ void __launch_bounds__(BLK) reject_tiger_lds_kernel(Problem P, Device
         s_st[i]          = (uint8_t)st;
     }
     __syncthreads();
+    REJECT_PROF_MARK(0)
     int acc = 0, base = 0;
     while (acc < N) {
         if (base >= REJECT_MAX_ATTEMPTS) {  // see reject_kernel
@@ -760,6 +772,7 @@ __global__ void __launch_bounds__(BLK) reject_tiger_lds_kernel(Problem P, Device
         base += BLK;
         __syncthreads();
     }
+    REJECT_PROF_MARK(1)
     // the new filter: record j = source record with T(s, a, s') and O(a, s', o) bumped and the new state
     const int part = tid & 3;
     constexpr int GROUPS = BLK / 4, UNROLL = 4;  // four independent copies in flight per thread
@@ -783,6 +796,10 @@ __global__ void __launch_bounds__(BLK) reject_tiger_lds_kernel(Problem P, Device
             reinterpret_cast<float4*>(dcn)[(size_t)j * 4 + part] = v[q];
         }
     }
+    REJECT_PROF_MARK(2)
+#ifdef FBA_PROFILE_REJECT
+    if (tid == 0) atomicAdd(&g_reject_prof[3], 1ull);
+#endif
     if (tid == 0) {
         D.bufsel[e] = cur ^ 1;
         D.belief_steps[e] += (unsigned long long)s_count;
@@ -793,6 +810,181 @@ __global__ void __launch_bounds__(BLK) reject_tiger_lds_kernel(Problem P, Device
         D.cur[e].update_count = s_count;
     }
 }
+
+// ---------------------------------------------------------------------------------------------
+// reject_tiger_once_kernel: reject_tiger_lds_kernel for the filters at which LDS leaves that kernel two workgroups per CU
+// (N >= TIGER_ONCE_MIN_N), reading the filter once.  Its sweep loads every record whole -- the strided words of the sweep above bring the
+// whole 64 bytes up from memory anyway -- parks BOTH transition pairs of the action (16 bytes + the state per particle, 64 + 4 KB; the
+// attempt picks by its state) and ORs together every word a step of the action cannot read, the pad words included.  Where those are all
+// zero -- the episodic tiger: only `listen` continues an episode, so only its words ever count -- record j of the new filter is its
+// source's four parked words with the two "+1"s, the new state and zeros elsewhere: built from LDS and stored, no second read of the
+// sources, no load for the stores to wait for.  Otherwise (the continuous tiger after an `open`) the listed sources are gathered as above.
+// GATHER (reject_tiger_once_gather_kernel, FBA_TIGER_GATHER=1: same-box comparisons and tests): every slot gathers.
+// Same draws, same order, same result.  LDS: 68 KB + 16 dynamic, 8.4 KB static: two workgroups per CU.
+// ---------------------------------------------------------------------------------------------
+constexpr int TIGER_ONCE_MIN_N = 3584;   // 13 N + 8.3 KB of reject_tiger_lds_kernel no longer fit three times into a CU's 160 KB
+template <int BLK, bool GATHER>
+__device__ __forceinline__ void reject_tiger_once_body(Problem P, const DeviceState& D)
+{
+    P.model = FBA_MODEL_BA_TABLE;
+    P.S = 2; P.A = 3; P.O = 2; P.phi_len = 12; P.C = 12; P.Cs = 16;
+    if (P.domain != FBA_DOM_TIGER_CONTINUOUS) P.domain = FBA_DOM_TIGER_EPISODIC;
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_park[];  // [N][4] words, then [N] state bytes
+    __shared__ uint16_t s_acc[TIGER_LDS_MAX_N];
+    __shared__ __attribute__((aligned(8))) float s_prior[24];
+    __shared__ int32_t s_wave[BLK / 64];
+    __shared__ int32_t s_count;
+    const int e = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (!D.need_update[e]) return;
+    const int a = D.action[e], o = D.obs[e], N = P.N;
+    const int cur = D.bufsel[e];
+    const size_t sb = pbase(P, e, cur), db = pbase(P, e, cur ^ 1);
+    const float* scn = D.p_rec + sb * (size_t)P.Cs;
+    float* dcn       = D.p_rec + db * (size_t)P.Cs;
+    uint4* s_tab     = reinterpret_cast<uint4*>(s_park);   // {T(0, a, .), T(1, a, .), O(a, 0, .), O(a, 1, .)} = words a, 3 + a, 6 + 2a, 7 + 2a
+    uint8_t* s_st    = reinterpret_cast<uint8_t*>(s_park + 4 * (size_t)N);
+    if (tid < 24) s_prior[tid] = D.prior_dense[tid];
+    const bool lazy = slot_lazy(D, e);
+    Rng g = slot_rng(P, D, e);
+    REJECT_PROF_BEGIN
+    uint32_t other = 0;
+    const uint4* src4 = reinterpret_cast<const uint4*>(scn);
+    for (int i0 = tid; i0 < N; i0 += 2 * BLK) {   // two records, eight 16-byte loads in flight per thread
+        uint4 r[2][4];
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int h = 0; h < 4; ++h) r[u][h] = i0 + u * BLK < N ? src4[(size_t)(i0 + u * BLK) * 4 + h] : make_uint4(0u, 0u, 0u, 0u);
+        int ls[2] = {0, 0};
+        if (lazy) {   // a lazily reset slot's start states, drawn while the loads are in flight (every lane owns records; a draw past the filter's end is dropped)
+            ls[0] = lazy_state(P, g, i0);
+            ls[1] = lazy_state(P, g, i0 + BLK);
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int i = i0 + u * BLK;
+            if (i >= N) continue;
+            const uint4 q0 = r[u][0], q1 = r[u][1], q2 = r[u][2], q3 = r[u][3];
+            uint4 t;   // (selects on the slot's action, not an indexed array: that would be scratch)
+            t.x = a == 0 ? q0.x : (a == 1 ? q0.y : q0.z);
+            t.y = a == 0 ? q0.w : (a == 1 ? q1.x : q1.y);
+            t.z = a == 0 ? q1.z : (a == 1 ? q2.x : q2.z);
+            t.w = a == 0 ? q1.w : (a == 1 ? q2.y : q2.w);
+            // the words outside the four parked ones and the state (word 12)
+            const uint32_t o0 = (a == 0 ? 0u : q0.x) | (a == 1 ? 0u : q0.y) | (a == 2 ? 0u : q0.z) | (a == 0 ? 0u : q0.w);
+            const uint32_t o1 = (a == 1 ? 0u : q1.x) | (a == 2 ? 0u : q1.y) | (a == 0 ? 0u : q1.z) | (a == 0 ? 0u : q1.w);
+            const uint32_t o2 = (a == 1 ? 0u : q2.x) | (a == 1 ? 0u : q2.y) | (a == 2 ? 0u : q2.z) | (a == 2 ? 0u : q2.w);
+            other |= o0 | o1 | o2 | q3.y | q3.z | q3.w;
+            s_tab[i] = t;
+            s_st[i]  = (uint8_t)(lazy ? (uint32_t)ls[u] : q3.x);
+        }
+    }
+    const bool gather = __syncthreads_or(other != 0u) != 0 || GATHER;
+    REJECT_PROF_MARK(0)
+    int acc = 0, base = 0;
+    while (acc < N) {
+        if (base >= REJECT_MAX_ATTEMPTS) {  // see reject_kernel
+            if (tid == 0) {
+                atomicCAS(D.fault, 0, 1 + e);
+                D.need_update[e] = 0;
+                D.active[e]      = 0;
+            }
+            return;
+        }
+        const int k = base + tid;
+        g.stream(FBA_PHASE_REJECT, (uint32_t)k);
+        const int src = P.point ? 0 : g.uniform_int(N);         // FlatFilter::sample
+        const int s0  = s_st[src];
+        int s = s0, so;
+        double r;
+        {
+            const uint4 t = s_tab[src];
+            const uint32_t wt = s0 ? t.y : t.x, wo0 = t.z, wo1 = t.w;
+            tiger_step_packed(P, g, [&](int w) { return w < 6 ? wt : (w & 1 ? wo1 : wo0); }, s_prior, s, a, so, r, NoInc{});
+        }
+        const bool ok = (so == o);
+        const unsigned long long ballot = __ballot(ok);
+        const int prefix = __popcll(ballot & ((1ull << lane) - 1ull));
+        if (lane == 0) s_wave[wave] = __popcll(ballot);
+        __syncthreads();
+        int woff = 0, chunk = 0;
+        for (int w = 0; w < BLK / 64; ++w) {
+            if (w < wave) woff += s_wave[w];
+            chunk += s_wave[w];
+        }
+        const int j = acc + woff + prefix;  // position among all accepted attempts
+        if (ok && j < N) {
+            s_acc[j] = (uint16_t)(src | (s0 << 12) | (s << 13));
+            if (j == N - 1) s_count = k + 1;
+        }
+        acc += min(chunk, N - acc);
+        base += BLK;
+        __syncthreads();
+    }
+    REJECT_PROF_MARK(1)
+    // the new filter: record j = source record with T(s, a, s') and O(a, s', o) bumped and the new state
+    const int part = tid & 3;
+    constexpr int GROUPS = BLK / 4;
+    if (!gather) {
+        // where this thread's quarter of a record takes its four words from: place 0..3 of the parked words, 4 = the state, -1 = zero
+        const auto place_of = [&](int w) { return w == a ? 0 : (w == 3 + a ? 1 : (w == 6 + 2 * a ? 2 : (w == 7 + 2 * a ? 3 : (w == 12 ? 4 : -1)))); };
+        const int d0 = place_of(4 * part), d1 = place_of(4 * part + 1), d2 = place_of(4 * part + 2), d3 = place_of(4 * part + 3);
+        const auto word_of = [&](int d, const uint4& t, int ns) {
+            return d == 0 ? t.x : (d == 1 ? t.y : (d == 2 ? t.z : (d == 3 ? t.w : (d == 4 ? (uint32_t)ns : 0u))));
+        };
+        const uint32_t add_o = o ? 0x10000u : 1u;
+        for (int j = tid >> 2; j < N; j += GROUPS) {
+            const uint32_t en = s_acc[j];
+            const int s0 = (en >> 12) & 1, ns = (en >> 13) & 1;
+            uint4 t = s_tab[en & 4095];
+            const uint32_t add_t = ns ? 0x10000u : 1u;   // cell 6 s + 2 a + s' is half s' of word 3 s + a; cell 12 + 4 a + 2 s' + o is half o of word 6 + 2 a + s'
+            t.x += s0 ? 0u : add_t;
+            t.y += s0 ? add_t : 0u;
+            t.z += ns ? 0u : add_o;
+            t.w += ns ? add_o : 0u;
+            reinterpret_cast<uint4*>(dcn)[(size_t)j * 4 + part] = make_uint4(word_of(d0, t, ns), word_of(d1, t, ns), word_of(d2, t, ns), word_of(d3, t, ns));
+        }
+    } else {
+        constexpr int UNROLL = 4;  // four independent copies in flight per thread
+        for (int j0 = tid >> 2; j0 < N; j0 += GROUPS * UNROLL) {
+            uint32_t en[UNROLL];
+            float4 v[UNROLL];
+#pragma unroll
+            for (int q = 0; q < UNROLL; ++q) {
+                const int j = j0 + q * GROUPS;
+                en[q] = j < N ? s_acc[j] : 0u;
+                if (j < N) v[q] = reinterpret_cast<const float4*>(scn)[(size_t)(en[q] & 4095) * 4 + part];
+            }
+#pragma unroll
+            for (int q = 0; q < UNROLL; ++q) {
+                const int j = j0 + q * GROUPS;
+                if (j >= N) continue;
+                const int s0 = (en[q] >> 12) & 1, ns = (en[q] >> 13) & 1;
+                bump_cell(v[q], s0 * 6 + a * 2 + ns, part * 4, true);
+                bump_cell(v[q], 12 + a * 4 + ns * 2 + o, part * 4, true);
+                if (part == 3) v[q].x = __int_as_float(ns);  // the state word (12)
+                reinterpret_cast<float4*>(dcn)[(size_t)j * 4 + part] = v[q];
+            }
+        }
+    }
+    REJECT_PROF_MARK(2)
+#ifdef FBA_PROFILE_REJECT
+    if (tid == 0) atomicAdd(&g_reject_prof[3], 1ull);
+#endif
+    if (tid == 0) {
+        D.bufsel[e] = cur ^ 1;
+        D.belief_steps[e] += (unsigned long long)s_count;
+        D.upd_attempts[e] += (unsigned long long)s_count;
+        D.upd_particles[e] += (unsigned long long)N;
+        D.need_update[e]      = 0;
+        D.lazy_reset[e]       = 0;  // every record of the new buffer carries its real state
+        D.cur[e].update_count = s_count;
+    }
+}
+template <int BLK>
+__global__ void __launch_bounds__(BLK) reject_tiger_once_kernel(Problem P, DeviceState D) { reject_tiger_once_body<BLK, false>(P, D); }
+template <int BLK>
+__global__ void __launch_bounds__(BLK) reject_tiger_once_gather_kernel(Problem P, DeviceState D) { reject_tiger_once_body<BLK, true>(P, D); }
 
 // ---------------------------------------------------------------------------------------------
 // reinvigorate_kernel: ReinvigoratingRejectionSampling::reinvigorateParticles
@@ -2773,6 +2965,10 @@ void launch_belief_update(const Problem& P, const DeviceState& D, hipStream_t st
             else if (ft == 3) hipLaunchKernelGGL((reject_kernel<false, 0, 3>), dim3(P.E), dim3(REJECT_BLOCK), 0, st, P, D, fc);
             else if (ft == 4) hipLaunchKernelGGL((reject_kernel<false, 0, 4>), dim3(P.E), dim3(REJECT_BLOCK), 0, st, P, D, fc);
             else if (P.dirichlet_regular) hipLaunchKernelGGL((reject_kernel<true, 0>), dim3(P.E), dim3(REJECT_BLOCK), 0, st, P, D, fc);
+            else if (tiger_table && P.packed && P.N <= TIGER_LDS_MAX_N && P.N >= TIGER_ONCE_MIN_N && D.ab_tiger_gather)
+                hipLaunchKernelGGL((reject_tiger_once_gather_kernel<512>), dim3(P.E), dim3(512), (size_t)P.N * 17 + 16, st, P, D);
+            else if (tiger_table && P.packed && P.N <= TIGER_LDS_MAX_N && P.N >= TIGER_ONCE_MIN_N)
+                hipLaunchKernelGGL((reject_tiger_once_kernel<512>), dim3(P.E), dim3(512), (size_t)P.N * 17 + 16, st, P, D);
             else if (tiger_table && P.packed && P.N <= TIGER_LDS_MAX_N)
                 hipLaunchKernelGGL((reject_tiger_lds_kernel<512>), dim3(P.E), dim3(512), (size_t)P.N * 13 + 16, st, P, D);
             else if (tiger_table && P.packed)  // (chunks of 512 are 4 % faster than 256 / 1024 on packed records)
@@ -2811,6 +3007,17 @@ void launch_belief_update(const Problem& P, const DeviceState& D, hipStream_t st
     }
     launch_importance_multi(P, D, P.E, st);
 }
+#ifdef FBA_PROFILE_REJECT
+extern "C" int fba_debug_reject_profile(unsigned long long* out, int reset)
+{
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_reject_prof), sizeof(unsigned long long) * 4) != hipSuccess) return -1;
+    if (reset) {
+        const unsigned long long z[4] = {0, 0, 0, 0};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(g_reject_prof), z, sizeof z) != hipSuccess) return -1;
+    }
+    return 0;
+}
+#endif
 void launch_init(const Problem& P, const DeviceState& D, hipStream_t st)
 {
     hipLaunchKernelGGL(init_kernel, dim3(ceil_div(P.N, PARTICLE_TILE), P.E), dim3(256), 0, st, P, D, 0);
