@@ -2612,17 +2612,19 @@ int fba_belief_predict(fba_ctx* c, int32_t first, int32_t count, int32_t nq, con
 
 // What the forecast's and the probe's kernels need to know of a model's layout: where node j's entries start in a particle's transition
 // table (TL entries), its rows in the observation table (RL rows), the rows of the max layout, the lanes that share one row and the
-// particles of one workgroup; FBA_ESTATE (named after `who`) where the model does not fit the kernels
+// particles of one workgroup (what the LDS holds); FBA_ESTATE (named after `who`) where the model does not fit the kernels
 namespace {
 
 struct FactorLayout {
-    int FS = 1, FO = 1, nn = 2, TL = 0, RL = 0, longest = 1, jw = 1, wg = 1;
-    std::vector<int32_t> seg, rows;
+    BeliefFactorLayout lay{};         // for the kernels: everything but seg and rows, which point to the device copy the caller makes ...
+    std::vector<int32_t> seg, rows;   // ... of these ([nn] each)
+    int nn = 2;
 };
 int factor_layout(fba_ctx* c, const char* who, FactorLayout& fl)
 {
     const Problem& P = c->P;
-    int &FS = fl.FS, &FO = fl.FO, &nn = fl.nn, &TL = fl.TL, &RL = fl.RL, &longest = fl.longest;
+    int FS, FO, TL, RL, longest;
+    int& nn = fl.nn;
     std::vector<int32_t>&seg = fl.seg, &rows = fl.rows;
     const bool factored = P.model == FBA_MODEL_BA_FACTORED;
     const FDesc& fd = c->fdesc;
@@ -2665,8 +2667,13 @@ int factor_layout(fba_ctx* c, const char* who, FactorLayout& fl)
     const size_t fixed = forecast_lds_bytes(TL, RL, nn, 0, P.hist != 0), per = forecast_lds_bytes(TL, RL, nn, 1, P.hist != 0) - fixed;
     if (fixed + per > (size_t)FORECAST_LDS)
         return fail(c, FBA_ESTATE, "%s: one particle's factor tables (%d transition entries, %d observation rows) do not fit the kernel's LDS", who, TL, RL);
-    fl.wg = (int)std::min<size_t>({(size_t)256, (size_t)P.N, ((size_t)FORECAST_LDS - fixed) / per});
-    while (fl.jw < longest && fl.jw < 64) fl.jw <<= 1;
+    BeliefFactorLayout& lay = fl.lay;
+    lay.nT = FS; lay.nO = FO; lay.TL = TL; lay.RL = RL;
+    lay.chunk = (int)std::min<size_t>({(size_t)256, (size_t)P.N, ((size_t)FORECAST_LDS - fixed) / per});
+    lay.ncounts = factored ? fd.ncounts : c->dense_C;
+    lay.jw = 1;
+    while (lay.jw < longest && lay.jw < 64) lay.jw <<= 1;
+    lay.ft_FS = factored ? fd.FS : 0;
     return FBA_OK;
 }
 
@@ -2695,12 +2702,9 @@ int fba_belief_forecast(fba_ctx* c, int32_t first, int32_t count, const int32_t*
         if (obs && (obs[b] < 0 || obs[b] >= P.O))
             return fail(c, FBA_EINVAL, "fba_belief_forecast: slot %d: observation %d is outside the model's %d observations", first + b, obs[b], P.O);
     }
-    const bool factored = P.model == FBA_MODEL_BA_FACTORED;
-    const FDesc& fd = c->fdesc;
     FactorLayout fl;
     if (const int rc = factor_layout(c, "fba_belief_forecast", fl)) return rc;
-    const int S = P.S, FS = fl.FS, FO = fl.FO, nn = fl.nn, TL = fl.TL, RL = fl.RL, wg = fl.wg;
-    const std::vector<int32_t>&seg = fl.seg, &rows = fl.rows;
+    const int S = P.S, nn = fl.nn;
     if (P.hist) {   // a slot whose records hold more entries than they have room for has no readable filter (the update kernels report it)
         std::vector<uint32_t> cnt((size_t)count);
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2714,8 +2718,9 @@ int fba_belief_forecast(fba_ctx* c, int32_t first, int32_t count, const int32_t*
     HIPCHK(c, d_meta.alloc((size_t)nn * 2));
     HIPCHK(c, hipMemcpyAsync(d_in.p, action, (size_t)count * 4, hipMemcpyHostToDevice, c->stream));
     if (obs) HIPCHK(c, hipMemcpyAsync(d_in.p + count, obs, (size_t)count * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_meta.p, seg.data(), (size_t)nn * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_meta.p + nn, rows.data(), (size_t)nn * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_meta.p, fl.seg.data(), (size_t)nn * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_meta.p + nn, fl.rows.data(), (size_t)nn * 4, hipMemcpyHostToDevice, c->stream));
+    fl.lay.seg = d_meta.p; fl.lay.rows = d_meta.p + nn;
     const size_t per_slot = (size_t)S * 4 + 1;
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>({(size_t)count, (size_t)32768, ((size_t)256 << 20) / (per_slot * 8)}));
     ScratchBuf<double> d_acc, d_next, d_post, d_ev;
@@ -2729,11 +2734,7 @@ int fba_belief_forecast(fba_ctx* c, int32_t first, int32_t count, const int32_t*
         a.first = first + done; a.count = n;
         a.action = d_in.p + done; a.obs = obs ? d_in.p + count + done : nullptr;
         a.next_mass = d_next.p; a.post_mass = d_post.p; a.evidence = d_ev.p; a.acc = d_acc.p;
-        a.nT = FS; a.nO = FO; a.TL = TL; a.RL = RL; a.chunk = wg;
-        a.ncounts = factored ? fd.ncounts : c->dense_C;
-        a.jw = fl.jw;
-        a.ft_FS = factored ? fd.FS : 0;
-        a.seg = d_meta.p; a.rows = d_meta.p + nn;
+        a.lay = fl.lay;
         HIPCHK(c, hipMemsetAsync(d_acc.p, 0, (size_t)n * 2 * S * 8, c->stream));
         launch_belief_forecast(P, c->D, a, c->stream);
         HIPCHK(c, hipGetLastError());
@@ -2776,15 +2777,12 @@ int fba_probe_enable(fba_ctx* c, int32_t first, int32_t count, int32_t capacity)
     HIPCHK(c, hipMemcpyAsync(c->d_probe_meta, fl.seg.data(), (size_t)fl.nn * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->d_probe_meta + fl.nn, fl.rows.data(), (size_t)fl.nn * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));   // (fl is a local)
-    const bool factored = P.model == FBA_MODEL_BA_FACTORED;
     a.first = first; a.count = count; a.capacity = capacity;
-    a.nT = fl.FS; a.nO = fl.FO; a.TL = fl.TL; a.RL = fl.RL; a.chunk = std::min(fl.wg, PROBE_CHUNK);
+    a.lay = fl.lay;
+    a.lay.chunk = std::min(fl.lay.chunk, PROBE_CHUNK);
     if (const char* env = std::getenv("FBA_PROBE_CHUNK"))   // A/B: another number of particles per workgroup, up to what the LDS holds
-        a.chunk = std::max(1, std::min(fl.wg, std::atoi(env)));
-    a.ncounts = factored ? c->fdesc.ncounts : c->dense_C;
-    a.jw = fl.jw;
-    a.ft_FS = factored ? c->fdesc.FS : 0;
-    a.seg = c->d_probe_meta; a.rows = c->d_probe_meta + fl.nn;
+        a.lay.chunk = std::max(1, std::min(fl.lay.chunk, std::atoi(env)));
+    a.lay.seg = c->d_probe_meta; a.lay.rows = c->d_probe_meta + fl.nn;
     c->probe = a;
     return FBA_OK;
 }

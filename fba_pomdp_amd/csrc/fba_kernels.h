@@ -81,13 +81,9 @@ struct BeliefPredictArgs {
     double* hacc;               // history records: [count][nq][TL + OL + 2 * PREDICT_SLOTS + 1] raised terms, sum w / R per (slot, form), joint sum
 };
 void launch_belief_predict(const Problem& P, const DeviceState& D, const BeliefPredictArgs& a, hipStream_t st);
-// fba_belief_forecast (fba_forecast.hip): the one-step predictive of slots [first, first + count) after action[slot] (and under obs[slot])
-// into device buffers of the caller's; a null output = not wanted, obs may be null where only next_mass is.  The caller zeroes acc
-struct BeliefForecastArgs {
-    int32_t first, count;
-    const int32_t *action, *obs;                 // [count]
-    double *next_mass, *post_mass, *evidence;    // [count][S], [count][S], [count]
-    double* acc;                                 // [count][2][S]: sum_i w_i p_i(s'), sum_i w_i p_i(s') l_i(s')
+// what the kernels of fba_belief_forecast and fba_probe are told of a model's layout (factor_layout in fba_engine.hip fills it,
+// belief_factors in fba_belief_factors.h reads it)
+struct BeliefFactorLayout {
     int32_t nT, nO;             // transition / observation nodes of an action (1 / 1 for a tabular model)
     int32_t TL, RL;             // entries of a particle's transition rows; rows of its observation nodes in the max layout
     int32_t chunk;              // particles per workgroup (at most 256)
@@ -95,9 +91,19 @@ struct BeliefForecastArgs {
     const int32_t* seg;         // [nT + nO] where node j's entries start among the TL (j < nT), its rows among the RL
     const int32_t* rows;        // [nT + nO] rows of node j in the max layout
 };
+// fba_belief_forecast (fba_forecast.hip): the one-step predictive of slots [first, first + count) after action[slot] (and under obs[slot])
+// into device buffers of the caller's; a null output = not wanted, obs may be null where only next_mass is.  The caller zeroes acc
+struct BeliefForecastArgs {
+    int32_t first, count;
+    const int32_t *action, *obs;                 // [count]
+    double *next_mass, *post_mass, *evidence;    // [count][S], [count][S], [count]
+    double* acc;                                 // [count][2][S]: sum_i w_i p_i(s'), sum_i w_i p_i(s') l_i(s')
+    BeliefFactorLayout lay;
+};
 constexpr int FORECAST_LDS = 63 * 1024;   // dynamic LDS a forecast workgroup may use (the node descriptions take the rest of 64 KB)
-// dynamic LDS of one forecast_chunk_kernel workgroup: per particle the fp64 factor tables (history records: the observation rows' sums
-// and counts apart), weight, state and a parent-set word per node; history records: the prior's observation row sums and counts once
+// dynamic LDS of one forecast_chunk_kernel or probe_chunk_kernel workgroup (belief_factors carves it): per particle the fp64 factor tables
+// (history records: the observation rows' sums and counts apart), weight, state and a parent-set word per node; history records: the
+// prior's observation row sums and counts once
 inline size_t forecast_lds_bytes(int TL, int RL, int nn, int chunk, bool hist)
 {
     return ((size_t)chunk * ((size_t)TL + (size_t)RL * (hist ? 2 : 1) + 1) + (hist ? (size_t)2 * RL : 0)) * sizeof(double) + (size_t)chunk * (1 + nn) * 4;
@@ -113,11 +119,7 @@ struct BeliefProbeArgs {
     fba_probe_rec* recs;        // [capacity]
     unsigned long long* seen;   // [1] records written or counted since fba_probe_enable
     int32_t capacity;
-    int32_t nT, nO, TL, RL;     // as BeliefForecastArgs
-    int32_t chunk;              // particles per workgroup (PROBE_CHUNK, or what the LDS holds if that is fewer): one thread per particle in the evidence phase
-    int32_t ncounts, jw, ft_FS;
-    const int32_t* seg;         // [nT + nO]
-    const int32_t* rows;        // [nT + nO]
+    BeliefFactorLayout lay;     // chunk: PROBE_CHUNK, or what the LDS holds if that is fewer: one thread per particle in the evidence phase
 };
 // particles per probe workgroup, where the LDS holds more: one wave's worth for the one-thread-per-particle phases, and three to four
 // workgroups on a CU instead of the two that a full LDS leaves (same-box A/B on the shapes of scripts/bench_belief_probe.py, cost per

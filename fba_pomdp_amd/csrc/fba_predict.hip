@@ -10,15 +10,10 @@
 //   predict_hist_finish_kernel  history records: prior row * that sum + the raised terms, / weight total   one thread per output entry
 //
 // A translation unit of its own, outside the parity path: the order of the fp64 additions is the engine's.  Read-only on the context.
-#include "fba_kernels_common.h"
+#include "fba_belief_factors.h"   // lanes_sum, raised, slot_weight_total
 
 namespace fba {
 
-__device__ __forceinline__ double group_sum(double v, int width)   // over aligned groups of `width` lanes (a power of two)
-{
-    for (int off = 1; off < width; off <<= 1) v += __shfl_xor(v, off);
-    return v;
-}
 __device__ __forceinline__ double groups_sum(double v, int width)   // over the groups of a wave, lane by lane
 {
     for (int off = width; off < 64; off <<= 1) v += __shfl_xor(v, off);
@@ -29,16 +24,8 @@ __global__ void __launch_bounds__(256) predict_total_kernel(Problem P, DeviceSta
 {
     __shared__ double s_part[256];
     const int b = blockIdx.x, e = a.first + b, tid = threadIdx.x;
-    const SlotRecs r = slot_recs(P, D, e);
-    double lw = 0.0;
-    for (int i = tid; i < P.N; i += 256) lw += particle_weight(P, D, r, i);
-    s_part[tid] = lw;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if (tid < st) s_part[tid] += s_part[tid + st];
-        __syncthreads();
-    }
-    if (tid == 0) a.wtot[b] = s_part[0];
+    const double W = slot_weight_total(P, D, slot_recs(P, D, e), s_part);
+    if (tid == 0) a.wtot[b] = W;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -121,7 +108,7 @@ __global__ void __launch_bounds__(64 * PREDICT_WAVES) predict_rows_kernel(Proble
                 if (s_nd[wave][n].var >= 0) row = predict_row<FMT>(P, D, a, s_nd[wave][n], s_fv[wave][n], rec);
                 double sum = 0.0;
                 for (int k = kl; k < len; k += Wd) sum += (double)record_count<FMT>(P, D, rec, row + k);
-                sum = group_sum(sum, Wd);
+                sum = lanes_sum(sum, Wd);
                 const double cv = (double)record_count<FMT>(P, D, rec, row + s_val[wave][n]);
                 prod *= sum > 0.0 ? cv / sum : 0.0;
             }
@@ -152,7 +139,7 @@ __global__ void __launch_bounds__(64 * PREDICT_WAVES) predict_rows_kernel(Proble
             const int row    = n.nd.var >= 0 ? predict_row<FMT>(P, D, a, n.nd, n.fv, rec) : row0;
             double sum = 0.0;
             for (int k = kl; k < len; k += Wd) sum += (double)record_count<FMT>(P, D, rec, row + k);
-            sum = group_sum(sum, Wd);
+            sum = lanes_sum(sum, Wd);
             const double w = valid ? particle_weight(P, D, r, i) : 0.0;
 #pragma unroll
             for (int t = 0; t < PREDICT_TILES; ++t) {
@@ -212,9 +199,7 @@ __global__ void __launch_bounds__(256) predict_hist_kernel(Problem P, DeviceStat
             if (HIST != 3) return (double)mult;
             // the prior's count after `mult` single additions of 1.0f, which need not be prior + mult
             const float p0 = qp[form[k] * TLOL + seg[k] + rel];
-            float v = p0;
-            for (int m = 0; m < mult; ++m) v += 1.0f;
-            return (double)v - (double)p0;
+            return (double)raised(p0, mult) - (double)p0;
         };
         if (HIST == 3) {
             hist_distinct_cells<HIST, NC>(dims, rec, mask, act, j0, na, rb, len, [&](int k, int rel, int mult) {
@@ -258,15 +243,15 @@ __global__ void __launch_bounds__(256) predict_hist_kernel(Problem P, DeviceStat
                 const double p0 = (double)qp[form[k] * TLOL + n.seg + n.val];
                 prod *= R[k] > 0.0 ? (p0 + hit[k]) / R[k] : 0.0;
                 const double inv = R[k] > 0.0 ? w / R[k] : 0.0;
-                const double v0  = group_sum(form[k] ? 0.0 : inv, 64);
+                const double v0  = lanes_sum(form[k] ? 0.0 : inv, 64);
                 if (lane == 0 && v0 != 0.0) unsafeAtomicAdd(&s_acc[TLOL + 2 * k], v0);
                 if (n.var >= 0) {
-                    const double v1 = group_sum(form[k] ? inv : 0.0, 64);
+                    const double v1 = lanes_sum(form[k] ? inv : 0.0, 64);
                     if (lane == 0 && v1 != 0.0) unsafeAtomicAdd(&s_acc[TLOL + 2 * k + 1], v1);
                 }
             }
         }
-        const double js = group_sum(w * prod, 64);
+        const double js = lanes_sum(w * prod, 64);
         if (lane == 0 && js != 0.0) unsafeAtomicAdd(&s_acc[TLOL + 2 * PREDICT_SLOTS], js);
         __syncthreads();
         for (int k = tid; k < hw; k += 256) {

@@ -9,7 +9,10 @@ import fba_pomdp_amd as fba
 from fba_pomdp_amd import _native as N
 
 ARGS = "ENS_7ProblemENS_11DeviceStateENS_18BeliefForecastArgsE"
-# (scratch bytes, VGPRs, spilled VGPRs)
+# (scratch bytes, VGPRs, spilled VGPRs).  Three counts moved when the factor phase became belief_factors (fba_belief_factors.h), a function
+# the kernel inlines, where it had been statements of the kernel's own body (91, 87 and 104 then; the function's statements put back into
+# a kernel's body give the old counts, so it is the function boundary that moves them).  None of them changes the waves a SIMD can
+# hold, min(8, 512 // (ceil(count / 8) * 8)): 5 for any count from 86 to 96, 4 for 103 and 104.
 PINNED = {
     "_ZN3fba22forecast_finish_kernel" + ARGS: (0, 24, 0),
     "_ZN3fba21forecast_chunk_kernelILi0EEEv" + ARGS[1:]: (0, 40, 0),    # fp32 counts
@@ -17,9 +20,9 @@ PINNED = {
     "_ZN3fba21forecast_chunk_kernelILi2EEEv" + ARGS[1:]: (0, 41, 0),    # packed factored tiger, 2 to 4 state features
     "_ZN3fba21forecast_chunk_kernelILi3EEEv" + ARGS[1:]: (0, 41, 0),
     "_ZN3fba21forecast_chunk_kernelILi4EEEv" + ARGS[1:]: (0, 41, 0),
-    "_ZN3fba21forecast_chunk_kernelILi5EEEv" + ARGS[1:]: (0, 91, 0),    # gridworld FBA-POMDP records
-    "_ZN3fba21forecast_chunk_kernelILi6EEEv" + ARGS[1:]: (0, 87, 0),    # tabular gridworld records
-    "_ZN3fba21forecast_chunk_kernelILi7EEEv" + ARGS[1:]: (0, 104, 0),   # collision-avoidance records
+    "_ZN3fba21forecast_chunk_kernelILi5EEEv" + ARGS[1:]: (0, 95, 0),    # gridworld FBA-POMDP records (91 before: 5 waves as before)
+    "_ZN3fba21forecast_chunk_kernelILi6EEEv" + ARGS[1:]: (0, 91, 0),    # tabular gridworld records (87 before: 5 waves as before)
+    "_ZN3fba21forecast_chunk_kernelILi7EEEv" + ARGS[1:]: (0, 103, 0),   # collision-avoidance records (104 before: 4 waves as before)
 }
 
 
