@@ -12,8 +12,8 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB_PATH = os.environ.get("FBA_LIB") or os.path.join(HERE, "libfba_hip.so")   # (FBA_LIB: an instrumented build of the same sources, scripts/search_regions.py)
-SOURCES = [os.path.join(HERE, "csrc", f) for f in ("fba_search.hip", "fba_kernels.hip", "fba_summary.hip", "fba_predict.hip", "fba_forecast.hip", "fba_probe.hip", "fba_engine.hip")]
-HEADERS = [os.path.join(HERE, "csrc", f) for f in ("fba_device.h", "fba_state.h", "fba_kernels.h", "fba_kernels_common.h", "fba_belief_factors.h", "fba_search_hist2.inc")] + [
+SOURCES = [os.path.join(HERE, "csrc", f) for f in ("fba_search.hip", "fba_kernels.hip", "fba_summary.hip", "fba_predict.hip", "fba_forecast.hip", "fba_probe.hip", "fba_snapshot.hip", "fba_engine.hip")]
+HEADERS = [os.path.join(HERE, "csrc", f) for f in ("fba_device.h", "fba_state.h", "fba_kernels.h", "fba_kernels_common.h", "fba_belief_factors.h", "fba_snapshot_format.h", "fba_search_hist2.inc")] + [
     os.path.join(ROOT, "include", "fba_hip.h")]
 OBJ_DIR = os.path.join(HERE, "build")   # per-source objects (git-ignored): a change to one translation unit recompiles that one
 
@@ -123,6 +123,22 @@ PROBE_DTYPE = np.dtype([
     ("evidence", "<f8"), ("next_true", "<f8"), ("post_true", "<f8"),
 ], align=True)
 
+# fba_snapshot_head: the 64 bytes a belief snapshot block starts with
+SNAPSHOT_MAGIC, SNAPSHOT_VERSION, SNAPSHOT_CHECK_MUL = 0x53414246, 1, 0x9E3779B97F4A7C15
+SNAPSHOT_HEAD_DTYPE = np.dtype([
+    ("magic", "<u4"), ("version", "<u2"), ("record_format", "u1"), ("weighted", "u1"), ("model", "u1"), ("domain", "u1"), ("actions", "<u2"),
+    ("size", "<i2"), ("width", "<i2"), ("height", "<i2"), ("updates", "<u2"),
+    ("particles", "<i4"), ("particle_bytes", "<i4"), ("counts_len", "<i4"), ("states", "<i4"), ("observations", "<i4"),
+    ("hist_cnt", "<u4"), ("stride", "<u4"), ("prior_hash", "<u8"), ("checksum", "<u8"),
+], align=True)
+
+
+def snapshot_checksum(payload):
+    """The checksum of a snapshot block's payload (everything behind the 64-byte header), by the formula of include/fba_hip.h."""
+    w = np.ascontiguousarray(payload).view(np.uint8).reshape(-1).view("<u4").astype(np.uint64)
+    with np.errstate(over="ignore"):
+        return int((w * ((np.arange(len(w), dtype=np.uint64) + np.uint64(1)) * np.uint64(SNAPSHOT_CHECK_MUL))).sum(dtype=np.uint64))
+
 
 # every symbol include/fba_hip.h declares
 EXPORTS = [
@@ -133,6 +149,7 @@ EXPORTS = [
     "fba_run_planning", "fba_run_bapomdp", "fba_run_ticks", "fba_get_returns", "fba_get_counters", "fba_get_return_sums",
     "fba_get_kernel_times", "fba_reset_kernel_times", "fba_trace_count", "fba_get_trace", "fba_get_trace_hist",
     "fba_probe_enable", "fba_probe_count", "fba_get_probe",
+    "fba_belief_snapshot_bytes", "fba_belief_export", "fba_belief_import", "fba_belief_replicate",
     "fba_selftest_ucb", "fba_stat_add", "fba_stat_var", "fba_stat_stder",
 ]
 
@@ -247,6 +264,11 @@ def load():
         L.fba_probe_enable.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]   # first, count, capacity
         L.fba_probe_count.argtypes = [vp, P(C.c_int64)]
         L.fba_get_probe.argtypes = [vp, vp, C.c_int32]
+    if not os.environ.get("FBA_LIB") or hasattr(L, "fba_belief_export"):
+        L.fba_belief_snapshot_bytes.argtypes = [vp, P(C.c_int64)]
+        L.fba_belief_export.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int64]    # first, count, buf, cap
+        L.fba_belief_import.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int64]    # first, count, buf, bytes
+        L.fba_belief_replicate.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]     # src, first, count
     L.fba_selftest_ucb.argtypes = [vp, vp, vp, C.c_int32, C.c_double, vp]
     L.fba_stat_add.argtypes = [P(Stat), C.c_double]
     L.fba_stat_var.restype = C.c_double

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "fba_kernels.h"
+#include "fba_snapshot_format.h"
 
 using namespace fba;
 
@@ -1773,7 +1774,9 @@ int fba_create(const fba_config* cfg, fba_ctx** out)
     if (D.single_rec)
         if (const char* ev = std::getenv("FBA_SCRATCH_SLOTS")) D.scratch_slots = std::max(1, std::min(E, std::atoi(ev)));   // (tests: several chunks with a few slots)
     D.rec_scratch = nullptr; D.copy_pending = nullptr; D.rec_buf = nullptr;
-    CHK(dev_alloc(c, &D.p_rec, (D.single_rec ? (size_t)E + D.scratch_slots : (size_t)2 * E) * P.N * P.Cs, false));
+    // (zeroed: a slot whose belief was never initiated -- a slot of fba_run_bapomdp beyond the configured runs -- then holds all-zero records and weights, which is
+    // what fba_belief_export writes for it and a block fba_belief_import takes in every record format; nothing else reads such a slot)
+    CHK(dev_alloc(c, &D.p_rec, (D.single_rec ? (size_t)E + D.scratch_slots : (size_t)2 * E) * P.N * P.Cs, true));
     if (D.single_rec) {   // E + scratch_slots buffers; a slot's filter and a scratch place's buffer change places after a resample / reset (swap_buffers_kernel)
         CHK(dev_alloc(c, &D.rec_buf, (size_t)E + D.scratch_slots));
         std::vector<int32_t> ids((size_t)E + D.scratch_slots);
@@ -2869,6 +2872,272 @@ int fba_belief_set(fba_ctx* c, int32_t slot, const int32_t* state, const double*
         HIPCHK(c, hipMemcpy(c->D.p_rec + pb * P.Cs, tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice));
     }
     c->belief_ready = true;
+    return FBA_OK;
+}
+
+// ---- belief snapshots (include/fba_hip.h; format and host pass: fba_snapshot_format.h; kernels: fba_snapshot.hip) ----
+
+// the state a belief keeps beside its main filter, which a snapshot would not carry; null = the belief is the main filter alone
+static const char* snapshot_extra_state(const fba_ctx* c)
+{
+    switch (c->cfg.belief) {
+        case FBA_BELIEF_REJECTION: case FBA_BELIEF_IMPORTANCE: case FBA_BELIEF_POINT: return nullptr;
+        case FBA_BELIEF_REINVIGORATION: return "the reinvigoration belief also keeps a fully connected filter (fba_belief_get_fully_connected)";
+        case FBA_BELIEF_CHEATING: return "the cheating belief also keeps a correct-graph filter and a likelihood";
+        case FBA_BELIEF_INCUBATOR: return "the incubator belief also keeps a fully connected filter and a weighted shadow filter";
+        case FBA_BELIEF_MH_GIBBS: return "the mh-within-gibbs belief also keeps the run's action-observation history and log likelihood";
+        case FBA_BELIEF_MH_NIPS: return "the mh-nips belief also keeps the run's action-observation history and log likelihood";
+        case FBA_BELIEF_NESTED: return "the nested belief also keeps a flat filter of domain states per particle (fba_belief_get_nested)";
+        default: return "this belief keeps state beside its main filter";
+    }
+}
+static int snapshot_record_format(const fba_ctx* c)   // as with_record_format numbers them
+{
+    const Problem& P = c->P;
+    if (P.hist) return 4 + P.hist;
+    if (P.ft_packed) return c->fdesc.FS == 2 ? 2 : (c->fdesc.FS == 3 ? 3 : 4);
+    return P.packed ? 1 : 0;
+}
+static bool snapshot_weighted(const fba_ctx* c) { return c->P.belief == FBA_BELIEF_IMPORTANCE; }
+// what a block must match to be taken by this context
+static fba_snapshot::Accepts snapshot_accepts(const fba_ctx* c)
+{
+    const Problem& P = c->P;
+    fba_snapshot::Accepts acc{};
+    fba_snapshot_head& h = acc.want;
+    h.magic = FBA_SNAPSHOT_MAGIC; h.version = FBA_SNAPSHOT_VERSION;
+    h.record_format = (uint8_t)snapshot_record_format(c);
+    h.weighted = snapshot_weighted(c) ? 1 : 0;
+    h.model = (uint8_t)P.model; h.domain = (uint8_t)P.domain; h.actions = (uint16_t)P.A;
+    h.size = (int16_t)c->cfg.size; h.width = (int16_t)c->cfg.width; h.height = (int16_t)c->cfg.height;
+    h.particles = P.N; h.particle_bytes = P.Cs * 4; h.counts_len = c->dense_C;
+    h.states = P.S; h.observations = P.O;
+    uint64_t ph = fba_snapshot::hash_words(FBA_SNAPSHOT_HASH_SEED, c->prior.data(), c->prior.size());
+    ph = fba_snapshot::hash_words(ph, c->prior_alt.data(), c->prior_alt.size());
+    ph = fba_snapshot::hash_words(ph, &P.structure_prior, 1);
+    if (P.ft_packed) {
+        const float listen[3] = {P.ft_acc, P.ft_inacc, P.ft_unif};
+        ph = fba_snapshot::hash_words(ph, listen, 3);
+    }
+    h.prior_hash = ph;
+    acc.hist_cap = P.hist_cap;
+    acc.compact  = P.hist_compact;
+    return acc;
+}
+// range and belief checks shared by the three calls
+static int snapshot_range(fba_ctx* c, const char* call, int32_t first, int32_t count)
+{
+    if (first < 0 || count < 0 || (long long)first + count > c->P.E)
+        return fail(c, FBA_EINVAL, "%s: slots [%d, %lld) are not within the context's %d", call, first, (long long)first + count, c->P.E);
+    if (const char* extra = snapshot_extra_state(c))
+        return fail(c, FBA_EINVAL, "%s: a snapshot holds the main filter of a slot, and %s", call, extra);
+    return FBA_OK;
+}
+// a destination slot must be between steps: no update pending, no parked search, no buffer swap pending (src >= 0: skipped, but its own
+// filter must be in its live buffer)
+static int snapshot_quiet(fba_ctx* c, const char* call, int32_t first, int32_t count, int32_t src)
+{
+    if (count <= 0) return FBA_OK;
+    const DeviceState& D = c->D;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<uint8_t> upd((size_t)count), swp((size_t)count, 0);
+    std::vector<int32_t> sim((size_t)count, 0);
+    HIPCHK(c, hipMemcpy(upd.data(), D.need_update + first, (size_t)count, hipMemcpyDeviceToHost));
+    if (D.copy_pending) HIPCHK(c, hipMemcpy(swp.data(), D.copy_pending + first, (size_t)count, hipMemcpyDeviceToHost));
+    if (D.s_sim) HIPCHK(c, hipMemcpy(sim.data(), D.s_sim + first, (size_t)count * 4, hipMemcpyDeviceToHost));
+    for (int b = 0; b < count; ++b) {
+        if (first + b == src) continue;
+        if (upd[(size_t)b]) return fail(c, FBA_ESTATE, "%s: slot %d has a belief update pending", call, first + b);
+        if (sim[(size_t)b]) return fail(c, FBA_ESTATE, "%s: slot %d has a parked search", call, first + b);
+        if (swp[(size_t)b]) return fail(c, FBA_ESTATE, "%s: slot %d has a buffer swap pending", call, first + b);
+    }
+    if (src >= 0 && D.copy_pending) {
+        uint8_t s = 0;
+        HIPCHK(c, hipMemcpy(&s, D.copy_pending + src, 1, hipMemcpyDeviceToHost));
+        if (s) return fail(c, FBA_ESTATE, "%s: slot %d has a buffer swap pending", call, src);
+    }
+    return FBA_OK;
+}
+// the kernels' arguments but for the range; d_limit: the limits of the parent-set words, uploaded here
+static int snapshot_args(fba_ctx* c, BeliefSnapshotArgs& a, ScratchBuf<uint32_t>& d_limit)
+{
+    const Problem& P = c->P;
+    const bool factored = P.model == FBA_MODEL_BA_FACTORED;
+    a = BeliefSnapshotArgs{};
+    a.per_slot = fba_snapshot::block_bytes(snapshot_weighted(c), P.N, (int64_t)P.Cs * 4);
+    a.weighted = snapshot_weighted(c) ? 1 : 0;
+    a.ncounts  = factored ? c->fdesc.ncounts : P.C;
+    a.ncells   = P.hist ? (factored ? c->fdesc.ncounts : c->dense_C) : 0;
+    if (factored && !P.hist && c->fdesc.nvar > 0) {
+        a.nvar    = P.ft_packed ? 1 : c->fdesc.nvar;
+        a.mask_at = P.ft_packed ? c->fdesc.ncounts / 2 : c->fdesc.ncounts;
+        std::vector<uint32_t> limit((size_t)a.nvar, 0xffffffffu);   // word m names parents among the candidates of every node it serves
+        const int nodes = P.A * (c->fdesc.FS + c->fdesc.FO);
+        for (int k = 0; k < nodes && k < MAXNODES; ++k) {
+            const FNode& nd = c->fdesc.nodes[k];
+            if (nd.var >= 0 && nd.var < a.nvar && nd.nmax >= 0 && nd.nmax < 32) limit[(size_t)nd.var] = std::min(limit[(size_t)nd.var], 1u << nd.nmax);
+        }
+        HIPCHK(c, d_limit.alloc(limit.size()));
+        HIPCHK(c, hipMemcpy(d_limit.p, limit.data(), limit.size() * 4, hipMemcpyHostToDevice));
+        a.mask_limit = d_limit.p;
+    }
+    return FBA_OK;
+}
+// slots of one chunk: what SNAPSHOT_STAGE_BYTES of staging memory hold (one block at least), a grid's rows at most
+// (FBA_SNAPSHOT_STAGE_BYTES in the environment: another bound, read at every call -- include/fba_hip.h and INTEGRATION.md section 4a state it;
+// the tests use it for several chunks of a few small slots, a host short of device memory for less staging)
+static int snapshot_chunk(int64_t per_slot, int32_t count)
+{
+    int64_t stage = (int64_t)SNAPSHOT_STAGE_BYTES;
+    if (const char* ev = std::getenv("FBA_SNAPSHOT_STAGE_BYTES")) stage = std::max<int64_t>(1, std::atoll(ev));
+    return (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)count, (int64_t)SNAPSHOT_MAX_SLOTS, stage / per_slot}));
+}
+
+int fba_belief_snapshot_bytes(const fba_ctx* c, int64_t* per_slot)
+{
+    if (!c || !per_slot) return FBA_EINVAL;
+    *per_slot = fba_snapshot::block_bytes(snapshot_weighted(c), c->P.N, (int64_t)c->P.Cs * 4);
+    return FBA_OK;
+}
+
+int fba_belief_export(fba_ctx* c, int32_t first, int32_t count, void* buf, int64_t cap)
+{
+    if (!c) return FBA_EINVAL;
+    int rc;
+    if ((rc = snapshot_range(c, "fba_belief_export", first, count))) return rc;
+    const Problem& P = c->P;
+    BeliefSnapshotArgs a;
+    ScratchBuf<uint32_t> d_limit;
+    if ((rc = snapshot_args(c, a, d_limit))) return rc;
+    const int64_t per = a.per_slot;
+    if (count > 0 && (!buf || cap < (int64_t)count * per))
+        return fail(c, FBA_EINVAL, "fba_belief_export: %d blocks of %lld bytes need %lld, the buffer has %lld", count, (long long)per,
+                    (long long)count * per, (long long)(buf ? cap : 0));
+    if (count == 0) return FBA_OK;
+    launch_materialize_reset(c->P, c->D, c->stream);   // a lazily reset rejection filter: write the states out first, as fba_belief_get does
+    const int chunk = snapshot_chunk(per, count);
+    ScratchBuf<uint8_t> d_stage;
+    ScratchBuf<unsigned long long> d_check;
+    HIPCHK(c, d_stage.alloc((size_t)chunk * (size_t)per));
+    HIPCHK(c, d_check.alloc((size_t)chunk));
+    std::vector<unsigned long long> h_check((size_t)chunk);
+    std::vector<uint32_t> h_cnt((size_t)chunk, 0);
+    const fba_snapshot_head want = snapshot_accepts(c).want;
+    uint8_t* out = static_cast<uint8_t*>(buf);
+    for (int done = 0; done < count; done += chunk) {
+        const int n = std::min(chunk, count - done);
+        a.first = first + done; a.count = n; a.stage = d_stage.p; a.check = d_check.p;
+        HIPCHK(c, hipMemsetAsync(d_check.p, 0, (size_t)n * 8, c->stream));
+        launch_snapshot_pack(P, c->D, a, c->stream);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(out + (size_t)done * (size_t)per, d_stage.p, (size_t)n * (size_t)per, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(h_check.data(), d_check.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+        if (P.hist) HIPCHK(c, hipMemcpyAsync(h_cnt.data(), c->D.hist_cnt + first + done, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (int b = 0; b < n; ++b) {
+            const int e = first + done + b;
+            fba_snapshot_head h = want;
+            h.hist_cnt = h_cnt[(size_t)b];
+            h.stride   = (uint32_t)(P.hist ? hist_stride(P, hist_total(h.hist_cnt)) : P.Cs) * 4u;
+            h.updates  = (P.packed || P.ft_packed) && (size_t)e < c->packed_updates.size() ? (uint16_t)std::min<uint32_t>(c->packed_updates[(size_t)e], 65535u) : 0;
+            h.checksum = h_check[(size_t)b];
+            std::memcpy(out + (size_t)(done + b) * (size_t)per, &h, sizeof h);
+        }
+    }
+    return FBA_OK;
+}
+
+int fba_belief_import(fba_ctx* c, int32_t first, int32_t count, const void* buf, int64_t bytes)
+{
+    if (!c) return FBA_EINVAL;
+    int rc;
+    if ((rc = snapshot_range(c, "fba_belief_import", first, count))) return rc;
+    const Problem& P = c->P;
+    BeliefSnapshotArgs a;
+    ScratchBuf<uint32_t> d_limit;
+    if ((rc = snapshot_args(c, a, d_limit))) return rc;
+    const int64_t per = a.per_slot;
+    const uint8_t* in = static_cast<const uint8_t*>(buf);
+    const fba_snapshot::Accepts acc = snapshot_accepts(c);
+    if (bytes != (int64_t)count * per || (count > 0 && !buf)) {
+        // (blocks of another configuration have another size: where the first header says which field differs, that is the better message)
+        char msg[256];
+        if (buf && count > 0 && bytes >= (int64_t)sizeof(fba_snapshot_head) && fba_snapshot::check_head(in, per, acc, msg, sizeof msg))
+            return fail(c, FBA_EINVAL, "fba_belief_import: block 0 (slot %d): %s", first, msg);
+        return fail(c, FBA_EINVAL, "fba_belief_import: bytes %lld / %lld (%d blocks of %lld)", (long long)(buf ? bytes : 0), (long long)count * per, count, (long long)per);
+    }
+    if (count == 0) return FBA_OK;
+    // ---- host pass: every header, before anything reaches the device ----
+    std::vector<fba_snapshot_head> heads((size_t)count);
+    for (int b = 0; b < count; ++b) {
+        char msg[256];
+        if (fba_snapshot::check_head(in + (size_t)b * (size_t)per, per, acc, msg, sizeof msg))
+            return fail(c, FBA_EINVAL, "fba_belief_import: block %d (slot %d): %s", b, first + b, msg);
+        std::memcpy(&heads[(size_t)b], in + (size_t)b * (size_t)per, sizeof(fba_snapshot_head));
+    }
+    if ((rc = snapshot_quiet(c, "fba_belief_import", first, count, -1))) return rc;
+    // ---- device pass: checksum and every record of every block, then (and only then) the commit ----
+    const int chunk = snapshot_chunk(per, count);
+    const bool one = chunk >= count;   // the whole range is staged at once: it is uploaded once
+    ScratchBuf<uint8_t> d_stage;
+    ScratchBuf<unsigned long long> d_check;   // [chunk] checksums, then the error word
+    HIPCHK(c, d_stage.alloc((size_t)chunk * (size_t)per));
+    HIPCHK(c, d_check.alloc((size_t)chunk + 1));
+    std::vector<unsigned long long> h_check((size_t)chunk + 1);
+    static const char* const what_names[] = {"", "a weight that is negative or not finite", "a state outside the domain", "an illegal parent-set word",
+                                             "a history entry outside the domain's tables", "a count that is negative or not finite"};
+    for (int pass = 0; pass < 2; ++pass)
+        for (int done = 0; done < count; done += chunk) {
+            const int n = std::min(chunk, count - done);
+            a.first = first + done; a.count = n; a.stage = d_stage.p; a.check = d_check.p; a.bad = d_check.p + chunk;
+            if (pass == 0 || !one)
+                HIPCHK(c, hipMemcpyAsync(d_stage.p, in + (size_t)done * (size_t)per, (size_t)n * (size_t)per, hipMemcpyHostToDevice, c->stream));
+            if (pass == 1) {
+                launch_snapshot_commit(P, c->D, a, c->stream);
+                HIPCHK(c, hipGetLastError());
+                HIPCHK(c, hipStreamSynchronize(c->stream));   // (the staging buffer is reused by the next chunk, the caller's by the caller)
+                continue;
+            }
+            HIPCHK(c, hipMemsetAsync(d_check.p, 0, (size_t)chunk * 8, c->stream));
+            HIPCHK(c, hipMemsetAsync(a.bad, 0xff, 8, c->stream));
+            launch_snapshot_validate(P, c->D, a, c->stream);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipMemcpyAsync(h_check.data(), d_check.p, ((size_t)chunk + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            for (int b = 0; b < n; ++b)
+                if (h_check[(size_t)b] != heads[(size_t)(done + b)].checksum)
+                    return fail(c, FBA_EINVAL, "fba_belief_import: block %d (slot %d): checksum %016llx in the header, %016llx over the payload", done + b,
+                                first + done + b, (unsigned long long)heads[(size_t)(done + b)].checksum, h_check[(size_t)b]);
+            const unsigned long long bad = h_check[(size_t)chunk];
+            if (bad != ~0ull) {
+                const int b = done + (int)(bad >> 40), what = (int)(bad & 0xffu);
+                return fail(c, FBA_EINVAL, "fba_belief_import: block %d (slot %d), particle %lld: %s", b, first + b, (long long)((bad >> 8) & 0xffffffffull),
+                            what >= 1 && what <= 5 ? what_names[what] : "an invalid record");
+            }
+        }
+    if (P.packed || P.ft_packed) {
+        if (c->packed_updates.size() != (size_t)P.E) c->packed_updates.assign((size_t)P.E, 0);
+        for (int b = 0; b < count; ++b) c->packed_updates[(size_t)(first + b)] = heads[(size_t)b].updates;
+    }
+    c->belief_ready = true;
+    return FBA_OK;
+}
+
+int fba_belief_replicate(fba_ctx* c, int32_t src, int32_t first, int32_t count)
+{
+    if (!c) return FBA_EINVAL;
+    int rc;
+    if ((rc = snapshot_range(c, "fba_belief_replicate", first, count))) return rc;
+    if (src < 0 || src >= c->P.E) return fail(c, FBA_EINVAL, "fba_belief_replicate: source slot %d is not within the context's %d", src, c->P.E);
+    if (count == 0) return FBA_OK;
+    if (!c->belief_ready) return fail(c, FBA_ESTATE, "fba_belief_replicate: belief not initiated");
+    if ((rc = snapshot_quiet(c, "fba_belief_replicate", first, count, src))) return rc;
+    launch_materialize_reset(c->P, c->D, c->stream);   // (a lazily reset source: its states are written out, results keep their bits)
+    launch_snapshot_replicate(c->P, c->D, src, first, count, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((c->P.packed || c->P.ft_packed) && c->packed_updates.size() == (size_t)c->P.E)
+        for (int b = 0; b < count; ++b) c->packed_updates[(size_t)(first + b)] = c->packed_updates[(size_t)src];
     return FBA_OK;
 }
 

@@ -127,6 +127,27 @@ struct BeliefProbeArgs {
 // 64 -> 0.75, 32 -> 0.80, 16 -> 0.95)
 constexpr int PROBE_CHUNK = 64;
 void launch_belief_probe(const Problem& P, const DeviceState& D, const BeliefProbeArgs& a, hipStream_t st);
+// belief snapshots (fba_snapshot.hip): the blocks of `count` slots stand in `stage` at per_slot bytes each, laid out as include/fba_hip.h
+// states it (fba_snapshot_head, weights, records); slot first + b owns block b.  All state of the feature is in these arguments
+constexpr int SNAPSHOT_MAX_SLOTS = 32768;            // slots of one launch (a grid row each)
+constexpr size_t SNAPSHOT_STAGE_BYTES = (size_t)256 << 20;   // staging memory of one export / import chunk (one block at least)
+enum { SNAP_BAD_WEIGHT = 1, SNAP_BAD_STATE = 2, SNAP_BAD_STRUCTURE = 3, SNAP_BAD_ENTRY = 4, SNAP_BAD_COUNT = 5 };
+struct BeliefSnapshotArgs {
+    int32_t first, count;
+    uint8_t* stage;                 // [count][per_slot]
+    int64_t per_slot;               // bytes of a block
+    unsigned long long* check;      // [count] the payload checksums (the caller zeroes them)
+    unsigned long long* bad;        // [1] validation: the smallest (block << 40 | particle << 8 | SNAP_BAD_*) met; the caller sets ~0
+    int32_t weighted;               // the blocks hold weights
+    int32_t ncounts;                // fp32 records: the words of a record that are counts
+    int32_t nvar, mask_at;          // parent-set words of a record (0: none) and the word the first stands at
+    int32_t ncells;                 // history records: cells of the dense table an entry may name
+    const uint32_t* mask_limit;     // [nvar] parent-set word m is legal below this
+};
+void launch_snapshot_pack(const Problem& P, const DeviceState& D, const BeliefSnapshotArgs& a, hipStream_t st);      // export: gather + checksum
+void launch_snapshot_validate(const Problem& P, const DeviceState& D, const BeliefSnapshotArgs& a, hipStream_t st);  // import, first pass
+void launch_snapshot_commit(const Problem& P, const DeviceState& D, const BeliefSnapshotArgs& a, hipStream_t st);    // import, second pass
+void launch_snapshot_replicate(const Problem& P, const DeviceState& D, int src, int first, int count, hipStream_t st);
 void launch_uniform_scan(int n, double* w_tmp, double* out, double* total, double* ctot, hipStream_t st);
 
 }  // namespace fba

@@ -373,6 +373,34 @@ class Engine:
         self._chk(self.L.fba_belief_set(self.h, slot, None if s is None else s.ctypes.data,
                                         None if w is None else w.ctypes.data, None if c is None else c.ctypes.data))
 
+    # ---- belief snapshots
+    @property
+    def belief_snapshot_bytes(self):
+        """Bytes of one slot's snapshot block (fba_belief_snapshot_bytes): 64 + [particles * 8] + particles * particle_bytes."""
+        n = C.c_int64()
+        self._chk(self.L.fba_belief_snapshot_bytes(self.h, C.byref(n)))
+        return n.value
+
+    def belief_export(self, first=0, count=None):
+        """The main filters of slots [first, first + count) as stored (fba_belief_export): np.uint8[count, belief_snapshot_bytes], one
+        self-describing block per slot -- header (N.SNAPSHOT_HEAD_DTYPE), weights, records.  No count table is built."""
+        count = self.slots - first if count is None else count
+        out = np.zeros((max(count, 0), self.belief_snapshot_bytes), np.uint8)
+        self._chk(self.L.fba_belief_export(self.h, first, count, out.ctypes.data, out.nbytes))
+        return out
+
+    def belief_import(self, first, blocks):
+        """Blocks of belief_export (of this or another context of the same configuration and prior) into slots first, first + 1, ...
+        (fba_belief_import).  Every block is checked before any is taken: a ValueError leaves the context as it was."""
+        b = np.ascontiguousarray(blocks, np.uint8)
+        per = self.belief_snapshot_bytes
+        count = b.size // per if b.ndim != 2 else b.shape[0]
+        self._chk(self.L.fba_belief_import(self.h, first, count, b.ctypes.data, b.nbytes))
+
+    def belief_replicate(self, src, first, count):
+        """The filter of slot `src` into every slot of [first, first + count) on the device (fba_belief_replicate); `src` is skipped."""
+        self._chk(self.L.fba_belief_replicate(self.h, src, first, count))
+
     def last_step_info(self):
         out = np.zeros(self.slots, N.TRACE_DTYPE)
         self._chk(self.L.fba_last_step_info(self.h, out.ctypes.data))

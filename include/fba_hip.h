@@ -447,6 +447,85 @@ int fba_probe_enable(fba_ctx* ctx, int32_t first, int32_t count, int32_t capacit
 int fba_probe_count(const fba_ctx* ctx, int64_t* seen);  /* returns the records stored; *seen (may be NULL) counts every step probed, so seen > stored says the buffer was too small */
 int fba_get_probe(const fba_ctx* ctx, fba_probe_rec* out, int32_t cap);
 
+/* Belief snapshots: keeping, moving and copying the main filter of a slot in the record format the context stores (fba_particle_bytes) --
+ * no count table is built anywhere, so a 16 384-particle gridworld filter is 3.0 MB, not the 3.1 GB fba_belief_get would hand out, and the
+ * history-record contexts that refuse fba_belief_set are served like every other.
+ * A snapshot is one opaque, self-describing block per slot, of fba_belief_snapshot_bytes bytes, constant for a context:
+ *   the header fba_snapshot_head, 64 bytes | weights, particles * 8 bytes (importance filters only) | records, particles * fba_particle_bytes bytes
+ * The header carries a fingerprint of what a block must match to be taken: the record format (0 fp32 counts, a plain POMDP's states included,
+ * 1 packed tiger, 2..4 packed factored tiger of that many state features, 5 gridworld FBA-POMDP history records, 6 tabular gridworld
+ * history records, 7 collision-avoidance history records), model, domain and its size arguments, particles, fba_particle_bytes,
+ * fba_counts_len, S / A / O, weighted or flat, and a 64-bit hash of the prior the records stand over (FNV-1a over the 32-bit words of
+ * what fba_get_prior returns, then of the gridworld's alternative x / y rows where history records use them, then of the structure prior
+ * and, for packed factored-tiger records, the three counts of the listen node).  Records stand from the start of their part at the slot's
+ * CURRENT stride, head.stride bytes: 64, 128 or fba_particle_bytes for history records of up to 14, up to 30 or more entries,
+ * fba_particle_bytes otherwise; the bytes behind the last record, behind a history record's last entry and behind a record's state word
+ * are zero, so two exports of one filter are equal byte for byte and export(import(x)) == x.
+ *   checksum = sum over the 32-bit words w[i] of the payload (all that follows the header, i from 0) of w[i] * ((i + 1) * FBA_SNAPSHOT_CHECK_MUL)
+ *              modulo 2^64 -- a sum, so no order of additions can change it; a host recomputes it from this line.
+ * fba_belief_export writes the blocks of slots [first, first + count) to buf (cap >= count * fba_belief_snapshot_bytes).  Like fba_belief_get
+ *   it first writes out the states of a lazily reset rejection filter (results keep their bits); nothing else of the context changes, so
+ *   it may stand between any two calls, after fba_run_*, and on inactive slots.  Slots are packed on the device and copied a chunk at a
+ *   time, through at most 256 MB of staging memory (FBA_SNAPSHOT_STAGE_BYTES in the environment, read at every export and import, sets
+ *   another bound in bytes; one block is staged at least).  Export does not ask whether a belief was ever initiated: a slot that never
+ *   was -- a slot of fba_run_planning / fba_run_bapomdp beyond the configured runs (fba_run_ticks keeps every slot busy), any slot before fba_belief_init -- holds all-zero records and weights
+ *   since fba_create, and its block says so: state 0 in every particle, no history entries, counts 0.0, weights 0.0.  Such a block is
+ *   well-formed, an import takes it, and the slot it lands in is as uninitiated as its source.  Export does not look at pending updates or
+ *   parked searches of its slots either: it writes the filter as it stands.
+ * fba_belief_import takes `count` blocks (bytes == count * fba_belief_snapshot_bytes) into slots [first, first + count), in two passes, so
+ *   that a refused block leaves the context untouched.  Host pass: magic, layout version, every fingerprint field, hist_cnt against the
+ *   stride and the room of a record, the stride against the format -- FBA_EINVAL, the message names the block, the field and both values.
+ *   Device pass: the checksum, then EVERY record before anything is committed -- weights finite and >= 0, state in [0, S), parent-set words
+ *   legal for their nodes, fp32 counts finite and >= 0, every history entry decoding to fields of the domain and cells inside the table --
+ *   FBA_EINVAL, the message names the slot, the particle and what was wrong with it (the first such particle).  Commit: records into the
+ *   slot's live buffer at the block's stride, weights into the live weight buffer, the slot's entries per action set, a pending lazy reset
+ *   dropped.  Nothing else of the slot is touched: position, environment state, returns, counters, trace and fba_last_step_info stay.  A
+ *   destination slot with a belief update pending, a parked search or a pending buffer swap (inside fba_run_* with a search budget) gives
+ *   FBA_ESTATE.  Like fba_belief_set, a successful import makes the belief usable without fba_belief_init.  The caller's buffer must not
+ *   change during the call: a range beyond the staging bound is read twice (every chunk validated, then every chunk committed), and the
+ *   second reading is not judged again.  The weights are judged one by one, as stated: a block whose weights are all 0.0 (what a
+ *   never-initiated slot exports) or whose weights sum beyond the fp64 range is taken, and the slot then behaves as a filter of that
+ *   weight total does everywhere else in the engine -- the readers above give zeros for it; it is the host's to import filters it means to run.
+ * fba_belief_replicate copies the filter of slot src into every slot of [first, first + count) on the device, with no host round trip
+ *   and no validation (the source is the engine's own); src itself is skipped where it lies inside the range.  Same commit, same FBA_ESTATE,
+ *   and FBA_ESTATE too on a context whose belief was never made usable (fba_belief_init, fba_belief_set, fba_belief_import or fba_run_*).
+ *   The copies are independent filters: they run on at their own slots' Philox positions.
+ * Serves the rejection, importance and point-estimate beliefs in every record format, fp32 records under FBA_DENSE_PARTICLES=1 and the
+ * plain POMDP filter (states only) included.  FBA_EINVAL for the beliefs whose state is more than the main filter -- reinvigoration and
+ * cheating (a second filter), incubator (second and shadow filters), mh-within-gibbs and mh-nips (the run's action-observation history and
+ * log likelihood), nested (a filter of domain states per particle) -- for a slot range outside the context and for a buffer too small.
+ * fba_run_planning and fba_run_bapomdp initiate a slot's belief at the start of every run, and so does fba_run_ticks when it first
+ * sets the slots up and whenever a slot starts a run: an imported belief lives until its slot's run ends.  Warm-starting the
+ * whole-experiment drivers from snapshots is not offered. */
+#define FBA_SNAPSHOT_MAGIC     0x53414246u              /* "FBAS" */
+#define FBA_SNAPSHOT_VERSION   1
+#define FBA_SNAPSHOT_CHECK_MUL 0x9E3779B97F4A7C15ull
+#define FBA_SNAPSHOT_HASH_SEED 0xcbf29ce484222325ull
+typedef struct fba_snapshot_head {
+    uint32_t magic;           /* FBA_SNAPSHOT_MAGIC                                                                            */
+    uint16_t version;         /* FBA_SNAPSHOT_VERSION                                                                          */
+    uint8_t  record_format;   /* 0..7, above                                                                                   */
+    uint8_t  weighted;        /* 1: importance filter, the block holds weights; 0: flat filter                                 */
+    uint8_t  model, domain;   /* FBA_MODEL_*, FBA_DOM_*                                                                        */
+    uint16_t actions;         /* A                                                                                             */
+    int16_t  size, width, height;   /* fba_config's domain size arguments                                                      */
+    uint16_t updates;         /* packed records: belief updates the slot has counted since fba_belief_init (what fba_belief_update
+                               * guards the 16-bit increments with); 0 otherwise                                              */
+    int32_t  particles;       /* N                                                                                             */
+    int32_t  particle_bytes;  /* fba_particle_bytes                                                                            */
+    int32_t  counts_len;      /* fba_counts_len                                                                                */
+    int32_t  states;          /* S                                                                                             */
+    int32_t  observations;    /* O                                                                                             */
+    uint32_t hist_cnt;        /* history records: entries per record of action a in bits 8a..8a+7; 0 otherwise                 */
+    uint32_t stride;          /* bytes between the records of this block                                                       */
+    uint64_t prior_hash;
+    uint64_t checksum;
+} fba_snapshot_head;
+int fba_belief_snapshot_bytes(const fba_ctx* ctx, int64_t* per_slot);
+int fba_belief_export   (fba_ctx* ctx, int32_t first, int32_t count, void* buf, int64_t cap);
+int fba_belief_import   (fba_ctx* ctx, int32_t first, int32_t count, const void* buf, int64_t bytes);
+int fba_belief_replicate(fba_ctx* ctx, int32_t src, int32_t first, int32_t count);
+
 /* diagnostic: out[i] = u * sqrt(L[i] / n[i]) evaluated on the device, to check that the
  * engine's fp64 divide and square root round like the host's (they must, for UCB parity) */
 int fba_selftest_ucb(fba_ctx* ctx, const double* L, const int32_t* n, int32_t count, double u, double* out);
