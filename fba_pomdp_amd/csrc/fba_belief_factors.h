@@ -57,20 +57,29 @@ __device__ __forceinline__ double slot_weight_total(const Problem& P, const Devi
     return s_part[0];
 }
 
-// calls f(std::integral_constant<int, FMT>) with the record format of the context: FMT 0 fp32 counts, 1 packed tiger, 2..4 packed factored
-// tiger of that many state features (record_count), 5..7 history records of Problem::hist = FMT - 4
+// the record format of a context, FMT: 0 fp32 counts, 1 packed tiger, 2..4 packed factored tiger of that many state features (ft_FS;
+// record_count), 5..7 history records of Problem::hist = FMT - 4.  The one numbering: the kernels' FMT and the snapshot header's record_format
+inline int record_format(const Problem& P, int ft_FS)
+{
+    if (P.hist) return 4 + P.hist;
+    if (P.ft_packed) return ft_FS == 2 ? 2 : (ft_FS == 3 ? 3 : 4);
+    return P.packed ? 1 : 0;
+}
+
+// calls f(std::integral_constant<int, FMT>) with the record format of the context
 template <class F>
 void with_record_format(const Problem& P, int ft_FS, F&& f)
 {
-    if (P.hist == 3) f(std::integral_constant<int, 7>{});
-    else if (P.hist == 2) f(std::integral_constant<int, 6>{});
-    else if (P.hist) f(std::integral_constant<int, 5>{});
-    else if (P.ft_packed) {
-        if (ft_FS == 2) f(std::integral_constant<int, 2>{});
-        else if (ft_FS == 3) f(std::integral_constant<int, 3>{});
-        else f(std::integral_constant<int, 4>{});
-    } else if (P.packed) f(std::integral_constant<int, 1>{});
-    else f(std::integral_constant<int, 0>{});
+    switch (record_format(P, ft_FS)) {
+        case 7: return f(std::integral_constant<int, 7>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        case 5: return f(std::integral_constant<int, 5>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 1: return f(std::integral_constant<int, 1>{});
+        default: return f(std::integral_constant<int, 0>{});
+    }
 }
 
 // what belief_factors leaves in LDS for the caller's own phases

@@ -12,9 +12,10 @@
 #include <cstring>
 #include <string>
 #include <map>
-#include <queue>
+#include <memory>
 #include <vector>
 
+#include "fba_belief_factors.h"   // record_format
 #include "fba_kernels.h"
 #include "fba_snapshot_format.h"
 
@@ -95,6 +96,8 @@ int fail(fba_ctx* c, int code, const char* fmt, ...)
         if (_e != hipSuccess)                                                                       \
             return fail((c), FBA_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_e), __FILE__, __LINE__); \
     } while (0)
+
+#define TRY(x) do { if (const int _rc = (x)) return _rc; } while (0)   // passes a refusal on to the caller
 
 template <typename T>
 int dev_alloc(fba_ctx* c, T** p, size_t n, bool zero = true)
@@ -1204,6 +1207,773 @@ uint64_t sum_counter(fba_ctx* c, const T* dev, int n, int* rc)
     return s;
 }
 
+// ==== The stages of fba_create, in the order it calls them ("How a context is made").  A stage returns FBA_OK or the
+// code of a refusal whose message fail() has stored: in g_create_error while no context exists, in the context from then on.
+
+// ---- stage 1: the environment switches, read once per fba_create (not cached: tests change them between contexts of one process)
+struct CreateSwitches {
+    bool double_buffer, node_visits, wide_hash, dense_particles;   // set at all
+    bool no_etiger, tiger_gather;                                  // set to a number other than 0
+    int hist_multi;                                                // 0 unset, 1 set to 0, 2 set to another number
+    bool hist_lockstep;                                            // on unless set to 0
+    bool tree_records, rows_hbm, stride_full;                      // FBA_HIST_TREE=records, FBA_HIST_ROWS=hbm, FBA_HIST_STRIDE=full
+    bool is_multi_min_set;                                         // FBA_IS_MULTI_MIN is set (tests: exercise the large-filter path), and
+    int is_multi_min;                                              // ... the particle count from which the importance filter takes several launches
+    int scratch_slots, node_bound;                                 // 0 unset, else at least 1 / 2
+    int node_words;                                                // 0 unset
+};
+CreateSwitches read_create_switches()
+{
+    const auto number = [](const char* v, int unset) { return v ? std::atoi(v) : unset; };
+    const auto says   = [](const char* v, const char* word) { return v && !std::strcmp(v, word); };
+    const auto at_least = [](const char* v, int least) { return v ? std::max(least, std::atoi(v)) : 0; };
+    CreateSwitches s{};
+    s.double_buffer   = std::getenv("FBA_DOUBLE_BUFFER") != nullptr;
+    s.node_visits     = std::getenv("FBA_NODE_VISITS") != nullptr;
+    s.wide_hash       = std::getenv("FBA_WIDE_HASH") != nullptr;
+    s.dense_particles = std::getenv("FBA_DENSE_PARTICLES") != nullptr;
+    s.no_etiger       = number(std::getenv("FBA_NO_ETIGER"), 0) != 0;
+    s.tiger_gather    = number(std::getenv("FBA_TIGER_GATHER"), 0) != 0;
+    const char* multi = std::getenv("FBA_HIST_MULTI");
+    s.hist_multi      = multi ? (std::atoi(multi) != 0 ? 2 : 1) : 0;
+    s.hist_lockstep   = number(std::getenv("FBA_HIST_LOCKSTEP"), 1) != 0;
+    s.tree_records    = says(std::getenv("FBA_HIST_TREE"), "records");
+    s.rows_hbm        = says(std::getenv("FBA_HIST_ROWS"), "hbm");
+    s.stride_full     = says(std::getenv("FBA_HIST_STRIDE"), "full");
+    // one workgroup per slot up to IS_MAX_CHUNKS * 256 particles, several launches beyond; the switch lowers the switch-over
+    const char* multi_min = std::getenv("FBA_IS_MULTI_MIN");
+    s.is_multi_min_set = multi_min != nullptr;
+    s.is_multi_min     = multi_min ? std::max(1, std::atoi(multi_min)) : IS_MAX_CHUNKS * 256 + 1;
+    s.scratch_slots   = at_least(std::getenv("FBA_SCRATCH_SLOTS"), 1);   // (tests: several chunks with a few slots)
+    s.node_bound      = at_least(std::getenv("FBA_NODE_BOUND"), 2);      // (tests: exercise the overflow guard)
+    s.node_words      = number(std::getenv("FBA_NODE_WORDS"), 0);        // (layout experiments: padded records)
+    return s;
+}
+
+// ---- stage 2: what needs no context -- the argument checks, the composite beliefs mapped onto the two filters, the domain
+// the reference's constructor / validate() errors (POUCT.cpp:34-50, RejectionSampling.cpp:7-13, FactoredTiger.cpp:13-17, TigerPriors.cpp:22-25)
+int check_arguments(const fba_config& cfg)
+{
+    if (cfg.sims < 1 && cfg.planner == FBA_PLANNER_POUCT) return fail(nullptr, FBA_EINVAL, "cannot initiate POUCT with %d simulations, must be greater than 0", cfg.sims);
+    if (cfg.horizon <= 0) return fail(nullptr, FBA_EINVAL, "cannot initiate POUCT with %d horizon, must be greater than 0", cfg.horizon);
+    if (cfg.horizon > 255) return fail(nullptr, FBA_EINVAL, "horizon %d exceeds the 255 steps a stream address holds", cfg.horizon);
+    if (cfg.particles < 1) return fail(nullptr, FBA_EINVAL, "cannot initiate belief with n = %d", cfg.particles);
+    if (cfg.discount <= 0 || cfg.discount > 1) return fail(nullptr, FBA_EINVAL, "discount must be in (0, 1]");
+    if (cfg.runs < 1 || cfg.episodes < 1) return fail(nullptr, FBA_EINVAL, "runs and episodes must be >= 1");
+    if (cfg.episodes > 65535) return fail(nullptr, FBA_EINVAL, "episodes %d exceeds the 65535 a stream address holds", cfg.episodes);
+    if (cfg.model == FBA_MODEL_POMDP && cfg.episodes != 1) return fail(nullptr, FBA_EINVAL, "planning runs have exactly one episode per run");
+    int ndev = 0;   // (behind the checks above: they answer on a machine without a device too)
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, FBA_ENODEVICE, "no HIP device visible: libfba_hip has no CPU path");
+    if (cfg.device < 0 || cfg.device >= ndev) return fail(nullptr, FBA_EINVAL, "device %d out of range (%d visible)", cfg.device, ndev);
+    return FBA_OK;
+}
+
+// the reference has fully connected priors for factored tiger, collision avoidance and sysadmin
+// (GridWorldFactBAPrior::sampleFullyConnectedState throws "nyi"): all three are built
+bool has_fully_connected_prior(const fba_config& cfg)
+{
+    return cfg.model == FBA_MODEL_BA_FACTORED && (is_ftiger(cfg.domain) || is_ca(cfg.domain) || is_sys(cfg.domain)) &&
+           !(is_ca(cfg.domain) && cfg.structure_prior == FBA_SP_FULLY_CONNECTED);
+}
+
+// a weighted (importance) filter + a rejection filter of correct-graph particles it copies from when
+// its log likelihood drops below --threshold (prototypes/CheatingReinvigoration.cpp)
+int map_cheating(const fba_config& cfg, Problem& P)
+{
+    if (cfg.model != FBA_MODEL_BA_FACTORED) return fail(nullptr, FBA_EINVAL, "cheating-reinvigoration belief: needs a factored model (fbapomdp)");
+    if (cfg.particles < 1 || cfg.resample_amount < 1)  // CheatingReinvigoration.cpp:30-34; :36-40 below
+        return fail(nullptr, FBA_EINVAL, "CheatingReinvigoration::cannot initiate belief of size < 1 (%d), or resample size of < 1 (%d)", cfg.particles, cfg.resample_amount);
+    if (cfg.threshold >= 0) return fail(nullptr, FBA_EINVAL, "CheatingReinvigoration::cannot initiate with resample_threshold >= 0 (is:%f)", cfg.threshold);
+    P.belief = FBA_BELIEF_IMPORTANCE;
+    P.cheat  = cfg.resample_amount;
+    return FBA_OK;
+}
+
+// an importance filter + the run's (a, o) history + a Metropolis-Hastings re-draw of the filter when the log
+// likelihood drops below --threshold (MHwithinGibbs.cpp, MHNIPS2018.cpp); built for the priors that have
+// computePriorModel and mutate and a fully enumerable state space: factored tiger, collision avoidance
+int map_mh(const fba_config& cfg, Problem& P)
+{
+    const bool nips  = cfg.belief == FBA_BELIEF_MH_NIPS;
+    const char* name = nips ? "MHNIPS2018" : "MHwithinGibbs";
+    if (cfg.model != FBA_MODEL_BA_FACTORED || cfg.dirichlet_regular ||
+        !(is_ftiger(cfg.domain) || is_ca(cfg.domain) || cfg.domain == FBA_DOM_GRIDWORLD || is_sys(cfg.domain)) ||
+        (is_ca(cfg.domain) && cfg.structure_prior == FBA_SP_FULLY_CONNECTED))
+        return fail(nullptr, FBA_EINVAL, "%s belief: needs a factored model (fbapomdp) in the expected Dirichlet mode, at most %d structure words per particle",
+                    nips ? "mh-nips" : "mh-within-gibbs", MH_MAXVAR);
+    if (nips && is_sys(cfg.domain))
+        return fail(nullptr, FBA_EINVAL, "mh-nips belief on sysadmin: MHNIPS2018::MH scores a particle's counts (grown from the domain's prior, 10000 per row) "
+                    "against computePriorModel(structure) (rows {total * p, total - p}, SysAdminFactoredPrior.cpp:98-127): a different prior, "
+                    "whose score difference admits no proposal -- the reference does not return from it");
+    if (cfg.particles < 1) return fail(nullptr, FBA_EINVAL, "%s::cannot initiate MH with size 0", name);  // MHwithinGibbs.cpp:243-246, MHNIPS2018.cpp:116-119
+    if (cfg.threshold >= 0) return fail(nullptr, FBA_EINVAL, "%s::cannot initiate with threshold >= 0 (is:%f)", name, cfg.threshold);  // :248-252, MHNIPS2018.cpp:121-126
+    P.belief = FBA_BELIEF_IMPORTANCE;
+    P.mh     = nips ? 3 : cfg.belief_option == 1 ? 2 : 1;
+    return FBA_OK;
+}
+
+// StructureIncubatorSampling(size, reinvigor_amount, threshold) (BABelief.cpp:53-58): the reinvigoration belief's two
+// rejection filters + a weighted shadow filter of bred particles; same domains (a fully connected prior is needed)
+int map_incubator(const fba_config& cfg, Problem& P)
+{
+    if (!has_fully_connected_prior(cfg))
+        return fail(nullptr, FBA_EINVAL, "incubator belief: needs a factored model (fbapomdp) of factored tiger, collision avoidance or sysadmin");
+    if (cfg.particles < 1 || cfg.resample_amount < 1)  // StructureIncubatorSampling.cpp:28-33; :35-39 below
+        return fail(nullptr, FBA_EINVAL, "StructureIncubatorSampling::Cannot initiate Incubator belief update with size < 1 (%d) or resample size < 1 (%d)",
+                    cfg.particles, cfg.resample_amount);
+    if (cfg.threshold <= 0 || cfg.threshold > 1) return fail(nullptr, FBA_EINVAL, "StructureIncubatorSampling::must initiate with 1 < threshold <= 0 (is:%f)", cfg.threshold);
+    if (cfg.resample_amount >= cfg.particles || cfg.resample_amount > 1024)  // WeightedFilter::leastLikely asserts n < size() (WeightedFilter.cpp:207)
+        return fail(nullptr, FBA_EINVAL, "incubator belief: the resample amount (%d) must be below the number of particles (%d): WeightedFilter::leastLikely",
+                    cfg.resample_amount, cfg.particles);
+    if (cfg.particles > IS_LDS_MAX_N) return fail(nullptr, FBA_EINVAL, "incubator belief: at most %d particles per slot", IS_LDS_MAX_N);
+    P.belief = FBA_BELIEF_REJECTION;
+    P.incub  = cfg.resample_amount;
+    return FBA_OK;
+}
+
+// NestedBelief(particle_amount, particle_amount^2) (BABelief.cpp:67-70): a weighted filter of count particles, each
+// with its own flat filter of domain states; the BABelief factory only, i.e. bapomdp / fbapomdp
+int map_nested(const fba_config& cfg, Problem& P)
+{
+    if (cfg.model == FBA_MODEL_POMDP) return fail(nullptr, FBA_EINVAL, "nested belief: needs a Bayes-adaptive model (bapomdp / fbapomdp)");
+    if (cfg.particles < 1)  // NestedBelief.cpp:22-27
+        return fail(nullptr, FBA_EINVAL, "NestedBelief: cannot initiate with filter size < 1 (top: %d, bottom: %d)", cfg.particles, cfg.particles * cfg.particles);
+    if (cfg.particles > 256) return fail(nullptr, FBA_EINVAL, "nested belief: at most 256 count particles (each carries particles^2 domain states)");
+    P.belief = FBA_BELIEF_IMPORTANCE;
+    P.nested = cfg.particles * cfg.particles;
+    return FBA_OK;
+}
+
+// two rejection filters + breeding (ReinvigoratingRejectionSampling.hpp)
+int map_reinvigoration(const fba_config& cfg, Problem& P)
+{
+    if (!has_fully_connected_prior(cfg))
+        return fail(nullptr, FBA_EINVAL, "reinvigoration belief: needs a factored model (fbapomdp) of factored tiger, collision avoidance or sysadmin");
+    if (cfg.particles < 1 || cfg.resample_amount < 1)  // ReinvigoratingRejectionSampling.cpp:43-49
+        return fail(nullptr, FBA_EINVAL, "ReinvigoratingRejectionSampling::cannot initiate belief of size < 1 (%d), or resample size of < 1 (%d)",
+                    cfg.particles, cfg.resample_amount);
+    P.belief  = FBA_BELIEF_REJECTION;
+    P.reinvig = cfg.resample_amount;
+    return FBA_OK;
+}
+
+// cfg.belief onto the filter that carries it (P.belief) and what it keeps beside that filter.  A point estimate is the rejection update of
+// a single state (PointEstimation.cpp:36-76 / BAPointEstimation.cpp): the configuration itself changes.
+int map_belief(fba_config& cfg, Problem& P)
+{
+    if (cfg.belief == FBA_BELIEF_POINT) { cfg.belief = FBA_BELIEF_REJECTION; cfg.particles = 1; P.point = 1; }
+    P.belief = cfg.belief;
+    switch (cfg.belief) {
+        case FBA_BELIEF_CHEATING: return map_cheating(cfg, P);
+        case FBA_BELIEF_MH_GIBBS:
+        case FBA_BELIEF_MH_NIPS: return map_mh(cfg, P);
+        case FBA_BELIEF_INCUBATOR: return map_incubator(cfg, P);
+        case FBA_BELIEF_NESTED: return map_nested(cfg, P);
+        case FBA_BELIEF_REINVIGORATION: return map_reinvigoration(cfg, P);
+        default: return FBA_OK;
+    }
+}
+
+// the domain's tables as the context keeps them on the host
+struct DomainTables { SysDesc sys{}; CADesc ca{}; GridDesc grid{}; };
+
+// the domain's sizes and tables, or the error of its constructor in the reference
+int map_domain(const fba_config& cfg, Problem& P, DomainTables& t)
+{
+    switch (cfg.domain) {
+        case FBA_DOM_TIGER_EPISODIC:
+        case FBA_DOM_TIGER_CONTINUOUS: P.S = 2; P.A = 3; P.O = 2; break;
+        case FBA_DOM_FTIGER_EPISODIC:
+        case FBA_DOM_FTIGER_CONTINUOUS:
+            if (cfg.size < 1 || cfg.size > 12) return fail(nullptr, FBA_EINVAL, "cannot initiate FactoredTiger with %d irrelevant features", cfg.size);
+            P.S = 2 << cfg.size; P.A = 3; P.O = 2;
+            break;
+        case FBA_DOM_AGR:  // AGR(10): 21 x 21 (goal, position) states, 21 help actions + work + observe, 21 positions + "none"
+            if (cfg.model != FBA_MODEL_POMDP || cfg.belief != FBA_BELIEF_REJECTION)  // AGR.cpp:307-310 (thrown by the first weighted update)
+                return fail(nullptr, FBA_EINVAL, "AGR::computeObservationProbability nyi");
+            P.S = 21 * 21; P.A = 23; P.O = 22;
+            break;
+        case FBA_DOM_COFFEE:
+        case FBA_DOM_COFFEE_BOUTILIER:  // CoffeeProblem.hpp: 5 binary features, {GetCoffee, CheckCoffee}, {Want, NotWant}
+            if (cfg.model != FBA_MODEL_POMDP)  // factory::makeBADomainExtension has no coffee entry
+                return fail(nullptr, FBA_EINVAL, "the coffee problem has no Bayes-adaptive extension: planning only");
+            P.S = 32; P.A = 2; P.O = 2;
+            break;
+        case FBA_DOM_SYSADMIN_INDEPENDENT:
+        case FBA_DOM_SYSADMIN_LINEAR:
+            if (cfg.size < 1 || cfg.size > 8)  // SysAdmin.cpp:17-21; 2N actions <= FBA_MAX_ACTIONS
+                return fail(nullptr, FBA_EINVAL, cfg.size < 1 ? "Cannot initiate Sysadmin with n %d" : "sysadmin: at most 8 computers (n = %d)", cfg.size);
+            build_sysadmin(t.sys, cfg.size);
+            P.S = 1 << cfg.size; P.A = 2 * cfg.size; P.O = 2;
+            break;
+        case FBA_DOM_COLLISION_AVOID:
+        case FBA_DOM_COLLISION_AVOID_CENTERED: {
+            const int W = cfg.width, H = cfg.height, n = cfg.size;
+            if (W < 1) return fail(nullptr, FBA_EINVAL, "Cannot initiate CollisionAvoidance with width %d", W);
+            if (H < 1 || H % 2 != 1 || H > 15) return fail(nullptr, FBA_EINVAL, "Cannot initiate CollisionAvoidance with height %d, must be uneven", H);
+            if (n > W || n < 1 || n > MAXF - 2)
+                return fail(nullptr, FBA_EINVAL, "cannot initiate collision avoidance with more obstacles (%d ) than columns (%d)!", n, W);
+            build_collision_avoidance(t.ca, W, H, n, cfg.domain == FBA_DOM_COLLISION_AVOID);
+            P.S = W * H * t.ca.Hn; P.A = 3; P.O = t.ca.Hn;
+            break;
+        }
+        case FBA_DOM_GRIDWORLD:
+            if (cfg.size < 3 || cfg.size > 15)
+                return fail(nullptr, FBA_EINVAL, "please enter a size larger than 3 to be able to run gridworld (you entered %d)", cfg.size);
+            build_gridworld(t.grid, cfg.size);
+            P.S = P.O = cfg.size * cfg.size * t.grid.G; P.A = 4;
+            break;
+        default: return fail(nullptr, FBA_EINVAL, "domain %d is not supported by this build", cfg.domain);
+    }
+    return FBA_OK;
+}
+
+// what the configuration says of the problem in so many words
+void set_problem_parameters(const fba_config& cfg, Problem& P)
+{
+    P.domain = cfg.domain; P.model = cfg.model; P.planner = cfg.planner;
+    P.N = cfg.particles; P.sims = cfg.sims; P.horizon = cfg.horizon; P.episodes = cfg.episodes;
+    P.max_depth = cfg.max_depth < 0 ? cfg.horizon : cfg.max_depth;  // ArgumentParser.cpp:37-40
+    P.exploration = cfg.exploration; P.gamma = cfg.discount;
+    P.seed_lo = (uint32_t)cfg.seed; P.seed_hi = (uint32_t)(cfg.seed >> 32);
+    P.noise = cfg.noise; P.counts_total = cfg.counts_total; P.structure_prior = cfg.structure_prior;
+    P.dirichlet_regular = cfg.dirichlet_regular ? 1 : 0;
+}
+
+// ---- the context exists from here on
+// the length of a particle's count table and, for a factored model, its built-in prior and description; then the two limits of every model
+int build_model(fba_ctx* c)
+{
+    const fba_config& cfg = c->cfg;
+    Problem& P = c->P;
+    if (cfg.model == FBA_MODEL_BA_TABLE) {
+        P.phi_len = P.S * P.A * P.S;
+        P.C       = P.phi_len + P.A * P.S * P.O;
+    } else if (cfg.model == FBA_MODEL_BA_FACTORED) {
+        TRY(build_factored_prior(c));
+        P.C = c->fdesc.ncounts + c->fdesc.nvar;
+    } else if (cfg.model != FBA_MODEL_POMDP) return fail(c, FBA_EINVAL, "model %d is not supported by this build", cfg.model);
+    c->dense_C = P.C;
+    if (P.A > FBA_MAX_ACTIONS) return fail(c, FBA_EINVAL, "more than %d actions", FBA_MAX_ACTIONS);
+    if (cfg.belief == FBA_BELIEF_IMPORTANCE && P.N > (1 << 26)) return fail(c, FBA_EINVAL, "importance sampling supports at most %d particles per slot", 1 << 26);
+    return FBA_OK;
+}
+
+// ---- stage 3: the particle record format (fba_state.h): dense fp32 counts unless one of the four below applies
+long long run_steps(const fba_config& cfg) { return (long long)cfg.episodes * cfg.horizon; }   // the most belief updates of one run
+
+// the most 64-byte buckets whose keys fit 28 bits: (buckets * 4 + 3) * O + O - 1 < 2^28 (the root's "bucket" is index `buckets`)
+long long tree_bucket_fit(const Problem& P) { return (1ll << 28) / (4ll * P.O) - 2; }
+
+// the search of a history-particle context is the bucket-tree one (search_hist2_kernel, search_tabhist_kernel) and its keys fit: po-uct or
+// random, at most 65536 simulations, no records tree, a table of the default size or an explicit one within the fit
+bool bucket_tree_search(const fba_config& cfg, const CreateSwitches& sw, const Problem& P)
+{
+    return (cfg.planner == FBA_PLANNER_POUCT || cfg.planner == FBA_PLANNER_RANDOM) && cfg.sims <= 65536 && !sw.tree_records &&
+           (cfg.tree_buckets <= 0 || (long long)cfg.tree_buckets <= tree_bucket_fit(P));
+}
+
+// Packed particles (PackedView, fba_device.h): the tabular tiger particle as 24 uint16 increment counts over
+// the shared prior -- 64 bytes instead of 128 in every belief update and every root sample.  Only where every
+// kernel that touches the records is a tiger-table instantiation (launch_search / launch_belief_update), the
+// prior is exact under "+ 65535" (TigerBAPrior: 5000, 0 and the two listen counts below) and one run cannot
+// add more than 65535 to a cell (one T and one O increment per real step).
+void try_packed_tiger(fba_ctx* c, const CreateSwitches& sw)
+{
+    const fba_config& cfg = c->cfg;
+    if (!(cfg.model == FBA_MODEL_BA_TABLE && is_tiger(cfg.domain) && !cfg.dirichlet_regular && cfg.planner == FBA_PLANNER_POUCT &&
+          (cfg.belief == FBA_BELIEF_REJECTION || cfg.belief == FBA_BELIEF_IMPORTANCE) && cfg.particles <= IS_MAX_CHUNKS * 256 &&
+          !sw.is_multi_min_set && !sw.dense_particles && run_steps(cfg) <= 65535 && cfg.noise > -.15 && cfg.noise <= .3))
+        return;
+    if (!packable_prior({(.85f - cfg.noise) * cfg.counts_total, (.15f + cfg.noise) * cfg.counts_total, 5000.f, 0.f})) return;
+    c->P.packed = 1;
+    c->P.C      = (c->dense_C + 1) / 2;  // words holding the uint16 pairs; the state word follows
+}
+
+// Packed factored-tiger particles (PackedFtigerView, fba_device.h): uint16 increments over a prior that is a function of
+// the cell and the particle's structure bits -- 144 B instead of 288 B at --size 3, so twice the beliefs per gigabyte and
+// per kilobyte of LDS.  Only where every kernel that touches the records is a factored-tiger instantiation (po-uct,
+// plain rejection filter, expected Dirichlet, --size 1..3) and the prior's five values are exact under "+ 65535".
+void try_packed_ftiger(fba_ctx* c, const CreateSwitches& sw)
+{
+    const fba_config& cfg = c->cfg;
+    Problem& P = c->P;
+    if (!(cfg.model == FBA_MODEL_BA_FACTORED && is_ftiger(cfg.domain) && cfg.belief == FBA_BELIEF_REJECTION && !P.point &&
+          cfg.planner == FBA_PLANNER_POUCT && !cfg.dirichlet_regular && cfg.size >= 1 && cfg.size <= 3 && !sw.dense_particles &&
+          run_steps(cfg) <= 65535))
+        return;
+    const float acc = (.85f - cfg.noise) * cfg.counts_total, inacc = (.15f + cfg.noise) * cfg.counts_total, unif = .5f * cfg.counts_total;
+    if (!packable_prior({acc, inacc, unif, 5000.f, 0.f})) return;
+    P.ft_packed = 1;
+    P.ft_acc = acc; P.ft_inacc = inacc; P.ft_unif = unif;
+    P.C = c->fdesc.ncounts / 2 + 1;   // words of uint16 pairs, the structure word; the state word follows
+}
+
+// History particles (fba_device.h): the gridworld FBA-POMDP particle as one 4-byte entry per real step over the
+// shared prior tables -- 100-500 bytes instead of 191 KB (N = 7) -- where the importance filter is the plain one,
+// the run fits the record (one entry per belief update), the grid fits 3-bit coordinates and prior + j is exact in
+// fp32 for every count a run can reach (so a row read through the entries is bit for bit the dense row).
+// The plain rejection filter (reject_hist_kernel) stores them too where its search is the bucket-tree one (hist2_flat_search,
+// bucket_tree_search above -- the flat root sample exists there only); ts and the rest stay dense.
+// The tabular gridworld BA-POMDP stores them too (P.hist = 2: entries of state indices over the prior's sparse rows, 176 B instead of
+// 7.68 MB at N = 7) under the same filters, where its search is the bucket-tree one (search_tabhist_kernel); ts and the rest stay dense.
+void try_gridworld_history(fba_ctx* c, const CreateSwitches& sw)
+{
+    const fba_config& cfg = c->cfg;
+    Problem& P = c->P;
+    const bool bucket_tree = bucket_tree_search(cfg, sw, P);
+    const bool flat     = cfg.belief == FBA_BELIEF_REJECTION && !P.point && bucket_tree;
+    const bool weighted = cfg.belief == FBA_BELIEF_IMPORTANCE && cfg.particles <= IS_MAX_CHUNKS * 256 && !sw.is_multi_min_set;
+    const bool tabular  = cfg.model == FBA_MODEL_BA_TABLE && bucket_tree;
+    if (!((cfg.model == FBA_MODEL_BA_FACTORED || tabular) && cfg.domain == FBA_DOM_GRIDWORLD && (weighted || flat) && !cfg.dirichlet_regular &&
+          !sw.dense_particles && run_steps(cfg) <= HIST_MAX_CAP && cfg.size <= HIST_MAX_N))
+        return;
+    const int cap = cfg.episodes * cfg.horizon;
+    if (tabular) {
+        if (build_tabular_prior(c) != FBA_OK || !increments_exact(c->prior, cap + 1)) return;   // (built again by make_context, as for every tabular context)
+    } else {
+        build_gridworld_alt_prior(c);
+        const std::vector<float> counts(c->prior.begin(), c->prior.begin() + c->fdesc.ncounts);
+        if (!increments_exact(counts, cap + 1) || !increments_exact(c->prior_alt, cap + 1)) return;
+    }
+    P.hist     = tabular ? 2 : 1;
+    P.hist_cap = cap;
+    P.hist_row = std::max(c->gdesc.N, c->gdesc.G);
+    P.gw_N = c->gdesc.N; P.gw_G = c->gdesc.G;
+    uint32_t cells[4] = {0, 0, 0, 0};
+    for (int gq = 0; gq < c->gdesc.G; ++gq)
+        cells[gq >> 2] |= (uint32_t)(c->gdesc.goal[gq][0] * c->gdesc.N + c->gdesc.goal[gq][1]) << (8 * (gq & 3));
+    P.gw_goalcell0 = cells[0]; P.gw_goalcell1 = cells[1]; P.gw_goalcell2 = cells[2]; P.gw_goalcell3 = cells[3];
+    P.C        = 0;  // word 0 = state, word 1 = structure bits, words 2.. = entries
+}
+
+// The collision-avoidance FBA-POMDP in the prior's own graph (no structure prior: ca_fact_step's contexts) stores them too under the plain
+// importance filter where that filter is the multi-launch one (P.hist = 3: entries of 12 + 9n bits, the whole prior in LDS -- 328 B instead of
+// 3.5 KB at 7 x 7 with two obstacles and 80 steps), where the planner is po-uct or random, the grid fits 3-bit fields (W, H <= 8, n <= 2), the
+// run fits the record and the search's LDS (tables, path, one staged record per lane) fits a workgroup.  The prior need not be exact under
+// "+ j": cells that are not read their count from a table of sequential sums (ca_hist_sequences), at most CA_HIST_MAX_SEQ distinct values;
+// other priors stay dense.  Their update exists as the multi-launch filter only (is_multi_ca_step_kernel and the launches behind it), so the
+// format is used exactly where the dense records take that filter too (D.is_multi, plan_filters: from CreateSwitches::is_multi_min particles
+// up).  Up to 65 536 particles the records stay dense on the one-launch importance_kernel, as before.
+void try_collision_avoidance_history(fba_ctx* c, const CreateSwitches& sw)
+{
+    const fba_config& cfg = c->cfg;
+    Problem& P = c->P;
+    if (!(cfg.model == FBA_MODEL_BA_FACTORED && is_ca(cfg.domain) && cfg.belief == FBA_BELIEF_IMPORTANCE && !P.point && cfg.particles >= sw.is_multi_min &&
+          (cfg.planner == FBA_PLANNER_POUCT || cfg.planner == FBA_PLANNER_RANDOM) && !cfg.dirichlet_regular && !sw.dense_particles &&
+          c->fdesc.nvar == 0 && c->fdesc.nodes[2].nmax == 1 && !P.nested && !P.mh && !P.cheat && !P.incub && !P.reinvig &&
+          run_steps(cfg) <= HIST_MAX_CAP && run_steps(cfg) >= 1 &&
+          c->cadesc.W <= 8 && c->cadesc.H <= 8 && c->cadesc.n >= 1 && c->cadesc.n <= 2 && P.A == 3))
+        return;
+    const int cap = cfg.episodes * cfg.horizon, nc = c->fdesc.ncounts;
+    std::vector<uint8_t> sid;
+    std::vector<float> seq;
+    Problem Q = P;
+    Q.hist_row = nc; Q.hist_rid_bytes = (nc + 15) & ~15; Q.hist_distinct = CA_HIST_MAX_SEQ; Q.hist_cap = cap; Q.Cs = (2 + cap + 3) & ~3;
+    if (!(nc == ca_hist_ncounts(P.A, c->cadesc.W, c->cadesc.H, c->cadesc.n) && ca_hist_sequences(c->prior, nc, cap + 1, sid, seq) &&
+          ca_hist_search_lds(Q) <= 64 * 1024))
+        return;
+    P.hist     = 3;
+    P.hist_cap = cap;
+    P.hist_row = nc;   // (for these records: the cells of the prior table)
+    P.gw_N = 1; P.gw_G = 1;   // (init_kernel / reset_kernel pack the state into word 1 with these; nothing reads that word here)
+    P.C        = 0;    // word 0 = state, word 1 unused, words 2.. = entries
+}
+
+// the record format and, with it, the words of a record and its stride
+void choose_record_format(fba_ctx* c, const CreateSwitches& sw)
+{
+    Problem& P = c->P;
+    try_packed_tiger(c, sw);
+    try_packed_ftiger(c, sw);
+    try_gridworld_history(c, sw);
+    try_collision_avoidance_history(c, sw);
+    P.hist_compact = P.hist && !sw.stride_full ? 1 : 0;   // (A/B switch: every record at the full stride)
+    // record stride (fba_state.h): counts + state word, padded to a power of two up to 64 words
+    // (so small particles are whole cache lines), to a multiple of 4 words beyond that
+    if (P.hist) P.Cs = (2 + P.hist_cap + 3) & ~3;
+    else if (P.ft_packed) P.Cs = (P.C + 1 + 3) & ~3;   // 36 words at --size 3: the point is the bytes, not a power of two
+    else {
+        int need = P.C + 1, cs = 4;
+        if (need <= 64) { while (cs < need) cs <<= 1; }
+        else cs = (need + 3) & ~3;
+        P.Cs = cs;
+    }
+}
+
+// ---- stage 4: the search tree's layout and what one slot takes
+struct TreePlan {
+    bool hashed = false;                   // children through a hash table, not a dense child array per node
+    uint32_t hcap = 0;                     // ... of this many entries of hash_entry bytes (0: none)
+    size_t hash_entry = 16, bkt_lines = 0; // bkt_lines: the bucket tree's 128-byte lines (0: node records)
+    size_t per_slot = 0;                   // bytes of one slot, for the slot count of slots = 0
+};
+
+int plan_tree(fba_ctx* c, const CreateSwitches& sw, TreePlan& t)
+{
+    const fba_config& cfg = c->cfg;
+    Problem& P = c->P;
+    DeviceState& D = c->D;
+    // node record layout (fba_state.h)
+    t.hashed = P.A * P.O > 64;
+    // a hashed tree with an even number of actions drops the visits word (it is the sum of the action counts) and the
+    // padding word with it: 56 -> 48 bytes per node for the four actions of gridworld
+    D.cn_off     = (t.hashed && P.A % 2 == 0 && !sw.node_visits) ? 0 : 1;
+    D.cq_off     = (D.cn_off + P.A + 1) & ~1;
+    D.child_off  = D.cq_off + 2 * P.A;
+    D.node_words = std::max(t.hashed ? D.child_off : ((D.child_off + P.A * P.O + 1) & ~1), sw.node_words);
+    D.max_nodes  = P.sims + 2;  // one new node per simulation at most
+    // Episodic (factored) tiger: only `listen` continues an episode and it has two observations, so a node has at most
+    // two children and the tree of a search of depth D is at most the complete binary tree with levels 0..D:
+    // 2^(D+1) - 1 nodes, whatever the number of simulations (2047 at the default depth 10 against 4098 / 16386
+    // records for 4096 / 16384 simulations).  search_kernel refuses to go past max_nodes (fault -> FBA_ESTATE).
+    if ((cfg.domain == FBA_DOM_TIGER_EPISODIC || cfg.domain == FBA_DOM_FTIGER_EPISODIC) && P.max_depth >= 0 && P.max_depth < 24)
+        D.max_nodes = std::min(D.max_nodes, (1 << (P.max_depth + 1)) + 1);  // (+1: odd, so that the slots' trees are not a power of two
+                                                                             // of bytes apart -- at exactly 128 KB the search ran 45 % slower)
+    if (sw.node_bound) D.max_nodes = sw.node_bound;
+    if (t.hashed) {
+        t.hcap = 64;
+        while (t.hcap < 2u * (uint32_t)(D.max_nodes - 2)) t.hcap <<= 1;  // at most max_nodes - 2 children (one per simulation): load <= 1/2
+        D.hmask = t.hcap - 1;
+        if ((unsigned long long)D.max_nodes * P.A * P.O < (1ull << 27) && !sw.wide_hash) {
+            D.hash_compact = 1;
+            t.hash_entry   = 8;
+        }
+    }
+    // History-particle searches keep their tree in one table of 64-byte buckets (search_hist2_kernel, fba_state.h) where its keys fit:
+    // (parent bucket, action, observation) in 28 bits, counts below the root in 16.  FBA_HIST_TREE=records keeps node records + hash table
+    // (search_hist_kernel), for A/B runs and for what does not fit.
+    const bool bucket_records = P.hist && P.hist != 3 && !sw.tree_records;   // (collision-avoidance records: search_kernel's node records)
+    if (bucket_records && P.sims <= 65536) {
+        const long long buckets = std::max(cfg.tree_buckets > 0 ? (long long)cfg.tree_buckets : 2ll * (P.sims + 2), 8ll);
+        const long long fit     = tree_bucket_fit(P);
+        if (cfg.tree_buckets <= 0 || buckets <= fit) t.bkt_lines = (size_t)((std::min(buckets, fit) + 1) / 2);
+    }
+    if (cfg.tree_buckets < 0 || (cfg.tree_buckets > 0 && !t.bkt_lines && bucket_records))
+        return fail(c, FBA_EINVAL, "tree_buckets = %d: not a size this context's search can use (history-particle searches of at most 65536 "
+                    "simulations, keys of 28 bits)", cfg.tree_buckets);
+    if (t.bkt_lines) {   // no node records, no separate hash table
+        D.max_nodes = P.sims + 2;
+        t.hcap = 0;
+    }
+    P.search_budget = (P.hist && P.hist != 3 && cfg.search_budget > 0) ? cfg.search_budget : 0;   // (only search_hist_kernel parks and resumes)
+    // (per particle: two weights, a prefix sum and a side row, which a plain rejection filter of history records does not have, + its records)
+    const size_t per_particle_aux = (P.hist && P.belief == FBA_BELIEF_REJECTION) ? 0 : (size_t)(2 * 8 + 8 + 4 * (MAXINC + 1));
+    t.per_slot = (size_t)P.N * (per_particle_aux + ((P.reinvig || P.cheat) ? 4 : (P.incub ? 6 : (P.hist ? 1 : 2))) * (size_t)P.Cs * 4) +
+                 (t.bkt_lines ? t.bkt_lines * 128 : (size_t)D.max_nodes * D.node_words * 4 + (size_t)t.hcap * t.hash_entry) + 1024;
+    return FBA_OK;
+}
+
+// slots = 0: as many slots as half the free device memory holds (`budget` bytes), at most 32768 and no more than there are runs
+int slot_count(const fba_config& cfg, const TreePlan& t, size_t budget)
+{
+    if (cfg.slots > 0) return cfg.slots;
+    return std::min((int)std::min<size_t>(std::max<size_t>(budget / t.per_slot, 1), 32768), cfg.runs);
+}
+
+bool weighted_filters(const Problem& P) { return P.belief == FBA_BELIEF_IMPORTANCE || P.incub; }   // (the incubator's shadow filter is importance-sampled)
+
+// how the filters are kept and updated, and the limits of the composite beliefs that follow from it
+int plan_filters(fba_ctx* c, const CreateSwitches& sw)
+{
+    const Problem& P = c->P;
+    DeviceState& D = c->D;
+    // history particles keep ONE record buffer per slot; a resample / reset builds the new filter in a scratch pool shared by a
+    // chunk of slots (launch_belief_update / launch_reset: for_each_chunk) -- the second buffer was a quarter of a slot's memory
+    D.single_rec      = P.hist && !sw.double_buffer ? 1 : 0;
+    D.ab_rows_hbm = sw.rows_hbm ? 1 : 0; D.ab_hist_multi = sw.hist_multi; D.ab_no_etiger = sw.no_etiger ? 1 : 0; D.ab_tiger_gather = sw.tiger_gather ? 1 : 0;
+    D.ab_lockstep = sw.hist_lockstep ? 1 : 0;   // (on; only the bucket tree has it: alloc_tree)
+    D.side_w = 1 + (P.model == FBA_MODEL_BA_FACTORED ? c->fdesc.FS + c->fdesc.FO : (P.model == FBA_MODEL_BA_TABLE ? 2 : 0));
+    if (P.hist) D.side_w = 2;  // {new state, the step's entry}
+    D.is_multi    = weighted_filters(P) && P.N >= sw.is_multi_min;
+    D.ctot_stride = (P.N + 255) / 256 + 2;
+    if (P.mh) {
+        if (D.is_multi) return fail(c, FBA_EINVAL, "mh-within-gibbs belief: at most %d particles per slot", IS_MAX_CHUNKS * 256);
+        if (c->fdesc.nvar > MH_MAXVAR) return fail(c, FBA_EINVAL, "mh beliefs: at most %d structure words per particle", MH_MAXVAR);
+        size_t words = (size_t)3 * P.Cs + (size_t)P.S * P.A * P.S + (size_t)P.A * P.S * P.O + 2;
+        words += 2 * ((size_t)(P.horizon + 1) * P.S + P.S) + (size_t)P.episodes * (P.horizon + 1) + 2 * (size_t)P.horizon + 2;
+        D.mh_scratch_words = (int32_t)((words + 3) & ~(size_t)3);
+    }
+    if (P.cheat && D.is_multi) return fail(c, FBA_EINVAL, "cheating-reinvigoration belief: at most %d particles per slot", IS_MAX_CHUNKS * 256);
+    return FBA_OK;
+}
+
+// ---- stage 5: the device buffers, grouped as the data is, and the uploads
+template <typename... T>
+int alloc_each(fba_ctx* c, size_t n, T**... p)   // n zeroed elements for every one of the pointers
+{
+    int rc = FBA_OK;
+    ((rc = rc ? rc : dev_alloc(c, p, n)), ...);
+    return rc;
+}
+
+// per slot: where its run stands and what its last step was (slot bookkeeping), then its counters; the context's single words
+int alloc_slot_state(fba_ctx* c)
+{
+    DeviceState& D = c->D;
+    const size_t E = (size_t)c->P.E;
+    TRY(alloc_each(c, E, &D.run, &D.episode, &D.t, &D.active, &D.need_update, &D.need_reset, &D.need_init, &D.adv, &D.env_state, &D.ret, &D.disc,
+                   &D.action, &D.obs, &D.bufsel, &D.cur, &D.lazy_reset));
+    TRY(alloc_each(c, E, &D.sim_steps, &D.belief_steps, &D.env_steps, &D.upd_particles, &D.upd_attempts, &D.upd_entries));
+    TRY(dev_alloc(c, &D.ep_sums, 3 * E));
+    TRY(alloc_each(c, 1, &D.trace_count, &c->d_n_active, &D.fault));
+    D.trace_on   = c->cfg.trace ? 1 : 0;
+    D.runs_total = c->cfg.runs;
+    D.run_offset = c->cfg.run_offset;
+    return FBA_OK;
+}
+
+int alloc_filters(fba_ctx* c, const CreateSwitches& sw)
+{
+    const Problem& P = c->P;
+    DeviceState& D = c->D;
+    const int E = P.E;
+    const bool is = weighted_filters(P);
+    TRY(dev_alloc(c, &D.p_weight, is ? (size_t)2 * E * P.N : 1));
+    if (D.single_rec) D.scratch_slots = sw.scratch_slots ? std::min(E, sw.scratch_slots) : std::min(E, 1024);
+    // (zeroed: a slot whose belief was never initiated -- a slot of fba_run_bapomdp beyond the configured runs -- then holds all-zero records and weights, which is
+    // what fba_belief_export writes for it and a block fba_belief_import takes in every record format; nothing else reads such a slot)
+    TRY(dev_alloc(c, &D.p_rec, (D.single_rec ? (size_t)E + D.scratch_slots : (size_t)2 * E) * P.N * P.Cs, true));
+    if (D.single_rec) {   // E + scratch_slots buffers; a slot's filter and a scratch place's buffer change places after a resample / reset (swap_buffers_kernel)
+        TRY(dev_alloc(c, &D.rec_buf, (size_t)E + D.scratch_slots));
+        std::vector<int32_t> ids((size_t)E + D.scratch_slots);
+        for (size_t i = 0; i < ids.size(); ++i) ids[i] = (int32_t)i;
+        HIPCHK(c, hipMemcpy(D.rec_buf, ids.data(), ids.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        TRY(dev_alloc(c, &D.copy_pending, E));
+    }
+    TRY(dev_alloc(c, &D.wscan, is ? (size_t)E * P.N : 1, false));
+    TRY(dev_alloc(c, &D.hist_cnt, E));
+    TRY(dev_alloc(c, &D.p_side, is ? (size_t)E * P.N * D.side_w : 1, false));
+    TRY(dev_alloc(c, &D.ctot, is ? (size_t)E * D.ctot_stride : 1));
+    TRY(dev_alloc(c, &D.is_tot, (size_t)2 * E));
+    return FBA_OK;
+}
+
+// Which shadow particles the incubator breeds anew: the reference asks its weighted filter for the `n` least likely particles
+// (WeightedFilter.cpp:193-238) at a moment when all N weights are equal, so no particle ever displaces one of the first `n`
+// and the answer is those indices in the order a binary max-heap of equal keys releases them.  That order is libstdc++'s
+// (std::push_heap / std::pop_heap, which its priority_queue is made of); it is computed here once, with a comparison that
+// finds no key smaller than another.
+std::vector<int32_t> incubator_breeding_order(int n)
+{
+    std::vector<int32_t> heap, order;
+    const auto equal_keys = [](int32_t, int32_t) { return false; };
+    for (int i = 0; i < n; ++i) { heap.push_back(i); std::push_heap(heap.begin(), heap.end(), equal_keys); }
+    for (; !heap.empty(); heap.pop_back()) { std::pop_heap(heap.begin(), heap.end(), equal_keys); order.push_back(heap.back()); }
+    return order;
+}
+
+// what the composite beliefs keep beside the main filter: fully connected and shadow filters, nested states, the MH chains, the likelihood
+int alloc_composite(fba_ctx* c)
+{
+    const Problem& P = c->P;
+    DeviceState& D = c->D;
+    const int E = P.E;
+    if (P.reinvig || P.cheat || P.incub) {
+        TRY(dev_alloc(c, &D.p_rec_fc, (size_t)2 * E * P.N * P.Cs, false));
+        TRY(dev_alloc(c, &D.bufsel_fc, E));
+    }
+    if (P.incub) {
+        TRY(dev_alloc(c, &D.p_rec_sh, (size_t)2 * E * P.N * P.Cs, false));
+        TRY(dev_alloc(c, &D.p_weight_sh, (size_t)2 * E * P.N));
+        TRY(alloc_each(c, E, &D.bufsel_sh, &D.need_update_sh));
+        const std::vector<int32_t> order = incubator_breeding_order(P.incub);
+        int32_t* d_order = nullptr;
+        TRY(dev_alloc(c, &d_order, order.size()));
+        HIPCHK(c, hipMemcpy(d_order, order.data(), order.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        D.inc_order = d_order;
+    }
+    if (P.nested) {
+        TRY(dev_alloc(c, &D.nest_s, (size_t)2 * E * P.N * P.nested));
+        TRY(dev_alloc(c, &D.nest_scan, (size_t)E * P.N));
+        TRY(alloc_each(c, E, &D.nest_sel, &D.nest_total));
+    }
+    if (P.mh || P.cheat) {   // the log likelihood per slot, and the threshold behind them
+        TRY(dev_alloc(c, &D.lik, (size_t)E + 1));
+        TRY(dev_alloc(c, &D.cheat_pending, E));
+        const double thr = c->cfg.threshold;
+        HIPCHK(c, hipMemcpy(D.lik + E, &thr, sizeof thr, hipMemcpyHostToDevice));
+    }
+    if (P.mh) {
+        const size_t cap = (size_t)P.episodes * P.horizon;
+        TRY(alloc_each(c, (size_t)E * cap, &D.mh_a, &D.mh_o));
+        TRY(dev_alloc(c, &D.mh_ep_len, (size_t)E * (P.episodes + 1)));
+        TRY(dev_alloc(c, &D.mh_n_ep, E));
+        if (!mh_scratch_in_lds(D.mh_scratch_words)) TRY(dev_alloc(c, &D.mh_scratch, (size_t)E * D.mh_scratch_words));  // (else the chain's scratch is LDS)
+    }
+    return FBA_OK;
+}
+
+// the search's memory: the tree, the launch order of lock-step waves, the lists of budgeted searches (search_budget > 0)
+int alloc_tree(fba_ctx* c, const TreePlan& t)
+{
+    DeviceState& D = c->D;
+    const size_t E = (size_t)c->P.E;
+    if (t.bkt_lines) {
+        D.bkt_lines = (int32_t)t.bkt_lines;
+        TRY(dev_alloc(c, &D.bkt, E * t.bkt_lines * 8));   // (zeroed: key 0 carries epoch 0, which no search uses)
+        TRY(dev_alloc(c, &D.epoch, E));
+        TRY(dev_alloc(c, &D.nodes, 16));
+    } else {
+        TRY(dev_alloc(c, &D.nodes, E * D.max_nodes * D.node_words, false));
+        if (t.hashed) {
+            TRY(dev_alloc(c, &D.hash, E * t.hcap * t.hash_entry / 16));
+            TRY(dev_alloc(c, &D.epoch, E));
+        }
+    }
+    if (D.bkt && D.ab_lockstep) TRY(dev_alloc(c, &D.search_order, E));
+    if (!D.search_order) D.ab_lockstep = 0;   // (lock-step waves exist on the bucket tree only: search_hist2_kernel)
+    if (c->P.search_budget <= 0) return FBA_OK;
+    // budgeted searches: where a parked search stands
+    TRY(alloc_each(c, E, &D.s_sim, &D.s_nodes, &D.s_depth, &D.search_done));
+    if (D.bkt) TRY(dev_alloc(c, &D.s_root, 6 * E));
+    if (D.single_rec) {   // the chunked belief launches run over compacted lists of the slots that have work (fba_state.h)
+        TRY(alloc_each(c, E, &D.slot_list, &D.scratch_idx));
+        TRY(dev_alloc(c, &D.list_count, 1));
+        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&D.list_count_host), sizeof(int32_t), hipHostMallocDefault));
+    }
+    return FBA_OK;
+}
+
+// log1p(m) table: UCB(m, n) = u * sqrt(log1p(m) / n)  (POUCT.cpp:330-338, factorised so the
+// n x n table -- 134 MB at 4096 simulations, int overflow at 65536 -- never exists)
+std::vector<double> log1p_table(int sims)
+{
+    std::vector<double> t((size_t)sims + 2);
+    for (size_t m = 0; m < t.size(); ++m) t[m] = std::log1p((double)m);
+    return t;
+}
+
+// the prior buffers, the tables every search and filter reads, and the uniform weights' prefix sums (D.uni_total)
+int alloc_tables(fba_ctx* c)
+{
+    Problem& P = c->P;
+    DeviceState& D = c->D;
+    TRY(dev_alloc(c, &c->d_prior, P.Cs));
+    TRY(dev_alloc(c, &c->d_prior_dense, std::max(c->dense_C, 1) + 4));   // (+4: staged in 16-byte pieces)
+    if (P.hist == 1) {
+        const HistLayout L(c->gdesc.N, c->gdesc.G, P.A);
+        TRY(dev_alloc(c, &c->d_hist_base, (size_t)L.total + 16));   // (+16: a row fetch may run up to a row width past the last row)
+        TRY(dev_alloc(c, &c->d_hist_alt, (size_t)L.alt_total + 16));
+        TRY(dev_alloc(c, &c->d_hist_lds, (size_t)HistRowIds(c->gdesc.N, c->gdesc.G, P.A).total + 16 + 256 * 16 * sizeof(float)));
+        P.hist_base = c->d_hist_base; P.hist_alt = c->d_hist_alt;
+    }
+    if (P.hist == 3) TRY(dev_alloc(c, &c->d_hist_lds, (size_t)((P.hist_row + 15) & ~15) + (size_t)CA_HIST_MAX_SEQ * (P.hist_cap + 2) * sizeof(float) + 16));
+    TRY(dev_alloc(c, &c->d_uni_scan, (size_t)P.N + 1));
+    TRY(dev_alloc(c, &c->d_log1p, (size_t)P.sims + 2));
+    D.prior = c->d_prior; D.prior_dense = c->d_prior_dense;
+    D.uni_scan = c->d_uni_scan; D.log1p_tab = c->d_log1p;
+    const std::vector<double> t = log1p_table(P.sims);
+    HIPCHK(c, hipMemcpyAsync(c->d_log1p, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (weighted_filters(P)) {
+        double* tmp = nullptr;
+        TRY(dev_alloc(c, &tmp, (size_t)P.N + 1));
+        launch_uniform_scan(P.N, tmp, c->d_uni_scan, c->d_uni_scan + P.N, D.ctot, c->stream);
+        HIPCHK(c, hipMemcpyAsync(&D.uni_total, c->d_uni_scan + P.N, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return FBA_OK;
+}
+
+// reinvigorateBelief (StructureIncubatorSampling.cpp:155-188) tests normalised shadow weights that are uniform
+// whenever it runs (every update ends in a resample): none is promoted, or all of them -- and then every
+// shadow weight is zero and normalize() divides by their sum.  (D.uni_total is the device's sum: alloc_tables)
+int check_incubator_threshold(fba_ctx* c)
+{
+    const Problem& P = c->P;
+    if (P.incub && (1.0 / (double)P.N) / c->D.uni_total > c->cfg.threshold)
+        return fail(c, FBA_EINVAL, "incubator belief: with threshold %g every one of the %d shadow particles (normalised weight %g) is promoted at "
+                    "once; the shadow filter's total weight is then zero and StructureIncubatorSampling.cpp:160-188 divides by it",
+                    c->cfg.threshold, P.N, (1.0 / (double)P.N) / c->D.uni_total);
+    return FBA_OK;
+}
+
+// the regular Dirichlet mode: its two refusals, and the ziggurat tables of its normal draws
+int upload_regular_dirichlet(fba_ctx* c)
+{
+    Problem& P = c->P;
+    if (!P.dirichlet_regular) return FBA_OK;
+    if (P.model == FBA_MODEL_POMDP) return fail(c, FBA_EINVAL, "the Dirichlet sampling method only exists for Bayes-adaptive models");
+    int longest = std::max(P.S, P.O);
+    if (P.model == FBA_MODEL_BA_FACTORED) {
+        longest = 0;
+        for (int f = 0; f < c->fdesc.FS; ++f) longest = std::max(longest, c->fdesc.Ssz[f]);
+        for (int f = 0; f < c->fdesc.FO; ++f) longest = std::max(longest, c->fdesc.Osz[f]);
+    }
+    if (longest > MAXROW) return fail(c, FBA_EINVAL, "regular Dirichlet mode samples rows of at most %d counts (this model has %d)", MAXROW, longest);
+    ZigDesc z; build_ziggurat(z);
+    TRY(dev_alloc(c, &c->d_zig, 1));
+    HIPCHK(c, hipMemcpyAsync(c->d_zig, &z, sizeof z, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    P.zig = c->d_zig;
+    return FBA_OK;
+}
+
+template <typename T>
+int upload_desc(fba_ctx* c, T** dev, const T& host)   // (the host copy lives in the context: the copy may complete later)
+{
+    TRY(dev_alloc(c, dev, 1));
+    HIPCHK(c, hipMemcpyAsync(*dev, &host, sizeof(T), hipMemcpyHostToDevice, c->stream));
+    return FBA_OK;
+}
+
+// the descriptions of the domain and the factored model, the prior, and the default positions of the per-step interface
+int upload_model(fba_ctx* c)
+{
+    const fba_config& cfg = c->cfg;
+    Problem& P = c->P;
+    if (is_ca(cfg.domain)) { TRY(upload_desc(c, &c->d_cadesc, c->cadesc)); P.ca = c->d_cadesc; }
+    if (is_sys(cfg.domain)) { TRY(upload_desc(c, &c->d_sysdesc, c->sysdesc)); P.sys = c->d_sysdesc; }
+    if (cfg.domain == FBA_DOM_GRIDWORLD) { TRY(upload_desc(c, &c->d_gdesc, c->gdesc)); P.gw = c->d_gdesc; }
+    if (cfg.model == FBA_MODEL_BA_FACTORED) {
+        FDesc& fdh = c->fdesc;
+        const int nnodes = P.A * (fdh.FS + fdh.FO);
+        for (int k = 0; k < nnodes; ++k)
+            for (int j = 0; j < fdh.nodes[k].nmax; ++j) fdh.nodes[k].psz[j] = (uint8_t)fdh.Ssz[fdh.nodes[k].maxp[j]];
+        P.fd_bytes = (int32_t)(offsetof(FDesc, nodes) + (size_t)nnodes * sizeof(FNode));
+        P.ca_plain = (is_ca(cfg.domain) && fdh.nvar == 0 && fdh.nodes[2].nmax == 1) ||  // correct graph, no masks (not fully-connected)
+                     (is_sys(cfg.domain) && fdh.nvar == 0);
+        TRY(upload_desc(c, &c->d_fdesc, c->fdesc));
+        P.fd = c->d_fdesc;
+    }
+    TRY(upload_prior(c));
+    // default positions for the per-step interface: slot e is run run_offset + e
+    std::vector<int32_t> run((size_t)P.E);
+    for (int e = 0; e < P.E; ++e) run[e] = cfg.run_offset + e;
+    HIPCHK(c, hipMemcpyAsync(c->D.run, run.data(), run.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->D.active, 1, (size_t)P.E, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return FBA_OK;
+}
+
+// everything fba_create does once the context exists; on a refusal the context holds the message and the caller destroys it
+int make_context(fba_ctx* c, const CreateSwitches& sw)
+{
+    TreePlan tree;
+    TRY(build_model(c));
+    choose_record_format(c, sw);
+    TRY(plan_tree(c, sw, tree));
+    TRY(plan_filters(c, sw));
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    HIPCHK(c, hipStreamCreate(&c->stream));
+    size_t free_b = 0, total_b = 0;
+    if (c->cfg.slots <= 0) HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+    c->P.E = slot_count(c->cfg, tree, free_b / 2);
+    TRY(alloc_slot_state(c));
+    TRY(alloc_filters(c, sw));
+    TRY(alloc_composite(c));
+    TRY(alloc_tree(c, tree));
+    TRY(alloc_tables(c));
+    TRY(check_incubator_threshold(c));
+    if (c->cfg.model == FBA_MODEL_BA_TABLE) TRY(build_tabular_prior(c));
+    TRY(upload_regular_dirichlet(c));
+    TRY(upload_model(c));
+    return FBA_OK;
+}
+
+struct CtxDestroy { void operator()(fba_ctx* c) const { fba_destroy(c); } };
+
 }  // namespace
 
 // =============================================================================================
@@ -1238,799 +2008,36 @@ const char* fba_last_error(const fba_ctx* ctx) { return ctx ? ctx->err.c_str() :
 void fba_destroy(fba_ctx* c)
 {
     if (!c) return;
+    const std::unique_ptr<fba_ctx> freed_on_return(c);   // (the only place a context is freed: fba_create hands every one it abandons here)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (auto& p : c->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto& p : c->free_events) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (void* p : c->allocs) (void)hipFree(p);
     if (c->D.list_count_host) (void)hipHostFree(c->D.list_count_host);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
 }
 
-int fba_create(const fba_config* cfg, fba_ctx** out)
+int fba_create(const fba_config* cfg_in, fba_ctx** out)
 {
-    if (!cfg || !out) return fail(nullptr, FBA_EINVAL, "fba_create: null argument");
+    if (!cfg_in || !out) return fail(nullptr, FBA_EINVAL, "fba_create: null argument");
     *out = nullptr;
     (void)hipGetLastError();  // a new context starts from a clean error state
-    // ---- validation: the reference's constructor / validate() errors
-    // (POUCT.cpp:34-50, RejectionSampling.cpp:7-13, FactoredTiger.cpp:13-17, TigerPriors.cpp:22-25)
-    if (cfg->sims < 1 && cfg->planner == FBA_PLANNER_POUCT)
-        return fail(nullptr, FBA_EINVAL, "cannot initiate POUCT with %d simulations, must be greater than 0", cfg->sims);
-    if (cfg->horizon <= 0) return fail(nullptr, FBA_EINVAL, "cannot initiate POUCT with %d horizon, must be greater than 0", cfg->horizon);
-    if (cfg->horizon > 255) return fail(nullptr, FBA_EINVAL, "horizon %d exceeds the 255 steps a stream address holds", cfg->horizon);
-    if (cfg->particles < 1) return fail(nullptr, FBA_EINVAL, "cannot initiate belief with n = %d", cfg->particles);
-    if (cfg->discount <= 0 || cfg->discount > 1) return fail(nullptr, FBA_EINVAL, "discount must be in (0, 1]");
-    if (cfg->runs < 1 || cfg->episodes < 1) return fail(nullptr, FBA_EINVAL, "runs and episodes must be >= 1");
-    if (cfg->episodes > 65535) return fail(nullptr, FBA_EINVAL, "episodes %d exceeds the 65535 a stream address holds", cfg->episodes);
-    if (cfg->model == FBA_MODEL_POMDP && cfg->episodes != 1) return fail(nullptr, FBA_EINVAL, "planning runs have exactly one episode per run");
-
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, FBA_ENODEVICE, "no HIP device visible: libfba_hip has no CPU path");
-    if (cfg->device < 0 || cfg->device >= ndev) return fail(nullptr, FBA_EINVAL, "device %d out of range (%d visible)", cfg->device, ndev);
-
-    fba_config eff = *cfg;
-    const bool point = eff.belief == FBA_BELIEF_POINT;
-    if (point) {  // PointEstimation.cpp:36-76 / BAPointEstimation.cpp: the rejection update of a single state
-        eff.belief    = FBA_BELIEF_REJECTION;
-        eff.particles = 1;
+    const CreateSwitches sw = read_create_switches();
+    TRY(check_arguments(*cfg_in));
+    fba_config cfg = *cfg_in;
+    Problem P{};
+    DomainTables tables;
+    TRY(map_belief(cfg, P));
+    TRY(map_domain(cfg, P, tables));
+    set_problem_parameters(cfg, P);
+    std::unique_ptr<fba_ctx, CtxDestroy> c(new fba_ctx());   // destroyed on every way out but the last
+    c->cfg = cfg; c->P = P; c->sysdesc = tables.sys; c->cadesc = tables.ca; c->gdesc = tables.grid;
+    if (const int rc = make_context(c.get(), sw)) {
+        g_create_error = c->err;   // (the context, which held the message, goes)
+        return rc;
     }
-    cfg = &eff;
-    fba_ctx* c = new fba_ctx();
-    c->cfg     = *cfg;
-    Problem& P = c->P;
-    P.domain = cfg->domain; P.model = cfg->model; P.belief = cfg->belief; P.planner = cfg->planner;
-    P.reinvig = 0;
-    P.cheat   = 0;
-    P.point   = point ? 1 : 0;
-    if (cfg->belief == FBA_BELIEF_CHEATING) {
-        // a weighted (importance) filter + a rejection filter of correct-graph particles it copies from when
-        // its log likelihood drops below --threshold (prototypes/CheatingReinvigoration.cpp)
-        if (cfg->model != FBA_MODEL_BA_FACTORED) {
-            fail(nullptr, FBA_EINVAL, "cheating-reinvigoration belief: needs a factored model (fbapomdp)");
-            delete c;
-            return FBA_EINVAL;
-        }
-        if (cfg->particles < 1 || cfg->resample_amount < 1) {  // CheatingReinvigoration.cpp:30-34
-            fail(nullptr, FBA_EINVAL, "CheatingReinvigoration::cannot initiate belief of size < 1 (%d), or resample size of < 1 (%d)",
-                 cfg->particles, cfg->resample_amount);
-            delete c;
-            return FBA_EINVAL;
-        }
-        if (cfg->threshold >= 0) {  // :36-40
-            fail(nullptr, FBA_EINVAL, "CheatingReinvigoration::cannot initiate with resample_threshold >= 0 (is:%f)", cfg->threshold);
-            delete c;
-            return FBA_EINVAL;
-        }
-        P.belief = FBA_BELIEF_IMPORTANCE;
-        P.cheat  = cfg->resample_amount;
-    }
-    P.mh = 0;
-    if (cfg->belief == FBA_BELIEF_MH_GIBBS || cfg->belief == FBA_BELIEF_MH_NIPS) {
-        // an importance filter + the run's (a, o) history + a Metropolis-Hastings re-draw of the filter when the log
-        // likelihood drops below --threshold (MHwithinGibbs.cpp, MHNIPS2018.cpp); built for the priors that have
-        // computePriorModel and mutate and a fully enumerable state space: factored tiger, collision avoidance
-        const bool nips  = cfg->belief == FBA_BELIEF_MH_NIPS;
-        const char* name = nips ? "MHNIPS2018" : "MHwithinGibbs";
-        if (cfg->model != FBA_MODEL_BA_FACTORED || cfg->dirichlet_regular ||
-            !(is_ftiger(cfg->domain) || is_ca(cfg->domain) || cfg->domain == FBA_DOM_GRIDWORLD || is_sys(cfg->domain)) ||
-            (is_ca(cfg->domain) && cfg->structure_prior == FBA_SP_FULLY_CONNECTED)) {
-            fail(nullptr, FBA_EINVAL, "%s belief: needs a factored model (fbapomdp) in the expected Dirichlet mode, at most %d structure words per particle",
-                 nips ? "mh-nips" : "mh-within-gibbs", MH_MAXVAR);
-            delete c;
-            return FBA_EINVAL;
-        }
-        if (nips && is_sys(cfg->domain)) {
-            fail(nullptr, FBA_EINVAL, "mh-nips belief on sysadmin: MHNIPS2018::MH scores a particle's counts (grown from the domain's prior, 10000 per row) "
-                 "against computePriorModel(structure) (rows {total * p, total - p}, SysAdminFactoredPrior.cpp:98-127): a different prior, "
-                 "whose score difference admits no proposal -- the reference does not return from it");
-            delete c;
-            return FBA_EINVAL;
-        }
-        if (cfg->particles < 1) {  // MHwithinGibbs.cpp:243-246, MHNIPS2018.cpp:116-119
-            fail(nullptr, FBA_EINVAL, "%s::cannot initiate MH with size 0", name);
-            delete c;
-            return FBA_EINVAL;
-        }
-        if (cfg->threshold >= 0) {  // :248-252, MHNIPS2018.cpp:121-126
-            fail(nullptr, FBA_EINVAL, "%s::cannot initiate with threshold >= 0 (is:%f)", name, cfg->threshold);
-            delete c;
-            return FBA_EINVAL;
-        }
-        P.belief = FBA_BELIEF_IMPORTANCE;
-        P.mh     = nips ? 3 : cfg->belief_option == 1 ? 2 : 1;
-    }
-    P.incub = 0;
-    if (cfg->belief == FBA_BELIEF_INCUBATOR) {
-        // StructureIncubatorSampling(size, reinvigor_amount, threshold) (BABelief.cpp:53-58): the reinvigoration belief's two
-        // rejection filters + a weighted shadow filter of bred particles; same domains (a fully connected prior is needed)
-        const bool ftiger = cfg->domain == FBA_DOM_FTIGER_EPISODIC || cfg->domain == FBA_DOM_FTIGER_CONTINUOUS;
-        if (cfg->model != FBA_MODEL_BA_FACTORED || !(ftiger || is_ca(cfg->domain) || is_sys(cfg->domain)) ||
-            (is_ca(cfg->domain) && cfg->structure_prior == FBA_SP_FULLY_CONNECTED)) {
-            fail(nullptr, FBA_EINVAL, "incubator belief: needs a factored model (fbapomdp) of factored tiger, collision avoidance or sysadmin");
-            delete c;
-            return FBA_EINVAL;
-        }
-        if (cfg->particles < 1 || cfg->resample_amount < 1) {  // StructureIncubatorSampling.cpp:28-33
-            fail(nullptr, FBA_EINVAL, "StructureIncubatorSampling::Cannot initiate Incubator belief update with size < 1 (%d) or resample size < 1 (%d)",
-                 cfg->particles, cfg->resample_amount);
-            delete c;
-            return FBA_EINVAL;
-        }
-        if (cfg->threshold <= 0 || cfg->threshold > 1) {  // :35-39
-            fail(nullptr, FBA_EINVAL, "StructureIncubatorSampling::must initiate with 1 < threshold <= 0 (is:%f)", cfg->threshold);
-            delete c;
-            return FBA_EINVAL;
-        }
-        if (cfg->resample_amount >= cfg->particles || cfg->resample_amount > 1024) {  // WeightedFilter::leastLikely asserts n < size() (WeightedFilter.cpp:207)
-            fail(nullptr, FBA_EINVAL, "incubator belief: the resample amount (%d) must be below the number of particles (%d): WeightedFilter::leastLikely",
-                 cfg->resample_amount, cfg->particles);
-            delete c;
-            return FBA_EINVAL;
-        }
-        if (cfg->particles > IS_LDS_MAX_N) {
-            fail(nullptr, FBA_EINVAL, "incubator belief: at most %d particles per slot", IS_LDS_MAX_N);
-            delete c;
-            return FBA_EINVAL;
-        }
-        P.belief = FBA_BELIEF_REJECTION;
-        P.incub  = cfg->resample_amount;
-    }
-    P.nested = 0;
-    if (cfg->belief == FBA_BELIEF_NESTED) {
-        // NestedBelief(particle_amount, particle_amount^2) (BABelief.cpp:67-70): a weighted filter of count particles, each
-        // with its own flat filter of domain states; the BABelief factory only, i.e. bapomdp / fbapomdp
-        if (cfg->model == FBA_MODEL_POMDP) {
-            fail(nullptr, FBA_EINVAL, "nested belief: needs a Bayes-adaptive model (bapomdp / fbapomdp)");
-            delete c;
-            return FBA_EINVAL;
-        }
-        if (cfg->particles < 1) {  // NestedBelief.cpp:22-27
-            fail(nullptr, FBA_EINVAL, "NestedBelief: cannot initiate with filter size < 1 (top: %d, bottom: %d)", cfg->particles, cfg->particles * cfg->particles);
-            delete c;
-            return FBA_EINVAL;
-        }
-        if (cfg->particles > 256) {
-            fail(nullptr, FBA_EINVAL, "nested belief: at most 256 count particles (each carries particles^2 domain states)");
-            delete c;
-            return FBA_EINVAL;
-        }
-        P.belief = FBA_BELIEF_IMPORTANCE;
-        P.nested = cfg->particles * cfg->particles;
-    }
-    if (cfg->belief == FBA_BELIEF_REINVIGORATION) {
-        // two rejection filters + breeding (ReinvigoratingRejectionSampling.hpp); the reference has fully
-        // connected priors for factored tiger, collision avoidance and sysadmin
-        // (GridWorldFactBAPrior::sampleFullyConnectedState throws "nyi"): all three are built
-        const bool ftiger = cfg->domain == FBA_DOM_FTIGER_EPISODIC || cfg->domain == FBA_DOM_FTIGER_CONTINUOUS;
-        if (cfg->model != FBA_MODEL_BA_FACTORED || !(ftiger || is_ca(cfg->domain) || is_sys(cfg->domain)) ||
-            (is_ca(cfg->domain) && cfg->structure_prior == FBA_SP_FULLY_CONNECTED)) {
-            fail(nullptr, FBA_EINVAL, "reinvigoration belief: needs a factored model (fbapomdp) of factored tiger, collision avoidance or sysadmin");
-            delete c;
-            return FBA_EINVAL;
-        }
-        if (cfg->particles < 1 || cfg->resample_amount < 1) {  // ReinvigoratingRejectionSampling.cpp:43-49
-            fail(nullptr, FBA_EINVAL, "ReinvigoratingRejectionSampling::cannot initiate belief of size < 1 (%d), or resample size of < 1 (%d)",
-                 cfg->particles, cfg->resample_amount);
-            delete c;
-            return FBA_EINVAL;
-        }
-        P.belief  = FBA_BELIEF_REJECTION;
-        P.reinvig = cfg->resample_amount;
-    }
-    switch (cfg->domain) {
-        case FBA_DOM_TIGER_EPISODIC:
-        case FBA_DOM_TIGER_CONTINUOUS: P.S = 2; P.A = 3; P.O = 2; break;
-        case FBA_DOM_FTIGER_EPISODIC:
-        case FBA_DOM_FTIGER_CONTINUOUS:
-            if (cfg->size < 1 || cfg->size > 12) {
-                fail(nullptr, FBA_EINVAL, "cannot initiate FactoredTiger with %d irrelevant features", cfg->size);
-                delete c;
-                return FBA_EINVAL;
-            }
-            P.S = 2 << cfg->size; P.A = 3; P.O = 2;
-            break;
-        case FBA_DOM_AGR:  // AGR(10): 21 x 21 (goal, position) states, 21 help actions + work + observe, 21 positions + "none"
-            if (cfg->model != FBA_MODEL_POMDP || cfg->belief != FBA_BELIEF_REJECTION) {  // AGR.cpp:307-310 (thrown by the first weighted update)
-                fail(nullptr, FBA_EINVAL, "AGR::computeObservationProbability nyi");
-                delete c;
-                return FBA_EINVAL;
-            }
-            P.S = 21 * 21; P.A = 23; P.O = 22;
-            break;
-        case FBA_DOM_COFFEE:
-        case FBA_DOM_COFFEE_BOUTILIER:  // CoffeeProblem.hpp: 5 binary features, {GetCoffee, CheckCoffee}, {Want, NotWant}
-            if (cfg->model != FBA_MODEL_POMDP) {  // factory::makeBADomainExtension has no coffee entry
-                fail(nullptr, FBA_EINVAL, "the coffee problem has no Bayes-adaptive extension: planning only");
-                delete c;
-                return FBA_EINVAL;
-            }
-            P.S = 32; P.A = 2; P.O = 2;
-            break;
-        case FBA_DOM_SYSADMIN_INDEPENDENT:
-        case FBA_DOM_SYSADMIN_LINEAR:
-            if (cfg->size < 1 || cfg->size > 8) {  // SysAdmin.cpp:17-21; 2N actions <= FBA_MAX_ACTIONS
-                fail(nullptr, FBA_EINVAL, cfg->size < 1 ? "Cannot initiate Sysadmin with n %d" : "sysadmin: at most 8 computers (n = %d)", cfg->size);
-                delete c;
-                return FBA_EINVAL;
-            }
-            build_sysadmin(c->sysdesc, cfg->size);
-            P.S = 1 << cfg->size; P.A = 2 * cfg->size; P.O = 2;
-            break;
-        case FBA_DOM_COLLISION_AVOID:
-        case FBA_DOM_COLLISION_AVOID_CENTERED: {
-            const int W = cfg->width, H = cfg->height, n = cfg->size;
-            const char* bad = nullptr;
-            char msg[160];
-            if (W < 1) { snprintf(msg, sizeof msg, "Cannot initiate CollisionAvoidance with width %d", W); bad = msg; }
-            else if (H < 1 || H % 2 != 1 || H > 15) { snprintf(msg, sizeof msg, "Cannot initiate CollisionAvoidance with height %d, must be uneven", H); bad = msg; }
-            else if (n > W || n < 1 || n > MAXF - 2) { snprintf(msg, sizeof msg, "cannot initiate collision avoidance with more obstacles (%d ) than columns (%d)!", n, W); bad = msg; }
-            if (bad) {
-                fail(nullptr, FBA_EINVAL, "%s", bad);
-                delete c;
-                return FBA_EINVAL;
-            }
-            build_collision_avoidance(c->cadesc, W, H, n, cfg->domain == FBA_DOM_COLLISION_AVOID);
-            P.S = W * H * c->cadesc.Hn; P.A = 3; P.O = c->cadesc.Hn;
-            break;
-        }
-        case FBA_DOM_GRIDWORLD:
-            if (cfg->size < 3 || cfg->size > 15) {
-                fail(nullptr, FBA_EINVAL, "please enter a size larger than 3 to be able to run gridworld (you entered %d)", cfg->size);
-                delete c;
-                return FBA_EINVAL;
-            }
-            build_gridworld(c->gdesc, cfg->size);
-            P.S = P.O = cfg->size * cfg->size * c->gdesc.G; P.A = 4;
-            break;
-        default:
-            fail(nullptr, FBA_EINVAL, "domain %d is not supported by this build", cfg->domain);
-            delete c;
-            return FBA_EINVAL;
-    }
-    P.N = cfg->particles;
-    P.sims = cfg->sims;
-    P.horizon = cfg->horizon;
-    P.max_depth = cfg->max_depth < 0 ? cfg->horizon : cfg->max_depth;  // ArgumentParser.cpp:37-40
-    P.episodes = cfg->episodes;
-    P.exploration = cfg->exploration;
-    P.gamma = cfg->discount;
-    P.seed_lo = (uint32_t)cfg->seed;
-    P.seed_hi = (uint32_t)(cfg->seed >> 32);
-    P.noise = cfg->noise;
-    P.counts_total = cfg->counts_total;
-    P.structure_prior = cfg->structure_prior;
-    P.fd = nullptr;
-    P.gw = nullptr;
-    P.ca = nullptr;
-    P.sys = nullptr;
-    P.fd_bytes = 0;
-    P.ca_plain = 0;
-    P.zig = nullptr;
-    P.dirichlet_regular = cfg->dirichlet_regular ? 1 : 0;
-    P.packed = 0;
-    if (cfg->model == FBA_MODEL_BA_TABLE) {
-        P.phi_len = P.S * P.A * P.S;
-        P.C       = P.phi_len + P.A * P.S * P.O;
-    } else if (cfg->model == FBA_MODEL_POMDP) {
-        P.phi_len = 0;
-        P.C       = 0;
-    } else if (cfg->model == FBA_MODEL_BA_FACTORED) {
-        P.phi_len = 0;
-        int rc = build_factored_prior(c);
-        if (rc) {
-            g_create_error = c->err;
-            delete c;
-            return rc;
-        }
-        P.C = c->fdesc.ncounts + c->fdesc.nvar;
-    } else {
-        fail(nullptr, FBA_EINVAL, "model %d is not supported by this build", cfg->model);
-        delete c;
-        return FBA_EINVAL;
-    }
-    // record stride (fba_state.h): counts + state word, padded to a power of two up to 64 words
-    // (so small particles are whole cache lines), to a multiple of 4 words beyond that
-    c->dense_C = P.C;
-    // Packed particles (PackedView, fba_device.h): the tabular tiger particle as 24 uint16 increment counts over
-    // the shared prior -- 64 bytes instead of 128 in every belief update and every root sample.  Only where every
-    // kernel that touches the records is a tiger-table instantiation (launch_search / launch_belief_update), the
-    // prior is exact under "+ 65535" (TigerBAPrior: 5000, 0 and the two listen counts below) and one run cannot
-    // add more than 65535 to a cell (one T and one O increment per real step).
-    if (cfg->model == FBA_MODEL_BA_TABLE && is_tiger(cfg->domain) && !cfg->dirichlet_regular && cfg->planner == FBA_PLANNER_POUCT &&
-        (cfg->belief == FBA_BELIEF_REJECTION || cfg->belief == FBA_BELIEF_IMPORTANCE) && cfg->particles <= IS_MAX_CHUNKS * 256 &&
-        !std::getenv("FBA_IS_MULTI_MIN") && !std::getenv("FBA_DENSE_PARTICLES") && (long long)cfg->episodes * cfg->horizon <= 65535 &&
-        cfg->noise > -.15 && cfg->noise <= .3) {
-        const std::vector<float> listen = {(.85f - cfg->noise) * cfg->counts_total, (.15f + cfg->noise) * cfg->counts_total, 5000.f, 0.f};
-        if (packable_prior(listen)) {
-            P.packed = 1;
-            P.C      = (c->dense_C + 1) / 2;  // words holding the uint16 pairs; the state word follows
-        }
-    }
-    // Packed factored-tiger particles (PackedFtigerView, fba_device.h): uint16 increments over a prior that is a function of
-    // the cell and the particle's structure bits -- 144 B instead of 288 B at --size 3, so twice the beliefs per gigabyte and
-    // per kilobyte of LDS.  Only where every kernel that touches the records is a factored-tiger instantiation (po-uct,
-    // plain rejection filter, expected Dirichlet, --size 1..3) and the prior's five values are exact under "+ 65535".
-    P.ft_packed = 0; P.ft_acc = P.ft_inacc = P.ft_unif = 0.f;
-    if (cfg->model == FBA_MODEL_BA_FACTORED && is_ftiger(cfg->domain) && cfg->belief == FBA_BELIEF_REJECTION && !point &&
-        cfg->planner == FBA_PLANNER_POUCT && !cfg->dirichlet_regular && cfg->size >= 1 && cfg->size <= 3 &&
-        !std::getenv("FBA_DENSE_PARTICLES") && (long long)cfg->episodes * cfg->horizon <= 65535) {
-        const float acc = (.85f - cfg->noise) * cfg->counts_total, inacc = (.15f + cfg->noise) * cfg->counts_total, unif = .5f * cfg->counts_total;
-        if (packable_prior({acc, inacc, unif, 5000.f, 0.f})) {
-            P.ft_packed = 1;
-            P.ft_acc = acc; P.ft_inacc = inacc; P.ft_unif = unif;
-            P.C = c->fdesc.ncounts / 2 + 1;   // words of uint16 pairs, the structure word; the state word follows
-        }
-    }
-    // History particles (fba_device.h): the gridworld FBA-POMDP particle as one 4-byte entry per real step over the
-    // shared prior tables -- 100-500 bytes instead of 191 KB (N = 7) -- where the importance filter is the plain one,
-    // the run fits the record (one entry per belief update), the grid fits 3-bit coordinates and prior + j is exact in
-    // fp32 for every count a run can reach (so a row read through the entries is bit for bit the dense row).
-    // The plain rejection filter (reject_hist_kernel) stores them too where its search is the bucket-tree one (hist2_flat_search: po-uct or
-    // random, at most 65536 simulations, a table whose keys fit -- the flat root sample exists there only); ts and the rest stay dense.
-    P.hist = 0; P.hist_cap = 0; P.hist_row = 0; P.hist_base = nullptr; P.hist_alt = nullptr;
-    P.hist_lds = nullptr; P.hist_rid_bytes = 0; P.hist_distinct = 0;
-    const bool hist_records_tree = std::getenv("FBA_HIST_TREE") && !std::strcmp(std::getenv("FBA_HIST_TREE"), "records");
-    const bool hist_flat = cfg->belief == FBA_BELIEF_REJECTION && !point && (cfg->planner == FBA_PLANNER_POUCT || cfg->planner == FBA_PLANNER_RANDOM) &&
-                           cfg->sims <= 65536 && !hist_records_tree &&
-                           (cfg->tree_buckets <= 0 || (long long)cfg->tree_buckets <= (1ll << 28) / (4ll * P.O) - 2);   // (fit, below)
-    const bool hist_weighted = cfg->belief == FBA_BELIEF_IMPORTANCE && cfg->particles <= IS_MAX_CHUNKS * 256 && !std::getenv("FBA_IS_MULTI_MIN");
-    // The tabular gridworld BA-POMDP stores them too (P.hist = 2: entries of state indices over the prior's sparse rows, 176 B instead of
-    // 7.68 MB at N = 7) under the same filters, where its search is the bucket-tree one (search_tabhist_kernel: po-uct or random, at most 65536
-    // simulations, a table whose keys fit, no records tree); ts and the rest stay dense.
-    const bool hist_tab = cfg->model == FBA_MODEL_BA_TABLE && (cfg->planner == FBA_PLANNER_POUCT || cfg->planner == FBA_PLANNER_RANDOM) &&
-                          cfg->sims <= 65536 && !hist_records_tree && (cfg->tree_buckets <= 0 || (long long)cfg->tree_buckets <= (1ll << 28) / (4ll * P.O) - 2);
-    if ((cfg->model == FBA_MODEL_BA_FACTORED || hist_tab) && cfg->domain == FBA_DOM_GRIDWORLD && (hist_weighted || hist_flat) &&
-        !cfg->dirichlet_regular && !std::getenv("FBA_DENSE_PARTICLES") && (long long)cfg->episodes * cfg->horizon <= HIST_MAX_CAP && cfg->size <= HIST_MAX_N) {
-        const int cap = cfg->episodes * cfg->horizon;
-        bool exact = false;
-        if (hist_tab) exact = build_tabular_prior(c) == FBA_OK && increments_exact(c->prior, cap + 1);   // (built again below, as for every tabular context)
-        else {
-            build_gridworld_alt_prior(c);
-            std::vector<float> counts(c->prior.begin(), c->prior.begin() + c->fdesc.ncounts);
-            exact = increments_exact(counts, cap + 1) && increments_exact(c->prior_alt, cap + 1);
-        }
-        if (exact) {
-            P.hist     = hist_tab ? 2 : 1;
-            P.hist_cap = cap;
-            P.hist_row = std::max(c->gdesc.N, c->gdesc.G);
-            P.gw_N = c->gdesc.N; P.gw_G = c->gdesc.G;
-            uint32_t cells[4] = {0, 0, 0, 0};
-            for (int gq = 0; gq < c->gdesc.G; ++gq)
-                cells[gq >> 2] |= (uint32_t)(c->gdesc.goal[gq][0] * c->gdesc.N + c->gdesc.goal[gq][1]) << (8 * (gq & 3));
-            P.gw_goalcell0 = cells[0]; P.gw_goalcell1 = cells[1]; P.gw_goalcell2 = cells[2]; P.gw_goalcell3 = cells[3];
-            P.C        = 0;  // word 0 = state, word 1 = structure bits, words 2.. = entries
-        }
-    }
-    // The collision-avoidance FBA-POMDP in the prior's own graph (no structure prior: ca_fact_step's contexts) stores them too under the plain
-    // importance filter where that filter is the multi-launch one (P.hist = 3: entries of 12 + 9n bits, the whole prior in LDS -- 328 B instead of
-    // 3.5 KB at 7 x 7 with two obstacles and 80 steps), where the planner is po-uct or random, the grid fits 3-bit fields (W, H <= 8, n <= 2), the
-    // run fits the record and the search's LDS (tables, path, one staged record per lane) fits a workgroup.  The prior need not be exact under
-    // "+ j": cells that are not read their count from a table of sequential sums (ca_hist_sequences), at most CA_HIST_MAX_SEQ distinct values;
-    // other priors stay dense.  Their update exists as the multi-launch filter only (is_multi_ca_step_kernel and the launches behind it), so the
-    // format is used exactly where the dense records take that filter too (D.is_multi below: more than IS_MAX_CHUNKS * 256 particles, or from
-    // FBA_IS_MULTI_MIN up where that is set).  Up to 65 536 particles the records stay dense on the one-launch importance_kernel, as before.
-    const int ca_hist_min = std::getenv("FBA_IS_MULTI_MIN") ? std::max(1, std::atoi(std::getenv("FBA_IS_MULTI_MIN"))) : IS_MAX_CHUNKS * 256 + 1;
-    if (cfg->model == FBA_MODEL_BA_FACTORED && is_ca(cfg->domain) && cfg->belief == FBA_BELIEF_IMPORTANCE && !point && cfg->particles >= ca_hist_min &&
-        (cfg->planner == FBA_PLANNER_POUCT || cfg->planner == FBA_PLANNER_RANDOM) && !cfg->dirichlet_regular && !std::getenv("FBA_DENSE_PARTICLES") &&
-        c->fdesc.nvar == 0 && c->fdesc.nodes[2].nmax == 1 && !P.nested && !P.mh && !P.cheat && !P.incub && !P.reinvig &&
-        (long long)cfg->episodes * cfg->horizon <= HIST_MAX_CAP && (long long)cfg->episodes * cfg->horizon >= 1 &&
-        c->cadesc.W <= 8 && c->cadesc.H <= 8 && c->cadesc.n >= 1 && c->cadesc.n <= 2 && P.A == 3) {
-        const int cap = cfg->episodes * cfg->horizon, nc = c->fdesc.ncounts;
-        std::vector<uint8_t> sid;
-        std::vector<float> seq;
-        Problem Q = P;
-        Q.hist_row = nc; Q.hist_rid_bytes = (nc + 15) & ~15; Q.hist_distinct = CA_HIST_MAX_SEQ; Q.hist_cap = cap; Q.Cs = (2 + cap + 3) & ~3;
-        if (nc == ca_hist_ncounts(P.A, c->cadesc.W, c->cadesc.H, c->cadesc.n) && ca_hist_sequences(c->prior, nc, cap + 1, sid, seq) &&
-            ca_hist_search_lds(Q) <= 64 * 1024) {
-            P.hist     = 3;
-            P.hist_cap = cap;
-            P.hist_row = nc;   // (for these records: the cells of the prior table)
-            P.gw_N = 1; P.gw_G = 1;   // (init_kernel / reset_kernel pack the state into word 1 with these; nothing reads that word here)
-            P.C        = 0;    // word 0 = state, word 1 unused, words 2.. = entries
-        }
-    }
-    P.hist_compact = P.hist && !(std::getenv("FBA_HIST_STRIDE") && !std::strcmp(std::getenv("FBA_HIST_STRIDE"), "full")) ? 1 : 0;   // (A/B switch: every record at the full stride)
-    if (P.hist) P.Cs = (2 + P.hist_cap + 3) & ~3;
-    else if (P.ft_packed) P.Cs = (P.C + 1 + 3) & ~3;   // 36 words at --size 3: the point is the bytes, not a power of two
-    else {
-        int need = P.C + 1, cs = 4;
-        if (need <= 64) { while (cs < need) cs <<= 1; }
-        else cs = (need + 3) & ~3;
-        P.Cs = cs;
-    }
-    if (P.A > FBA_MAX_ACTIONS) {
-        fail(nullptr, FBA_EINVAL, "more than %d actions", FBA_MAX_ACTIONS);
-        delete c;
-        return FBA_EINVAL;
-    }
-    if (cfg->belief == FBA_BELIEF_IMPORTANCE && P.N > (1 << 26)) {
-        fail(nullptr, FBA_EINVAL, "importance sampling supports at most %d particles per slot", 1 << 26);
-        delete c;
-        return FBA_EINVAL;
-    }
-
-#define CHK(x)            \
-    do {                  \
-        int _rc = (x);    \
-        if (_rc) {        \
-            g_create_error = c->err; \
-            fba_destroy(c); \
-            return _rc;   \
-        }                 \
-    } while (0)
-#define HIPC(call)                                                                                           \
-    do {                                                                                                     \
-        hipError_t _e = (call);                                                                              \
-        if (_e != hipSuccess) {                                                                              \
-            fail(nullptr, FBA_EHIP, "%s failed: %s", #call, hipGetErrorString(_e));                          \
-            fba_destroy(c);                                                                                  \
-            return FBA_EHIP;                                                                                 \
-        }                                                                                                    \
-    } while (0)
-
-    HIPC(hipSetDevice(cfg->device));
-    HIPC(hipStreamCreate(&c->stream));
-
-    // node record layout (fba_state.h)
-    DeviceState& D = c->D;
-    const bool hashed = P.A * P.O > 64;
-    // a hashed tree with an even number of actions drops the visits word (it is the sum of the action counts) and the
-    // padding word with it: 56 -> 48 bytes per node for the four actions of gridworld
-    D.cn_off     = (hashed && P.A % 2 == 0 && !std::getenv("FBA_NODE_VISITS")) ? 0 : 1;
-    D.cq_off     = (D.cn_off + P.A + 1) & ~1;
-    D.child_off  = D.cq_off + 2 * P.A;
-    D.node_words = hashed ? D.child_off : ((D.child_off + P.A * P.O + 1) & ~1);
-    if (const char* ev = std::getenv("FBA_NODE_WORDS")) D.node_words = std::max(D.node_words, std::atoi(ev));   // (layout experiments: padded records)
-    D.max_nodes  = P.sims + 2;  // one new node per simulation at most
-    // Episodic (factored) tiger: only `listen` continues an episode and it has two observations, so a node has at most
-    // two children and the tree of a search of depth D is at most the complete binary tree with levels 0..D:
-    // 2^(D+1) - 1 nodes, whatever the number of simulations (2047 at the default depth 10 against 4098 / 16386
-    // records for 4096 / 16384 simulations).  search_kernel refuses to go past max_nodes (fault -> FBA_ESTATE).
-    if ((cfg->domain == FBA_DOM_TIGER_EPISODIC || cfg->domain == FBA_DOM_FTIGER_EPISODIC) && P.max_depth >= 0 && P.max_depth < 24)
-        D.max_nodes = std::min(D.max_nodes, (1 << (P.max_depth + 1)) + 1);  // (+1: odd, so that the slots' trees are not a power of two
-                                                                             // of bytes apart -- at exactly 128 KB the search ran 45 % slower)
-    if (const char* ev = std::getenv("FBA_NODE_BOUND")) D.max_nodes = std::max(2, std::atoi(ev));  // tests: exercise the overflow guard
-    uint32_t hcap = 0;
-    size_t hash_entry = 16;
-    D.hash_compact = 0;
-    if (hashed) {
-        hcap = 64;
-        while (hcap < 2u * (uint32_t)(D.max_nodes - 2)) hcap <<= 1;  // at most max_nodes - 2 children (one per simulation): load <= 1/2
-        D.hmask = hcap - 1;
-        if ((unsigned long long)D.max_nodes * P.A * P.O < (1ull << 27) && !std::getenv("FBA_WIDE_HASH")) {
-            D.hash_compact = 1;
-            hash_entry     = 8;
-        }
-    }
-
-    // History-particle searches keep their tree in one table of 64-byte buckets (search_hist2_kernel, fba_state.h) where its keys fit:
-    // (parent bucket, action, observation) in 28 bits, counts below the root in 16.  FBA_HIST_TREE=records keeps node records + hash table
-    // (search_hist_kernel), for A/B runs and for what does not fit.
-    D.bkt = nullptr; D.bkt_lines = 0; D.s_root = nullptr; D.search_order = nullptr;
-    size_t bkt_lines = 0;
-    const bool force_records = hist_records_tree;
-    if (P.hist && P.hist != 3 && P.sims <= 65536 && !force_records) {   // (collision-avoidance records: search_kernel's node records)
-        long long buckets = cfg->tree_buckets > 0 ? cfg->tree_buckets : 2ll * (P.sims + 2);
-        buckets = std::max(buckets, 8ll);
-        const long long fit = (1ll << 28) / (4ll * P.O) - 2;   // ((buckets * 4 + 3) * O + O - 1 < 2^28: the root's "bucket" is index `buckets`)
-        if (cfg->tree_buckets <= 0 || buckets <= fit) {
-            buckets   = std::min(buckets, fit);
-            bkt_lines = (size_t)((buckets + 1) / 2);
-        }
-    }
-    if (cfg->tree_buckets < 0 || (cfg->tree_buckets > 0 && !bkt_lines && P.hist && P.hist != 3 && !force_records)) {
-        fail(nullptr, FBA_EINVAL, "tree_buckets = %d: not a size this context's search can use (history-particle searches of at most 65536 "
-             "simulations, keys of 28 bits)", cfg->tree_buckets);
-        fba_destroy(c);
-        return FBA_EINVAL;
-    }
-    if (bkt_lines) {   // no node records, no separate hash table
-        D.max_nodes = P.sims + 2;
-        hcap = 0;
-    }
-
-    // slots
-    // (per particle: two weights, a prefix sum and a side row, which a plain rejection filter of history records does not have, + its records)
-    const size_t per_particle_aux = (P.hist && P.belief == FBA_BELIEF_REJECTION) ? 0 : (size_t)(2 * 8 + 8 + 4 * (MAXINC + 1));
-    const size_t per_slot = (size_t)P.N * (per_particle_aux + ((P.reinvig || P.cheat) ? 4 : (P.incub ? 6 : (P.hist ? 1 : 2))) * (size_t)P.Cs * 4) +
-                            (bkt_lines ? bkt_lines * 128 : (size_t)D.max_nodes * D.node_words * 4 + (size_t)hcap * hash_entry) + 1024;
-    int E = cfg->slots;
-    if (E <= 0) {
-        size_t free_b = 0, total_b = 0;
-        HIPC(hipMemGetInfo(&free_b, &total_b));
-        const size_t budget = free_b / 2;
-        E = (int)std::min<size_t>(std::max<size_t>(budget / per_slot, 1), 32768);
-        E = std::min(E, cfg->runs);
-    }
-    P.E = E;
-
-    CHK(dev_alloc(c, &D.run, E));
-    CHK(dev_alloc(c, &D.episode, E));
-    CHK(dev_alloc(c, &D.t, E));
-    CHK(dev_alloc(c, &D.active, E));
-    CHK(dev_alloc(c, &D.need_update, E));
-    CHK(dev_alloc(c, &D.need_reset, E));
-    CHK(dev_alloc(c, &D.need_init, E));
-    CHK(dev_alloc(c, &D.adv, E));
-    CHK(dev_alloc(c, &D.env_state, E));
-    CHK(dev_alloc(c, &D.ret, E));
-    CHK(dev_alloc(c, &D.disc, E));
-    CHK(dev_alloc(c, &D.action, E));
-    CHK(dev_alloc(c, &D.obs, E));
-    CHK(dev_alloc(c, &D.bufsel, E));
-    const bool is = P.belief == FBA_BELIEF_IMPORTANCE || P.incub;   // (the incubator's shadow filter is importance-sampled)
-    CHK(dev_alloc(c, &D.p_weight, is ? (size_t)2 * E * P.N : 1));
-    // history particles keep ONE record buffer per slot; a resample / reset builds the new filter in a scratch pool shared by a
-    // chunk of slots (launch_belief_update / launch_reset: for_each_chunk) -- the second buffer was a quarter of a slot's memory
-    D.single_rec = P.hist && !std::getenv("FBA_DOUBLE_BUFFER") ? 1 : 0;
-    D.ab_rows_hbm   = std::getenv("FBA_HIST_ROWS") && !std::strcmp(std::getenv("FBA_HIST_ROWS"), "hbm") ? 1 : 0;
-    D.ab_hist_multi = std::getenv("FBA_HIST_MULTI") ? (std::atoi(std::getenv("FBA_HIST_MULTI")) != 0 ? 2 : 1) : 0;
-    D.ab_no_etiger  = std::getenv("FBA_NO_ETIGER") && std::atoi(std::getenv("FBA_NO_ETIGER")) != 0 ? 1 : 0;
-    D.ab_tiger_gather = std::getenv("FBA_TIGER_GATHER") && std::atoi(std::getenv("FBA_TIGER_GATHER")) != 0 ? 1 : 0;
-    D.ab_lockstep   = std::getenv("FBA_HIST_LOCKSTEP") ? (std::atoi(std::getenv("FBA_HIST_LOCKSTEP")) != 0 ? 1 : 0) : 1;   // (on; only the bucket tree has it, below)
-    D.slot_base = 0;
-    D.scratch_slots = D.single_rec ? std::min(E, 1024) : 0;
-    if (D.single_rec)
-        if (const char* ev = std::getenv("FBA_SCRATCH_SLOTS")) D.scratch_slots = std::max(1, std::min(E, std::atoi(ev)));   // (tests: several chunks with a few slots)
-    D.rec_scratch = nullptr; D.copy_pending = nullptr; D.rec_buf = nullptr;
-    // (zeroed: a slot whose belief was never initiated -- a slot of fba_run_bapomdp beyond the configured runs -- then holds all-zero records and weights, which is
-    // what fba_belief_export writes for it and a block fba_belief_import takes in every record format; nothing else reads such a slot)
-    CHK(dev_alloc(c, &D.p_rec, (D.single_rec ? (size_t)E + D.scratch_slots : (size_t)2 * E) * P.N * P.Cs, true));
-    if (D.single_rec) {   // E + scratch_slots buffers; a slot's filter and a scratch place's buffer change places after a resample / reset (swap_buffers_kernel)
-        CHK(dev_alloc(c, &D.rec_buf, (size_t)E + D.scratch_slots));
-        std::vector<int32_t> ids((size_t)E + D.scratch_slots);
-        for (size_t i = 0; i < ids.size(); ++i) ids[i] = (int32_t)i;
-        HIPC(hipMemcpy(D.rec_buf, ids.data(), ids.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        CHK(dev_alloc(c, &D.copy_pending, E));
-    }
-    if (P.reinvig || P.cheat || P.incub) {
-        CHK(dev_alloc(c, &D.p_rec_fc, (size_t)2 * E * P.N * P.Cs, false));
-        CHK(dev_alloc(c, &D.bufsel_fc, E));
-    }
-    D.shadow = 0;
-    if (P.incub) {
-        CHK(dev_alloc(c, &D.p_rec_sh, (size_t)2 * E * P.N * P.Cs, false));
-        CHK(dev_alloc(c, &D.p_weight_sh, (size_t)2 * E * P.N));
-        CHK(dev_alloc(c, &D.bufsel_sh, E));
-        CHK(dev_alloc(c, &D.need_update_sh, E));
-        // Which shadow particles are bred anew: the reference asks its weighted filter for the `incub` least likely particles
-        // (WeightedFilter.cpp:193-238) at a moment when all N weights are equal, so no particle ever displaces one of the first `incub`
-        // and the answer is those indices in the order a binary max-heap of equal keys releases them.  That order is libstdc++'s
-        // (std::push_heap / std::pop_heap, which its priority_queue is made of); it is computed here once, with a comparison that
-        // finds no key smaller than another.
-        std::vector<int32_t> heap, order;
-        const auto equal_keys = [](int32_t, int32_t) { return false; };
-        for (int i = 0; i < P.incub; ++i) {
-            heap.push_back(i);
-            std::push_heap(heap.begin(), heap.end(), equal_keys);
-        }
-        while (!heap.empty()) {
-            std::pop_heap(heap.begin(), heap.end(), equal_keys);
-            order.push_back(heap.back());
-            heap.pop_back();
-        }
-        int32_t* d_order = nullptr;
-        CHK(dev_alloc(c, &d_order, order.size()));
-        HIPC(hipMemcpy(d_order, order.data(), order.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        D.inc_order = d_order;
-    }
-    CHK(dev_alloc(c, &D.wscan, is ? (size_t)E * P.N : 1, false));
-    D.side_w = 1 + (P.model == FBA_MODEL_BA_FACTORED ? c->fdesc.FS + c->fdesc.FO : (P.model == FBA_MODEL_BA_TABLE ? 2 : 0));
-    if (P.hist) D.side_w = 2;  // {new state, the step's entry}
-    CHK(dev_alloc(c, &D.hist_cnt, E));
-    CHK(dev_alloc(c, &D.p_side, is ? (size_t)E * P.N * D.side_w : 1, false));
-    {
-        // one workgroup per slot up to IS_MAX_CHUNKS*256 particles, several launches beyond
-        // (FBA_IS_MULTI_MIN lowers the switch-over so tests can exercise the large-filter path)
-        int multi_min = IS_MAX_CHUNKS * 256 + 1;
-        if (const char* ev = std::getenv("FBA_IS_MULTI_MIN")) multi_min = std::max(1, std::atoi(ev));
-        D.is_multi    = is && P.N >= multi_min;
-        D.ctot_stride = (P.N + 255) / 256 + 2;
-        CHK(dev_alloc(c, &D.ctot, is ? (size_t)E * D.ctot_stride : 1));
-        CHK(dev_alloc(c, &D.is_tot, (size_t)2 * E));
-    }
-    if (P.nested) {
-        CHK(dev_alloc(c, &D.nest_s, (size_t)2 * E * P.N * P.nested));
-        CHK(dev_alloc(c, &D.nest_sel, E));
-        CHK(dev_alloc(c, &D.nest_scan, (size_t)E * P.N));
-        CHK(dev_alloc(c, &D.nest_total, E));
-    }
-    if (P.mh) {
-        if (D.is_multi) {
-            fail(c, FBA_EINVAL, "mh-within-gibbs belief: at most %d particles per slot", IS_MAX_CHUNKS * 256);
-            g_create_error = c->err;
-            fba_destroy(c);
-            return FBA_EINVAL;
-        }
-        const size_t cap = (size_t)P.episodes * P.horizon;
-        CHK(dev_alloc(c, &D.lik, (size_t)E + 1));
-        CHK(dev_alloc(c, &D.cheat_pending, E));
-        CHK(dev_alloc(c, &D.mh_a, (size_t)E * cap));
-        CHK(dev_alloc(c, &D.mh_o, (size_t)E * cap));
-        CHK(dev_alloc(c, &D.mh_ep_len, (size_t)E * (P.episodes + 1)));
-        CHK(dev_alloc(c, &D.mh_n_ep, E));
-        size_t words = (size_t)3 * P.Cs + (size_t)P.S * P.A * P.S + (size_t)P.A * P.S * P.O + 2;
-        words += 2 * ((size_t)(P.horizon + 1) * P.S + P.S) + (size_t)P.episodes * (P.horizon + 1) + 2 * (size_t)P.horizon + 2;
-        if (c->fdesc.nvar > MH_MAXVAR) {
-            fail(c, FBA_EINVAL, "mh beliefs: at most %d structure words per particle", MH_MAXVAR);
-            g_create_error = c->err;
-            fba_destroy(c);
-            return FBA_EINVAL;
-        }
-        D.mh_scratch_words = (int32_t)((words + 3) & ~(size_t)3);
-        if (!mh_scratch_in_lds(D.mh_scratch_words)) CHK(dev_alloc(c, &D.mh_scratch, (size_t)E * D.mh_scratch_words));  // (else the chain's scratch is LDS)
-        const double thr = cfg->threshold;
-        HIPC(hipMemcpy(D.lik + E, &thr, sizeof thr, hipMemcpyHostToDevice));
-    }
-    if (P.cheat) {
-        if (D.is_multi) {
-            fail(c, FBA_EINVAL, "cheating-reinvigoration belief: at most %d particles per slot", IS_MAX_CHUNKS * 256);
-            g_create_error = c->err;
-            fba_destroy(c);
-            return FBA_EINVAL;
-        }
-        CHK(dev_alloc(c, &D.lik, (size_t)E + 1));
-        CHK(dev_alloc(c, &D.cheat_pending, E));
-        const double thr = cfg->threshold;
-        HIPC(hipMemcpy(D.lik + E, &thr, sizeof thr, hipMemcpyHostToDevice));
-    }
-    if (bkt_lines) {
-        D.bkt_lines = (int32_t)bkt_lines;
-        CHK(dev_alloc(c, &D.bkt, (size_t)E * bkt_lines * 8));   // (zeroed: key 0 carries epoch 0, which no search uses)
-        CHK(dev_alloc(c, &D.epoch, E));
-        CHK(dev_alloc(c, &D.nodes, 16));
-    } else {
-        CHK(dev_alloc(c, &D.nodes, (size_t)E * D.max_nodes * D.node_words, false));
-        if (hashed) {
-            CHK(dev_alloc(c, &D.hash, (size_t)E * hcap * hash_entry / 16));
-            CHK(dev_alloc(c, &D.epoch, E));
-        }
-    }
-    CHK(dev_alloc(c, &D.sim_steps, E));
-    CHK(dev_alloc(c, &D.belief_steps, E));
-    CHK(dev_alloc(c, &D.env_steps, E));
-    CHK(dev_alloc(c, &D.upd_particles, E));
-    CHK(dev_alloc(c, &D.ep_sums, (size_t)3 * E));
-    CHK(dev_alloc(c, &D.upd_attempts, E));
-    CHK(dev_alloc(c, &D.upd_entries, E));
-    CHK(dev_alloc(c, &D.cur, E));
-    CHK(dev_alloc(c, &D.trace_count, 1));
-    CHK(dev_alloc(c, &c->d_n_active, 1));
-    CHK(dev_alloc(c, &D.fault, 1));
-    CHK(dev_alloc(c, &D.lazy_reset, E));
-    P.search_budget = (P.hist && P.hist != 3 && cfg->search_budget > 0) ? cfg->search_budget : 0;   // (only search_hist_kernel parks and resumes)
-    if (P.search_budget > 0) {
-        CHK(dev_alloc(c, &D.s_sim, E));
-        CHK(dev_alloc(c, &D.s_nodes, E));
-        CHK(dev_alloc(c, &D.s_depth, E));
-        CHK(dev_alloc(c, &D.search_done, E));
-        if (D.bkt) CHK(dev_alloc(c, &D.s_root, (size_t)6 * E));
-        if (D.single_rec) {   // the chunked belief launches run over compacted lists of the slots that have work (fba_state.h)
-            CHK(dev_alloc(c, &D.slot_list, E));
-            CHK(dev_alloc(c, &D.scratch_idx, E));
-            CHK(dev_alloc(c, &D.list_count, 1));
-            HIPC(hipHostMalloc(reinterpret_cast<void**>(&D.list_count_host), sizeof(int32_t), hipHostMallocDefault));
-        }
-    }
-    if (D.bkt && D.ab_lockstep) CHK(dev_alloc(c, &D.search_order, (size_t)E));
-    if (!D.search_order) D.ab_lockstep = 0;   // (lock-step waves exist on the bucket tree only: search_hist2_kernel)
-    CHK(dev_alloc(c, &c->d_prior, P.Cs));
-    CHK(dev_alloc(c, &c->d_prior_dense, std::max(c->dense_C, 1) + 4));   // (+4: staged in 16-byte pieces)
-    if (P.hist == 1) {
-        const HistLayout L(c->gdesc.N, c->gdesc.G, P.A);
-        CHK(dev_alloc(c, &c->d_hist_base, (size_t)L.total + 16));   // (+16: a row fetch may run up to a row width past the last row)
-        CHK(dev_alloc(c, &c->d_hist_alt, (size_t)L.alt_total + 16));
-        CHK(dev_alloc(c, &c->d_hist_lds, (size_t)HistRowIds(c->gdesc.N, c->gdesc.G, P.A).total + 16 + 256 * 16 * sizeof(float)));
-        P.hist_base = c->d_hist_base;
-        P.hist_alt  = c->d_hist_alt;
-    }
-    if (P.hist == 3) CHK(dev_alloc(c, &c->d_hist_lds, (size_t)((P.hist_row + 15) & ~15) + (size_t)CA_HIST_MAX_SEQ * (P.hist_cap + 2) * sizeof(float) + 16));
-    CHK(dev_alloc(c, &c->d_uni_scan, (size_t)P.N + 1));
-    CHK(dev_alloc(c, &c->d_log1p, (size_t)P.sims + 2));
-    D.prior     = c->d_prior;
-    D.prior_dense = c->d_prior_dense;
-    D.uni_scan  = c->d_uni_scan;
-    D.log1p_tab = c->d_log1p;
-    D.trace_on  = cfg->trace ? 1 : 0;
-    D.trace_cap = 0;
-    D.runs_total = cfg->runs;
-    D.run_offset = cfg->run_offset;
-
-    // log1p(m) table: UCB(m, n) = u * sqrt(log1p(m) / n)  (POUCT.cpp:330-338, factorised so the
-    // n x n table -- 134 MB at 4096 simulations, int overflow at 65536 -- never exists)
-    {
-        std::vector<double> t((size_t)P.sims + 2);
-        for (size_t m = 0; m < t.size(); ++m) t[m] = std::log1p((double)m);
-        HIPC(hipMemcpyAsync(c->d_log1p, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        HIPC(hipStreamSynchronize(c->stream));
-    }
-    if (is) {
-        double* tmp = nullptr;
-        CHK(dev_alloc(c, &tmp, (size_t)P.N + 1));
-        launch_uniform_scan(P.N, tmp, c->d_uni_scan, c->d_uni_scan + P.N, D.ctot, c->stream);
-        HIPC(hipMemcpyAsync(&D.uni_total, c->d_uni_scan + P.N, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPC(hipStreamSynchronize(c->stream));
-    }
-    if (P.incub && (1.0 / (double)P.N) / D.uni_total > cfg->threshold) {
-        // reinvigorateBelief (StructureIncubatorSampling.cpp:155-188) tests normalised shadow weights that are uniform
-        // whenever it runs (every update ends in a resample): none is promoted, or all of them -- and then every
-        // shadow weight is zero and normalize() divides by their sum
-        fail(c, FBA_EINVAL, "incubator belief: with threshold %g every one of the %d shadow particles (normalised weight %g) is promoted at "
-             "once; the shadow filter's total weight is then zero and StructureIncubatorSampling.cpp:160-188 divides by it",
-             cfg->threshold, P.N, (1.0 / (double)P.N) / D.uni_total);
-        g_create_error = c->err;
-        fba_destroy(c);
-        return FBA_EINVAL;
-    }
-    if (cfg->model == FBA_MODEL_BA_TABLE) CHK(build_tabular_prior(c));
-    if (P.dirichlet_regular) {
-        if (cfg->model == FBA_MODEL_POMDP) {
-            fail(c, FBA_EINVAL, "the Dirichlet sampling method only exists for Bayes-adaptive models");
-            g_create_error = c->err;
-            fba_destroy(c);
-            return FBA_EINVAL;
-        }
-        int longest = std::max(P.S, P.O);
-        if (cfg->model == FBA_MODEL_BA_FACTORED) {
-            longest = 0;
-            for (int f = 0; f < c->fdesc.FS; ++f) longest = std::max(longest, c->fdesc.Ssz[f]);
-            for (int f = 0; f < c->fdesc.FO; ++f) longest = std::max(longest, c->fdesc.Osz[f]);
-        }
-        if (longest > MAXROW) {
-            fail(c, FBA_EINVAL, "regular Dirichlet mode samples rows of at most %d counts (this model has %d)", MAXROW, longest);
-            g_create_error = c->err;
-            fba_destroy(c);
-            return FBA_EINVAL;
-        }
-        ZigDesc z;
-        build_ziggurat(z);
-        CHK(dev_alloc(c, &c->d_zig, 1));
-        HIPC(hipMemcpyAsync(c->d_zig, &z, sizeof z, hipMemcpyHostToDevice, c->stream));
-        HIPC(hipStreamSynchronize(c->stream));
-        P.zig = c->d_zig;
-    }
-    if (is_ca(cfg->domain)) {
-        CHK(dev_alloc(c, &c->d_cadesc, 1));
-        HIPC(hipMemcpyAsync(c->d_cadesc, &c->cadesc, sizeof(CADesc), hipMemcpyHostToDevice, c->stream));
-        P.ca = c->d_cadesc;
-    }
-    if (is_sys(cfg->domain)) {
-        CHK(dev_alloc(c, &c->d_sysdesc, 1));
-        HIPC(hipMemcpyAsync(c->d_sysdesc, &c->sysdesc, sizeof(SysDesc), hipMemcpyHostToDevice, c->stream));
-        P.sys = c->d_sysdesc;
-    }
-    if (cfg->domain == FBA_DOM_GRIDWORLD) {
-        CHK(dev_alloc(c, &c->d_gdesc, 1));
-        HIPC(hipMemcpyAsync(c->d_gdesc, &c->gdesc, sizeof(GridDesc), hipMemcpyHostToDevice, c->stream));
-        P.gw = c->d_gdesc;
-    }
-    if (cfg->model == FBA_MODEL_BA_FACTORED) {
-        FDesc& fdh = c->fdesc;
-        const int nnodes = P.A * (fdh.FS + fdh.FO);
-        for (int k = 0; k < nnodes; ++k)
-            for (int j = 0; j < fdh.nodes[k].nmax; ++j) fdh.nodes[k].psz[j] = (uint8_t)fdh.Ssz[fdh.nodes[k].maxp[j]];
-        P.fd_bytes = (int32_t)(offsetof(FDesc, nodes) + (size_t)nnodes * sizeof(FNode));
-        P.ca_plain = (is_ca(cfg->domain) && fdh.nvar == 0 && fdh.nodes[2].nmax == 1) ||  // correct graph, no masks (not fully-connected)
-                     (is_sys(cfg->domain) && fdh.nvar == 0);
-        CHK(dev_alloc(c, &c->d_fdesc, 1));
-        HIPC(hipMemcpyAsync(c->d_fdesc, &c->fdesc, sizeof(FDesc), hipMemcpyHostToDevice, c->stream));
-        P.fd = c->d_fdesc;
-    }
-    CHK(upload_prior(c));
-    // default positions for the per-step interface: slot e is run run_offset + e
-    {
-        std::vector<int32_t> run((size_t)E);
-        for (int e = 0; e < E; ++e) run[e] = cfg->run_offset + e;
-        HIPC(hipMemcpyAsync(D.run, run.data(), run.size() * 4, hipMemcpyHostToDevice, c->stream));
-        HIPC(hipMemsetAsync(D.active, 1, (size_t)E, c->stream));
-        HIPC(hipStreamSynchronize(c->stream));
-    }
-    HIPC(hipStreamSynchronize(c->stream));
-    *out = c;
+    *out = c.release();
     return FBA_OK;
-#undef CHK
-#undef HIPC
 }
 
 int fba_domain_sizes(const fba_ctx* c, int32_t* S, int32_t* A, int32_t* O)
@@ -2891,13 +2898,6 @@ static const char* snapshot_extra_state(const fba_ctx* c)
         default: return "this belief keeps state beside its main filter";
     }
 }
-static int snapshot_record_format(const fba_ctx* c)   // as with_record_format numbers them
-{
-    const Problem& P = c->P;
-    if (P.hist) return 4 + P.hist;
-    if (P.ft_packed) return c->fdesc.FS == 2 ? 2 : (c->fdesc.FS == 3 ? 3 : 4);
-    return P.packed ? 1 : 0;
-}
 static bool snapshot_weighted(const fba_ctx* c) { return c->P.belief == FBA_BELIEF_IMPORTANCE; }
 // what a block must match to be taken by this context
 static fba_snapshot::Accepts snapshot_accepts(const fba_ctx* c)
@@ -2906,7 +2906,7 @@ static fba_snapshot::Accepts snapshot_accepts(const fba_ctx* c)
     fba_snapshot::Accepts acc{};
     fba_snapshot_head& h = acc.want;
     h.magic = FBA_SNAPSHOT_MAGIC; h.version = FBA_SNAPSHOT_VERSION;
-    h.record_format = (uint8_t)snapshot_record_format(c);
+    h.record_format = (uint8_t)record_format(P, c->fdesc.FS);
     h.weighted = snapshot_weighted(c) ? 1 : 0;
     h.model = (uint8_t)P.model; h.domain = (uint8_t)P.domain; h.actions = (uint16_t)P.A;
     h.size = (int16_t)c->cfg.size; h.width = (int16_t)c->cfg.width; h.height = (int16_t)c->cfg.height;
