@@ -690,7 +690,8 @@ struct TigerRowView {   // the counts one step of action a from state s can read
 };
 #ifdef FBA_PROFILE_REJECT
 // profiling build only (scripts/reject_regions.py): shader-clock cycles a workgroup spends in the sweep, the attempts and the pass that
-// writes the new filter (its stores waited for), and the number of workgroups
+// writes the new filter (its stores waited for), and the number of workgroups.  In reject_tiger_once_kernel the second region is the
+// attempts with the clean path's stores, drained, and the third the gather behind the loop (nothing on the clean path but the mark itself)
 __device__ unsigned long long g_reject_prof[4];
 #define REJECT_PROF_BEGIN long long rprev_ = clock64();
 #define REJECT_PROF_MARK(r) { __builtin_amdgcn_s_waitcnt(0); __syncthreads(); const long long now_ = clock64(); if (threadIdx.x == 0) atomicAdd(&g_reject_prof[r], (unsigned long long)(now_ - rprev_)); rprev_ = now_; }
@@ -817,8 +818,13 @@ __global__ void __launch_bounds__(BLK) reject_tiger_lds_kernel(Problem P, Device
 // whole 64 bytes up from memory anyway -- parks BOTH transition pairs of the action (16 bytes + the state per particle, 64 + 4 KB; the
 // attempt picks by its state) and ORs together every word a step of the action cannot read, the pad words included.  Where those are all
 // zero -- the episodic tiger: only `listen` continues an episode, so only its words ever count -- record j of the new filter is its
-// source's four parked words with the two "+1"s, the new state and zeros elsewhere: built from LDS and stored, no second read of the
-// sources, no load for the stores to wait for.  Otherwise (the continuous tiger after an `open`) the listed sources are gathered as above.
+// source's four parked words with the two "+1"s, the new state and zeros elsewhere: the thread whose attempt is accepted holds all of
+// that in registers and stores the record, whole, inside the attempt loop -- no list, no second read of the sources, no third phase, and
+// the stores of a round drain under the next round's draws (a round has one barrier, which waits for LDS only; s_wave has a half per
+// parity of the round so that the second one could go).  Otherwise (the continuous tiger after an `open`) the accepted attempts are
+// listed and the listed sources gathered behind the loop, as above.
+// A slot that gives up at REJECT_MAX_ATTEMPTS has by then written part of its OTHER buffer: harmless, bufsel is not flipped, the filter
+// it holds is untouched and the next update overwrites that buffer.
 // GATHER (reject_tiger_once_gather_kernel, FBA_TIGER_GATHER=1: same-box comparisons and tests): every slot gathers.
 // Same draws, same order, same result.  LDS: 68 KB + 16 dynamic, 8.4 KB static: two workgroups per CU.
 // ---------------------------------------------------------------------------------------------
@@ -832,7 +838,7 @@ __device__ __forceinline__ void reject_tiger_once_body(Problem P, const DeviceSt
     extern __shared__ __attribute__((aligned(16))) uint32_t s_park[];  // [N][4] words, then [N] state bytes
     __shared__ uint16_t s_acc[TIGER_LDS_MAX_N];
     __shared__ __attribute__((aligned(8))) float s_prior[24];
-    __shared__ int32_t s_wave[BLK / 64];
+    __shared__ int32_t s_wave[2 * (BLK / 64)];   // a half per parity of the round
     __shared__ int32_t s_count;
     const int e = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (!D.need_update[e]) return;
@@ -881,9 +887,11 @@ __device__ __forceinline__ void reject_tiger_once_body(Problem P, const DeviceSt
     }
     const bool gather = __syncthreads_or(other != 0u) != 0 || GATHER;
     REJECT_PROF_MARK(0)
-    int acc = 0, base = 0;
+    const uint32_t m0 = (uint32_t) - (int)(a == 0), m1 = (uint32_t) - (int)(a == 1), m2 = (uint32_t) - (int)(a == 2);
+    const uint32_t add_o = o ? 0x10000u : 1u;
+    int acc = 0, base = 0, half = 0;
     while (acc < N) {
-        if (base >= REJECT_MAX_ATTEMPTS) {  // see reject_kernel
+        if (base >= REJECT_MAX_ATTEMPTS) {  // see reject_kernel (records of earlier rounds are in the other buffer by now; the slot's filter is as it was)
             if (tid == 0) {
                 atomicCAS(D.fault, 0, 1 + e);
                 D.need_update[e] = 0;
@@ -897,55 +905,50 @@ __device__ __forceinline__ void reject_tiger_once_body(Problem P, const DeviceSt
         const int s0  = s_st[src];
         int s = s0, so;
         double r;
+        const uint4 t = s_tab[src];
         {
-            const uint4 t = s_tab[src];
             const uint32_t wt = s0 ? t.y : t.x, wo0 = t.z, wo1 = t.w;
             tiger_step_packed(P, g, [&](int w) { return w < 6 ? wt : (w & 1 ? wo1 : wo0); }, s_prior, s, a, so, r, NoInc{});
         }
         const bool ok = (so == o);
         const unsigned long long ballot = __ballot(ok);
         const int prefix = __popcll(ballot & ((1ull << lane) - 1ull));
-        if (lane == 0) s_wave[wave] = __popcll(ballot);
-        __syncthreads();
+        if (lane == 0) s_wave[half + wave] = __popcll(ballot);
+        __syncthreads();   // the round's only barrier: this half of s_wave is next written two rounds on, behind the next round's barrier
         int woff = 0, chunk = 0;
         for (int w = 0; w < BLK / 64; ++w) {
-            if (w < wave) woff += s_wave[w];
-            chunk += s_wave[w];
+            if (w < wave) woff += s_wave[half + w];
+            chunk += s_wave[half + w];
         }
         const int j = acc + woff + prefix;  // position among all accepted attempts
-        if (ok && j < N) {
-            s_acc[j] = (uint16_t)(src | (s0 << 12) | (s << 13));
+        if (ok && j < N) {   // (j < N: the last round overshoots, and record N is the next buffer's first)
+            if (!gather) {
+                // record j, whole, from this thread's registers: the source's parked words with T(s, a, s') and O(a, s', o) bumped -- cell
+                // 6 s + 2 a + s' is half s' of word 3 s + a; cell 12 + 4 a + 2 s' + o is half o of word 6 + 2 a + s' -- at words a, 3 + a,
+                // 6 + 2a, 7 + 2a, the new state at word 12, zeros elsewhere (masks on the slot's action, not selects: those become a chain
+                // of scalar branches here).  Nothing waits for these stores: they drain under the next round's attempts.
+                const uint32_t add_t = s ? 0x10000u : 1u;
+                const uint32_t bx = t.x + (s0 ? 0u : add_t), by = t.y + (s0 ? add_t : 0u), bz = t.z + (s ? 0u : add_o), bw = t.w + (s ? add_o : 0u);
+                uint4* d = reinterpret_cast<uint4*>(dcn) + (size_t)j * 4;
+                d[0] = make_uint4(bx & m0, bx & m1, bx & m2, by & m0);
+                d[1] = make_uint4(by & m1, by & m2, bz & m0, bw & m0);
+                d[2] = make_uint4(bz & m1, bw & m1, bz & m2, bw & m2);
+                d[3] = make_uint4((uint32_t)s, 0u, 0u, 0u);
+            } else {
+                s_acc[j] = (uint16_t)(src | (s0 << 12) | (s << 13));
+            }
             if (j == N - 1) s_count = k + 1;
         }
         acc += min(chunk, N - acc);
         base += BLK;
-        __syncthreads();
+        half ^= BLK / 64;
     }
+    __syncthreads();   // s_count, and the list of a slot that gathers
     REJECT_PROF_MARK(1)
-    // the new filter: record j = source record with T(s, a, s') and O(a, s', o) bumped and the new state
-    const int part = tid & 3;
-    constexpr int GROUPS = BLK / 4;
-    if (!gather) {
-        // where this thread's quarter of a record takes its four words from: place 0..3 of the parked words, 4 = the state, -1 = zero
-        const auto place_of = [&](int w) { return w == a ? 0 : (w == 3 + a ? 1 : (w == 6 + 2 * a ? 2 : (w == 7 + 2 * a ? 3 : (w == 12 ? 4 : -1)))); };
-        const int d0 = place_of(4 * part), d1 = place_of(4 * part + 1), d2 = place_of(4 * part + 2), d3 = place_of(4 * part + 3);
-        const auto word_of = [&](int d, const uint4& t, int ns) {
-            return d == 0 ? t.x : (d == 1 ? t.y : (d == 2 ? t.z : (d == 3 ? t.w : (d == 4 ? (uint32_t)ns : 0u))));
-        };
-        const uint32_t add_o = o ? 0x10000u : 1u;
-        for (int j = tid >> 2; j < N; j += GROUPS) {
-            const uint32_t en = s_acc[j];
-            const int s0 = (en >> 12) & 1, ns = (en >> 13) & 1;
-            uint4 t = s_tab[en & 4095];
-            const uint32_t add_t = ns ? 0x10000u : 1u;   // cell 6 s + 2 a + s' is half s' of word 3 s + a; cell 12 + 4 a + 2 s' + o is half o of word 6 + 2 a + s'
-            t.x += s0 ? 0u : add_t;
-            t.y += s0 ? add_t : 0u;
-            t.z += ns ? 0u : add_o;
-            t.w += ns ? add_o : 0u;
-            reinterpret_cast<uint4*>(dcn)[(size_t)j * 4 + part] = make_uint4(word_of(d0, t, ns), word_of(d1, t, ns), word_of(d2, t, ns), word_of(d3, t, ns));
-        }
-    } else {
-        constexpr int UNROLL = 4;  // four independent copies in flight per thread
+    if (gather) {
+        // the new filter: record j = source record with T(s, a, s') and O(a, s', o) bumped and the new state
+        const int part = tid & 3;
+        constexpr int GROUPS = BLK / 4, UNROLL = 4;  // four independent copies in flight per thread
         for (int j0 = tid >> 2; j0 < N; j0 += GROUPS * UNROLL) {
             uint32_t en[UNROLL];
             float4 v[UNROLL];

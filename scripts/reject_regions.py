@@ -1,6 +1,9 @@
-"""Where a workgroup of reject_tiger_lds_kernel spends its cycles: an instrumented build of the same sources (-DFBA_PROFILE_REJECT:
-clock64() marks behind the sweep, the attempts and the pass that writes the new filter, each behind a barrier and a wait for the
-workgroup's outstanding loads and stores) run on the bench workload.
+"""Where a workgroup of the packed tiger rejection update spends its cycles: an instrumented build of the same sources
+(-DFBA_PROFILE_REJECT: clock64() marks behind the sweep, the attempts and the pass that writes the new filter, each behind a barrier and
+a wait for the workgroup's outstanding loads and stores) run on the bench workload.  reject_tiger_once_kernel stores the new filter
+inside its attempt loop where it need not gather: there the second region is the attempts with their stores, drained, and the third
+(the gather behind the loop) is all but empty.  The names of the regions are those of the three marks in every build, so that a
+library of an older commit (FBA_LIB) prints the same line.
 python scripts/reject_regions.py build      (hipcc, no GPU needed)  ->  fba_pomdp_amd/libfba_hip_rprof.so
 python scripts/reject_regions.py [slots]    (on the GPU box)        ->  one JSON line
 FBA_LIB names another instrumented library (an older build of the kernel, for the before / after pair); FBA_PARTICLES another filter size."""
@@ -33,7 +36,7 @@ eng.run_ticks(2)
 L.fba_debug_reject_profile(out, 1)
 eng.run_ticks(8)
 L.fba_debug_reject_profile(out, 0)
-names = ["sweep", "attempts", "new filter"]
+names = ["sweep", "attempts", "new filter"]     # reject_tiger_once_kernel: sweep | attempts with the stores | gather behind the loop
 v = list(out)
 total = sum(v[:3])
 print(json.dumps({"lib": os.path.basename(os.environ["FBA_LIB"]), "slots": slots, "config": kw, "workgroups": v[3],
