@@ -256,6 +256,8 @@ def load():
     L.fba_get_return_sums.argtypes = [vp, vp]
     L.fba_get_kernel_times.argtypes = [vp, P(KernelTime)]
     L.fba_reset_kernel_times.argtypes = [vp]
+    if hasattr(L, "fba_debug_compact_slots"):   # diagnostic, not in include/fba_hip.h (an older library named by FBA_LIB lacks it)
+        L.fba_debug_compact_slots.argtypes = [vp, P(C.c_int32)]
     L.fba_trace_count.argtypes = [vp]
     L.fba_get_trace.argtypes = [vp, vp, C.c_int32]
     if not os.environ.get("FBA_LIB") or hasattr(L, "fba_get_trace_hist"):

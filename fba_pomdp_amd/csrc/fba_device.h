@@ -138,6 +138,18 @@ struct PackedView {
     }
 };
 
+// The words of a packed tiger particle held compact (DeviceState::compact, fba_state.h): its four `listen` words stand for words 2, 5,
+// 10 and 11 of the 64-byte record -- the state bit masked out of the last -- and every other count word is zero.  For PackedView.
+struct CompactTigerWords {
+    const float* p;
+    static constexpr bool row_regs = false;
+    __device__ __forceinline__ float at(int w) const
+    {
+        const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
+        return __uint_as_float(w == 2 ? q[0] : (w == 5 ? q[1] : (w == 10 ? q[2] : (w == 11 ? q[3] & 0x7fffffffu : 0u))));
+    }
+};
+
 // Packed factored-tiger particle (Problem::ft_packed, FS = K + 1 binary state features): the record holds, per cell of
 // the count table, how many "+1"s the cell has received (uint16, two per word, dense order), then the parent set of
 // the listen observation node (one word), then the state.  A count is prior(cell, parent set) + that number: the prior

@@ -70,8 +70,11 @@ struct fba_ctx {
     std::vector<EventPair> free_events;
     double k_ms[FBA_K_COUNT]          = {0};
     uint64_t k_launches[FBA_K_COUNT]  = {0};
-    uint64_t base_sim = 0, base_attempts = 0, base_particles = 0, base_entries = 0;
+    uint64_t base_sim = 0, base_attempts = 0, base_particles = 0, base_entries = 0, base_compact_full = 0, base_compact = 0;
     std::vector<fba_trace_rec> trace_host;
+    // compact filters (fba_state.h): the experiment loop of this context may keep them (plan_filters), and a tick has run that way since
+    // the last materialize_records
+    bool compact_ok = false, compact_dirty = false;
     // fba_probe: on while probe.count > 0; the buffers probe points into are the context's (fba_probe_enable)
     BeliefProbeArgs probe{};
     int32_t* d_probe_meta = nullptr;   // [2][nodes] seg, rows
@@ -1068,10 +1071,23 @@ int timed(fba_ctx* c, int kind, F&& launch)
 
 int k_update_kind(const fba_ctx* c) { return c->P.belief == FBA_BELIEF_REJECTION ? FBA_K_BELIEF_RS : FBA_K_BELIEF_IS; }
 
+// Every slot in 64-byte records: in front of everything outside tick() that reads or writes p_rec.  Where no tick has run compact since
+// the last call (fba_state.h) nothing is launched -- but for the callers that want pending lazy resets written out whatever the
+// format (`reset`: where launch_materialize_reset stood before compact filters existed)
+void materialize_records(fba_ctx* c, bool reset = false)
+{
+    if (c->compact_dirty) launch_materialize_records(c->P, c->D, c->stream);
+    else if (reset) launch_materialize_reset(c->P, c->D, c->stream);
+    c->compact_dirty = false;
+    c->D.compact_on  = 0;   // the per-call launches never leave a slot compact
+}
+
 // one real time-step of every active slot
 int tick(fba_ctx* c)
 {
     int rc;
+    c->D.compact_on = c->compact_ok && c->probe.count == 0 ? 1 : 0;   // (the probe reads records)
+    if (c->D.compact_on) c->compact_dirty = true;
     if ((rc = timed(c, FBA_K_SEARCH, [&] { launch_search(c->P, c->D, c->stream); }))) return rc;
     if ((rc = timed(c, FBA_K_ENV, [&] { launch_env(c->P, c->D, c->d_n_active, c->stream); }))) return rc;
     if (c->probe.count > 0) launch_belief_probe(c->P, c->D, c->probe, c->stream);   // (the slots env_kernel has just flagged for an update; in no time bucket)
@@ -1150,6 +1166,7 @@ int start_experiment(fba_ctx* c, int runs_total)
 {
     int rc;
     if ((rc = clear_parked_searches(c))) return rc;
+    materialize_records(c);   // (bufsel is rewritten below)
     c->D.runs_total = runs_total;
     c->D.run_offset = c->cfg.run_offset;
     const int32_t n_active = runs_total < 0 ? c->P.E : std::min(c->P.E, runs_total);
@@ -1213,7 +1230,7 @@ uint64_t sum_counter(fba_ctx* c, const T* dev, int n, int* rc)
 // ---- stage 1: the environment switches, read once per fba_create (not cached: tests change them between contexts of one process)
 struct CreateSwitches {
     bool double_buffer, node_visits, wide_hash, dense_particles;   // set at all
-    bool no_etiger, tiger_gather;                                  // set to a number other than 0
+    bool no_etiger, tiger_gather, no_compact;                      // set to a number other than 0
     int hist_multi;                                                // 0 unset, 1 set to 0, 2 set to another number
     bool hist_lockstep;                                            // on unless set to 0
     bool tree_records, rows_hbm, stride_full;                      // FBA_HIST_TREE=records, FBA_HIST_ROWS=hbm, FBA_HIST_STRIDE=full
@@ -1234,6 +1251,7 @@ CreateSwitches read_create_switches()
     s.dense_particles = std::getenv("FBA_DENSE_PARTICLES") != nullptr;
     s.no_etiger       = number(std::getenv("FBA_NO_ETIGER"), 0) != 0;
     s.tiger_gather    = number(std::getenv("FBA_TIGER_GATHER"), 0) != 0;
+    s.no_compact      = number(std::getenv("FBA_NO_COMPACT"), 0) != 0;
     const char* multi = std::getenv("FBA_HIST_MULTI");
     s.hist_multi      = multi ? (std::atoi(multi) != 0 ? 2 : 1) : 0;
     s.hist_lockstep   = number(std::getenv("FBA_HIST_LOCKSTEP"), 1) != 0;
@@ -1698,6 +1716,17 @@ int plan_filters(fba_ctx* c, const CreateSwitches& sw)
     return FBA_OK;
 }
 
+// Compact filters between the updates of the experiment loop (fba_state.h; FBA_NO_COMPACT=1 keeps 64-byte records, for A/B runs and
+// tests): where the update is reject_tiger_once_kernel on the episodic tiger's plain rejection filter and the search the one
+// instantiation that reads them, and a run cannot carry a count into bit 15 of its half.  Asked once the tree is planned
+bool compact_filters_ok(const fba_ctx* c, const CreateSwitches& sw)
+{
+    const Problem& P = c->P;
+    return P.packed && c->cfg.domain == FBA_DOM_TIGER_EPISODIC && P.belief == FBA_BELIEF_REJECTION && !P.reinvig && !P.incub && !P.cheat &&
+           !P.nested && !P.point && P.N >= TIGER_ONCE_MIN_N && P.N <= TIGER_LDS_MAX_N && run_steps(c->cfg) <= 32767 && !sw.tiger_gather &&
+           !sw.dense_particles && !sw.no_compact && search_takes_compact(P, c->D);
+}
+
 // ---- stage 5: the device buffers, grouped as the data is, and the uploads
 template <typename... T>
 int alloc_each(fba_ctx* c, size_t n, T**... p)   // n zeroed elements for every one of the pointers
@@ -1713,8 +1742,9 @@ int alloc_slot_state(fba_ctx* c)
     DeviceState& D = c->D;
     const size_t E = (size_t)c->P.E;
     TRY(alloc_each(c, E, &D.run, &D.episode, &D.t, &D.active, &D.need_update, &D.need_reset, &D.need_init, &D.adv, &D.env_state, &D.ret, &D.disc,
-                   &D.action, &D.obs, &D.bufsel, &D.cur, &D.lazy_reset));
-    TRY(alloc_each(c, E, &D.sim_steps, &D.belief_steps, &D.env_steps, &D.upd_particles, &D.upd_attempts, &D.upd_entries));
+                   &D.action, &D.obs, &D.bufsel, &D.cur, &D.lazy_reset, &D.compact));
+    TRY(alloc_each(c, E, &D.sim_steps, &D.belief_steps, &D.env_steps, &D.upd_particles, &D.upd_attempts, &D.upd_entries, &D.upd_compact_full,
+                   &D.upd_compact));
     TRY(dev_alloc(c, &D.ep_sums, 3 * E));
     TRY(alloc_each(c, 1, &D.trace_count, &c->d_n_active, &D.fault));
     D.trace_on   = c->cfg.trace ? 1 : 0;
@@ -1969,6 +1999,7 @@ int make_context(fba_ctx* c, const CreateSwitches& sw)
     if (c->cfg.model == FBA_MODEL_BA_TABLE) TRY(build_tabular_prior(c));
     TRY(upload_regular_dirichlet(c));
     TRY(upload_model(c));
+    c->compact_ok = compact_filters_ok(c, sw);
     return FBA_OK;
 }
 
@@ -2143,7 +2174,7 @@ int fba_set_position(fba_ctx* c, const int32_t* run, const int32_t* episode, con
     const size_t n = (size_t)c->P.E * 4;
     int rc;
     if ((rc = clear_parked_searches(c))) return rc;
-    if (run || episode) launch_materialize_reset(c->P, c->D, c->stream);  // a pending lazy reset belongs to the old (run, episode)
+    if (run || episode) materialize_records(c, true);  // a pending lazy reset belongs to the old (run, episode)
     if (run) HIPCHK(c, hipMemcpyAsync(c->D.run, run, n, hipMemcpyHostToDevice, c->stream));
     if (episode) HIPCHK(c, hipMemcpyAsync(c->D.episode, episode, n, hipMemcpyHostToDevice, c->stream));
     if (t) HIPCHK(c, hipMemcpyAsync(c->D.t, t, n, hipMemcpyHostToDevice, c->stream));
@@ -2156,6 +2187,7 @@ int fba_belief_init(fba_ctx* c)
     if (!c) return FBA_EINVAL;
     int rc;
     if ((rc = clear_parked_searches(c))) return rc;
+    materialize_records(c);   // (init_kernel writes 64-byte records)
     if ((rc = set_flags(c, c->D.need_init, nullptr, 1))) return rc;
     if ((rc = timed(c, FBA_K_BELIEF_INIT, [&] { launch_init(c->P, c->D, c->stream); }))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2170,6 +2202,7 @@ int fba_belief_reset_domain_state(fba_ctx* c)
     if (c->P.model == FBA_MODEL_POMDP) return fail(c, FBA_EINVAL, "resetDomainStateDistribution exists for Bayes-adaptive beliefs only");
     if (!c->belief_ready) return fail(c, FBA_ESTATE, "belief not initiated");
     int rc;
+    materialize_records(c);
     if ((rc = set_flags(c, c->D.need_reset, nullptr, 1))) return rc;
     if ((rc = timed(c, FBA_K_BELIEF_RESET, [&] { launch_reset(c->P, c->D, c->stream); }))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2181,6 +2214,7 @@ int fba_select_action(fba_ctx* c, const int32_t* hist_len, const uint8_t* active
     if (!c || !action) return FBA_EINVAL;
     if (!c->belief_ready) return fail(c, FBA_ESTATE, "belief not initiated");
     int rc;
+    materialize_records(c);   // the per-call interface works on 64-byte records
     if (hist_len) HIPCHK(c, hipMemcpyAsync(c->D.t, hist_len, (size_t)c->P.E * 4, hipMemcpyHostToDevice, c->stream));
     if ((rc = set_flags(c, c->D.active, active, 1))) return rc;
     {   // Planner::selectAction returns a finished search: whole searches in one launch, whatever the context's search_budget
@@ -2218,6 +2252,7 @@ int fba_belief_update(fba_ctx* c, const int32_t* action, const int32_t* obs, con
             if (!active || active[e]) ++c->packed_updates[e];
     }
     int rc;
+    materialize_records(c);   // the per-call interface works on 64-byte records
     HIPCHK(c, hipMemcpyAsync(c->D.action, action, (size_t)c->P.E * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->D.obs, obs, (size_t)c->P.E * 4, hipMemcpyHostToDevice, c->stream));
     if ((rc = set_flags(c, c->D.need_update, active, 1))) return rc;
@@ -2277,7 +2312,7 @@ static void hist_materialize(const fba_ctx* c, const uint32_t* rec, uint32_t cnt
 static int belief_get_range(fba_ctx* c, int32_t slot, int32_t first, int32_t n, int32_t* state, double* weight, float* counts)
 {
     const Problem& P = c->P;
-    launch_materialize_reset(c->P, c->D, c->stream);  // a lazily reset rejection filter: write the states out first
+    materialize_records(c, true);  // a lazily reset rejection filter: write the states out first
     HIPCHK(c, hipStreamSynchronize(c->stream));
     uint8_t sel = 0;
     HIPCHK(c, hipMemcpy(&sel, c->D.bufsel + slot, 1, hipMemcpyDeviceToHost));
@@ -2406,6 +2441,7 @@ int fba_belief_summary(fba_ctx* c, int32_t first, int32_t count, fba_belief_summ
     size_t per_slot = 2 + (size_t)S + (mean_counts ? (size_t)dense_C : 0) + (size_t)nvar * 17;
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>({(size_t)count, (size_t)32768, ((size_t)256 << 20) / (per_slot * 8)}));
     ScratchBuf<double> d_head, d_state, d_mean, d_emass, d_eprob;
+    materialize_records(c);   // the kernels below read 64-byte records
     HIPCHK(c, d_head.alloc((size_t)chunk * 2));
     if (state_mass) HIPCHK(c, d_state.alloc((size_t)chunk * S));
     if (mean_counts) HIPCHK(c, d_mean.alloc((size_t)chunk * dense_C));
@@ -2592,6 +2628,7 @@ int fba_belief_predict(fba_ctx* c, int32_t first, int32_t count, int32_t nq, con
     const size_t per_slot = (size_t)nq * ((trans ? (size_t)TL : 0) + (obsp ? (size_t)OL : 0) + 1 + (P.hist ? (size_t)hw : 0)) + 1;
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>({(size_t)count, (size_t)32768, ((size_t)256 << 20) / (per_slot * 8)}));
     ScratchBuf<double> d_trans, d_obsp, d_joint, d_wtot, d_hacc;
+    materialize_records(c);   // the kernels below read 64-byte records
     HIPCHK(c, d_wtot.alloc((size_t)chunk));
     if (trans) HIPCHK(c, d_trans.alloc((size_t)chunk * nq * TL));
     if (obsp) HIPCHK(c, d_obsp.alloc((size_t)chunk * nq * OL));
@@ -2734,6 +2771,7 @@ int fba_belief_forecast(fba_ctx* c, int32_t first, int32_t count, const int32_t*
     const size_t per_slot = (size_t)S * 4 + 1;
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>({(size_t)count, (size_t)32768, ((size_t)256 << 20) / (per_slot * 8)}));
     ScratchBuf<double> d_acc, d_next, d_post, d_ev;
+    materialize_records(c);   // the kernels below read 64-byte records
     HIPCHK(c, d_acc.alloc((size_t)chunk * 2 * S));
     if (next_mass) HIPCHK(c, d_next.alloc((size_t)chunk * S));
     if (post_mass) HIPCHK(c, d_post.alloc((size_t)chunk * S));
@@ -2771,6 +2809,7 @@ int fba_probe_enable(fba_ctx* c, int32_t first, int32_t count, int32_t capacity)
     FactorLayout fl;
     if (count > 0)
         if (const int rc = factor_layout(c, "fba_probe_enable", fl)) return rc;
+    materialize_records(c);   // (the probe reads 64-byte records: while it is on, tick() keeps them)
     HIPCHK(c, hipStreamSynchronize(c->stream));   // (nothing in flight writes the old buffers)
     dev_free(c, c->probe.acc);
     dev_free(c, c->probe.recs);
@@ -2829,7 +2868,7 @@ int fba_belief_set(fba_ctx* c, int32_t slot, const int32_t* state, const double*
     if (!c || slot < 0 || slot >= c->P.E) return FBA_EINVAL;
     const Problem& P = c->P;
     if (P.nested) return fail(c, FBA_EINVAL, "the nested belief cannot be set from the host (its weights' prefix sums and flat filters live on the device)");
-    launch_materialize_reset(c->P, c->D, c->stream);
+    materialize_records(c, true);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     uint8_t sel = 0;
     HIPCHK(c, hipMemcpy(&sel, c->D.bufsel + slot, 1, hipMemcpyDeviceToHost));
@@ -3014,7 +3053,7 @@ int fba_belief_export(fba_ctx* c, int32_t first, int32_t count, void* buf, int64
         return fail(c, FBA_EINVAL, "fba_belief_export: %d blocks of %lld bytes need %lld, the buffer has %lld", count, (long long)per,
                     (long long)count * per, (long long)(buf ? cap : 0));
     if (count == 0) return FBA_OK;
-    launch_materialize_reset(c->P, c->D, c->stream);   // a lazily reset rejection filter: write the states out first, as fba_belief_get does
+    materialize_records(c, true);   // a lazily reset rejection filter: write the states out first, as fba_belief_get does
     const int chunk = snapshot_chunk(per, count);
     ScratchBuf<uint8_t> d_stage;
     ScratchBuf<unsigned long long> d_check;
@@ -3076,6 +3115,7 @@ int fba_belief_import(fba_ctx* c, int32_t first, int32_t count, const void* buf,
         std::memcpy(&heads[(size_t)b], in + (size_t)b * (size_t)per, sizeof(fba_snapshot_head));
     }
     if ((rc = snapshot_quiet(c, "fba_belief_import", first, count, -1))) return rc;
+    materialize_records(c);   // (the commit writes 64-byte records into the live buffer)
     // ---- device pass: checksum and every record of every block, then (and only then) the commit ----
     const int chunk = snapshot_chunk(per, count);
     const bool one = chunk >= count;   // the whole range is staged at once: it is uploaded once
@@ -3132,7 +3172,7 @@ int fba_belief_replicate(fba_ctx* c, int32_t src, int32_t first, int32_t count)
     if (count == 0) return FBA_OK;
     if (!c->belief_ready) return fail(c, FBA_ESTATE, "fba_belief_replicate: belief not initiated");
     if ((rc = snapshot_quiet(c, "fba_belief_replicate", first, count, src))) return rc;
-    launch_materialize_reset(c->P, c->D, c->stream);   // (a lazily reset source: its states are written out, results keep their bits)
+    materialize_records(c, true);   // (a lazily reset source: its states are written out, results keep their bits)
     launch_snapshot_replicate(c->P, c->D, src, first, count, c->stream);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3249,6 +3289,8 @@ int fba_get_kernel_times(fba_ctx* c, fba_kernel_time* out)
     const uint64_t attempts  = sum_counter(c, c->D.upd_attempts, P.E, &rc) - c->base_attempts;
     const uint64_t particles = sum_counter(c, c->D.upd_particles, P.E, &rc) - c->base_particles;
     const uint64_t entries   = sum_counter(c, c->D.upd_entries, P.E, &rc) - c->base_entries;
+    const uint64_t compact_full = sum_counter(c, c->D.upd_compact_full, P.E, &rc) - c->base_compact_full;
+    const uint64_t compact      = sum_counter(c, c->D.upd_compact, P.E, &rc) - c->base_compact;
     if (rc) return rc;
     // algorithmic bytes, SURVEY.md section 8(d): Pb = particle payload, Rt / Ro = bytes of the
     // transition / observation rows one step consults
@@ -3274,7 +3316,10 @@ int fba_get_kernel_times(fba_ctx* c, fba_kernel_time* out)
         // reject_tiger_lds_kernel (packed particles, N <= TIGER_LDS_MAX_N): the alternative formula SURVEY 8(d) asks to be
         // stated when the build does not move dense particles -- the attempts run from LDS, so an update reads the
         // filter once to park it, reads the N accepted sources and writes N records, 64 bytes each
-        if (P.packed && P.N <= TIGER_LDS_MAX_N) out[FBA_K_BELIEF_RS].bytes = particles * 3 * (uint64_t)(P.Cs * 4);
+        // ... and where the experiment loop keeps compact filters (fba_state.h), what those launches moved: a particle written compact
+        // was read as 64 or as 16 bytes and written as 16 -- 80 or 32 bytes
+        if (P.packed && P.N <= TIGER_LDS_MAX_N)
+            out[FBA_K_BELIEF_RS].bytes = (particles - compact_full - compact) * 3 * (uint64_t)(P.Cs * 4) + compact_full * 80 + compact * 32;
         // packed factored-tiger records (reject_kernel on 144-byte records at --size 3): SURVEY's formula on the bytes a packed particle has --
         // an attempt reads its source record and one 4-byte word per two-cell Dirichlet row it samples, an accepted one writes a record
         if (P.ft_packed) {
@@ -3318,6 +3363,18 @@ int fba_debug_slot_counters(fba_ctx* c, unsigned long long* sim_steps, int32_t* 
     return FBA_OK;
 }
 
+// diagnostic (tests; not part of include/fba_hip.h): the slots whose filter is compact right now (fba_state.h)
+int fba_debug_compact_slots(fba_ctx* c, int32_t* n)
+{
+    if (!c || !n) return FBA_EINVAL;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<uint8_t> h((size_t)c->P.E);
+    HIPCHK(c, hipMemcpy(h.data(), c->D.compact, h.size(), hipMemcpyDeviceToHost));
+    *n = 0;
+    for (uint8_t v : h) *n += v != 0;
+    return FBA_OK;
+}
+
 int fba_reset_kernel_times(fba_ctx* c)
 {
     if (!c) return FBA_EINVAL;
@@ -3328,6 +3385,8 @@ int fba_reset_kernel_times(fba_ctx* c)
     c->base_attempts  = sum_counter(c, c->D.upd_attempts, c->P.E, &rc);
     c->base_particles = sum_counter(c, c->D.upd_particles, c->P.E, &rc);
     c->base_entries   = sum_counter(c, c->D.upd_entries, c->P.E, &rc);
+    c->base_compact_full = sum_counter(c, c->D.upd_compact_full, c->P.E, &rc);
+    c->base_compact      = sum_counter(c, c->D.upd_compact, c->P.E, &rc);
     return rc;
 }
 

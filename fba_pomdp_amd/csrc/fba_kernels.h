@@ -12,6 +12,7 @@ constexpr int SEARCH_STAGE_WORDS = 128; // particle records up to this many word
 constexpr int ROOT_CHILDREN = 8;        // root child pointers are kept in LDS when A*O is at most this
 constexpr int REJECT_BLOCK  = 256;   // attempts per chunk of the rejection filter
 constexpr int TIGER_LDS_MAX_N = 4096;  // reject_tiger_lds_kernel: filters up to this many packed tiger particles are parked in LDS
+constexpr int TIGER_ONCE_MIN_N = 3584;  // reject_tiger_once_kernel from here up: 13 N + 8.3 KB of reject_tiger_lds_kernel no longer fit three times into a CU's 160 KB
 constexpr int REJECT_MAX_ATTEMPTS = 1 << 28;  // per update: beyond this the observation is taken to be impossible under the filter
 constexpr int IS_BLOCK      = 512;   // one workgroup per slot in the importance filter (same-box A/B on the bench shape: 1024 -> 37.3 ms, 512 -> 31.1, 256 -> 32.3: three workgroups per CU overlap their barrier-separated phases)
 constexpr int PARTICLE_TILE = 4096;  // particles one workgroup initialises / resets
@@ -31,6 +32,7 @@ inline size_t ca_hist_search_lds(const Problem& P)
 }
 
 void launch_search(const Problem& P, const DeviceState& D, hipStream_t st);
+bool search_takes_compact(const Problem& P, const DeviceState& D);   // launch_search would launch the instantiation that reads compact filters (fba_state.h)
 void launch_start(const Problem& P, const DeviceState& D, hipStream_t st);
 void launch_env(const Problem& P, const DeviceState& D, int32_t* n_active, hipStream_t st);
 void launch_advance(const Problem& P, const DeviceState& D, int32_t* n_active, hipStream_t st);
@@ -38,6 +40,7 @@ void launch_belief_update(const Problem& P, const DeviceState& D, hipStream_t st
 void launch_init(const Problem& P, const DeviceState& D, hipStream_t st);
 void launch_reset(const Problem& P, const DeviceState& D, hipStream_t st);
 void launch_materialize_reset(const Problem& P, const DeviceState& D, hipStream_t st);
+void launch_materialize_records(const Problem& P, const DeviceState& D, hipStream_t st);   // ... behind the compact filters' expansion (fba_state.h)
 void launch_flush(const Problem& P, const DeviceState& D, hipStream_t st);
 void launch_selftest_lgamma(const double* x, int count, double* out, hipStream_t st);
 void launch_selftest_bd(const Problem& P, const float* cnt, const float* prior, double* out, hipStream_t st);

@@ -825,10 +825,14 @@ __global__ void __launch_bounds__(BLK) reject_tiger_lds_kernel(Problem P, Device
 // listed and the listed sources gathered behind the loop, as above.
 // A slot that gives up at REJECT_MAX_ATTEMPTS has by then written part of its OTHER buffer: harmless, bufsel is not flipped, the filter
 // it holds is untouched and the next update overwrites that buffer.
+// The same holds for the compact flag (DeviceState::compact), which is written beside bufsel and nowhere else in here.
+// Compact filters (fba_state.h; D.compact_on, the experiment loop's launches only): on that clean path, after a `listen`, the record the
+// accepted thread stores is its four parked words with the state in bit 31 of the last -- one 16-byte store where there were four --
+// and the slot is flagged compact.  A compact source is swept by a straight copy of 16 N bytes into s_tab (no `other` test: nothing else
+// is stored; no s_st: the attempts take the state from bit 31 and mask it out of the word) and always yields a compact filter.
 // GATHER (reject_tiger_once_gather_kernel, FBA_TIGER_GATHER=1: same-box comparisons and tests): every slot gathers.
 // Same draws, same order, same result.  LDS: 68 KB + 16 dynamic, 8.4 KB static: two workgroups per CU.
 // ---------------------------------------------------------------------------------------------
-constexpr int TIGER_ONCE_MIN_N = 3584;   // 13 N + 8.3 KB of reject_tiger_lds_kernel no longer fit three times into a CU's 160 KB
 template <int BLK, bool GATHER>
 __device__ __forceinline__ void reject_tiger_once_body(Problem P, const DeviceState& D)
 {
@@ -854,7 +858,25 @@ __device__ __forceinline__ void reject_tiger_once_body(Problem P, const DeviceSt
     Rng g = slot_rng(P, D, e);
     REJECT_PROF_BEGIN
     uint32_t other = 0;
+    const bool csrc  = D.compact[e] != 0;   // the source is a compact filter (the loop's own `listen` update wrote it: a == 2)
     const uint4* src4 = reinterpret_cast<const uint4*>(scn);
+    // bit 31 of a compact record's fourth word is the state: the count in that half may not reach it in what is left of the run
+    const uint32_t room = 32767u - (uint32_t)min(32767, P.episodes * P.horizon);
+    if (csrc) {
+        // a straight copy of 16 N bytes, two records in flight per thread; the state rides in bit 31 of the fourth word, also in LDS
+        for (int i0 = tid; i0 < N; i0 += 2 * BLK) {
+            uint4 r[2];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) r[u] = i0 + u * BLK < N ? src4[i0 + u * BLK] : make_uint4(0u, 0u, 0u, 0u);
+            if (lazy) {
+                r[0].w = (r[0].w & 0x7fffffffu) | ((uint32_t)lazy_state(P, g, i0) << 31);
+                r[1].w = (r[1].w & 0x7fffffffu) | ((uint32_t)lazy_state(P, g, i0 + BLK) << 31);
+            }
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+                if (i0 + u * BLK < N) s_tab[i0 + u * BLK] = r[u];
+        }
+    } else
     for (int i0 = tid; i0 < N; i0 += 2 * BLK) {   // two records, eight 16-byte loads in flight per thread
         uint4 r[2][4];
 #pragma unroll
@@ -880,12 +902,17 @@ __device__ __forceinline__ void reject_tiger_once_body(Problem P, const DeviceSt
             const uint32_t o0 = (a == 0 ? 0u : q0.x) | (a == 1 ? 0u : q0.y) | (a == 2 ? 0u : q0.z) | (a == 0 ? 0u : q0.w);
             const uint32_t o1 = (a == 1 ? 0u : q1.x) | (a == 2 ? 0u : q1.y) | (a == 0 ? 0u : q1.z) | (a == 0 ? 0u : q1.w);
             const uint32_t o2 = (a == 1 ? 0u : q2.x) | (a == 1 ? 0u : q2.y) | (a == 2 ? 0u : q2.z) | (a == 2 ? 0u : q2.w);
-            other |= o0 | o1 | o2 | q3.y | q3.z | q3.w;
+            other |= (o0 | o1 | o2 | q3.y | q3.z | q3.w) != 0u ? 1u : 0u;
+            other |= (t.w >> 16) > room ? 2u : 0u;   // (only a filter the per-call interface drove: it stays in 64-byte records)
             s_tab[i] = t;
             s_st[i]  = (uint8_t)(lazy ? (uint32_t)ls[u] : q3.x);
         }
     }
-    const bool gather = __syncthreads_or(other != 0u) != 0 || GATHER;
+    const int swept   = __syncthreads_or((int)other);
+    const bool gather = (swept & 1) != 0 || GATHER;
+    // the new filter is compact: from a compact source always, from 64-byte records where the loop allows it, the step was a `listen` and
+    // nothing but its four words and the state is set
+    const bool cdst   = csrc || (D.compact_on != 0 && !gather && swept == 0 && a == 2);
     REJECT_PROF_MARK(0)
     const uint32_t m0 = (uint32_t) - (int)(a == 0), m1 = (uint32_t) - (int)(a == 1), m2 = (uint32_t) - (int)(a == 2);
     const uint32_t add_o = o ? 0x10000u : 1u;
@@ -902,10 +929,11 @@ __device__ __forceinline__ void reject_tiger_once_body(Problem P, const DeviceSt
         const int k = base + tid;
         g.stream(FBA_PHASE_REJECT, (uint32_t)k);
         const int src = P.point ? 0 : g.uniform_int(N);         // FlatFilter::sample
-        const int s0  = s_st[src];
+        uint4 t = s_tab[src];
+        const int s0  = csrc ? (int)(t.w >> 31) : (int)s_st[src];
+        if (csrc) t.w &= 0x7fffffffu;
         int s = s0, so;
         double r;
-        const uint4 t = s_tab[src];
         {
             const uint32_t wt = s0 ? t.y : t.x, wo0 = t.z, wo1 = t.w;
             tiger_step_packed(P, g, [&](int w) { return w < 6 ? wt : (w & 1 ? wo1 : wo0); }, s_prior, s, a, so, r, NoInc{});
@@ -929,11 +957,14 @@ __device__ __forceinline__ void reject_tiger_once_body(Problem P, const DeviceSt
                 // of scalar branches here).  Nothing waits for these stores: they drain under the next round's attempts.
                 const uint32_t add_t = s ? 0x10000u : 1u;
                 const uint32_t bx = t.x + (s0 ? 0u : add_t), by = t.y + (s0 ? add_t : 0u), bz = t.z + (s ? 0u : add_o), bw = t.w + (s ? add_o : 0u);
-                uint4* d = reinterpret_cast<uint4*>(dcn) + (size_t)j * 4;
-                d[0] = make_uint4(bx & m0, bx & m1, bx & m2, by & m0);
-                d[1] = make_uint4(by & m1, by & m2, bz & m0, bw & m0);
-                d[2] = make_uint4(bz & m1, bw & m1, bz & m2, bw & m2);
-                d[3] = make_uint4((uint32_t)s, 0u, 0u, 0u);
+                if (cdst) reinterpret_cast<uint4*>(dcn)[j] = make_uint4(bx, by, bz, bw | ((uint32_t)s << 31));   // the whole compact record
+                else {
+                    uint4* d = reinterpret_cast<uint4*>(dcn) + (size_t)j * 4;
+                    d[0] = make_uint4(bx & m0, bx & m1, bx & m2, by & m0);
+                    d[1] = make_uint4(by & m1, by & m2, bz & m0, bw & m0);
+                    d[2] = make_uint4(bz & m1, bw & m1, bz & m2, bw & m2);
+                    d[3] = make_uint4((uint32_t)s, 0u, 0u, 0u);
+                }
             } else {
                 s_acc[j] = (uint16_t)(src | (s0 << 12) | (s << 13));
             }
@@ -979,6 +1010,8 @@ __device__ __forceinline__ void reject_tiger_once_body(Problem P, const DeviceSt
         D.belief_steps[e] += (unsigned long long)s_count;
         D.upd_attempts[e] += (unsigned long long)s_count;
         D.upd_particles[e] += (unsigned long long)N;
+        if (cdst) (csrc ? D.upd_compact : D.upd_compact_full)[e] += (unsigned long long)N;
+        D.compact[e]          = cdst ? 1 : 0;   // (beside the bufsel flip: a slot that gave up above keeps its flag with its filter)
         D.need_update[e]      = 0;
         D.lazy_reset[e]       = 0;  // every record of the new buffer carries its real state
         D.cur[e].update_count = s_count;
@@ -2554,6 +2587,34 @@ __global__ void post_materialize_kernel(Problem P, DeviceState D)
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e < P.E) D.lazy_reset[e] = 0;
 }
+// A compact filter (fba_state.h) back into 64-byte records, for everything but the experiment loop's own kernels: from the first 16 N
+// bytes of the live buffer into the OTHER buffer -- the four `listen` words at 2, 5, 10, 11, the state at 12, zeros elsewhere: the very
+// record reject_tiger_once_kernel would have stored.  (A lazily reset slot's state bits are stale; materialize_reset_kernel, which the
+// launcher runs behind this, writes the real ones.)  post_expand_kernel then makes that buffer the live one and clears the flag.
+__global__ void __launch_bounds__(256) expand_compact_kernel(Problem P, DeviceState D)
+{
+    const int e = blockIdx.y, tid = threadIdx.x;
+    if (!D.compact[e]) return;
+    const int i_lo = blockIdx.x * PARTICLE_TILE, i_hi = min(P.N, i_lo + PARTICLE_TILE);
+    const int cur = D.bufsel[e];
+    const uint4* src = reinterpret_cast<const uint4*>(D.p_rec + pbase(P, e, cur) * (size_t)P.Cs);
+    uint4* dst       = reinterpret_cast<uint4*>(D.p_rec + pbase(P, e, cur ^ 1) * (size_t)P.Cs);
+    for (int i = i_lo + tid; i < i_hi; i += 256) {
+        const uint4 v = src[i];
+        uint4* d = dst + (size_t)i * 4;
+        d[0] = make_uint4(0u, 0u, v.x, 0u);
+        d[1] = make_uint4(0u, v.y, 0u, 0u);
+        d[2] = make_uint4(0u, 0u, v.z, v.w & 0x7fffffffu);
+        d[3] = make_uint4(v.w >> 31, 0u, 0u, 0u);
+    }
+}
+__global__ void post_expand_kernel(Problem P, DeviceState D)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= P.E || !D.compact[e]) return;
+    D.bufsel[e] ^= 1;
+    D.compact[e] = 0;
+}
 
 // clears the request flags after init_kernel / reset_kernel (several workgroups serve one slot)
 __global__ void post_init_kernel(Problem P, DeviceState D)
@@ -2561,6 +2622,7 @@ __global__ void post_init_kernel(Problem P, DeviceState D)
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= P.E) return;
     if (P.hist && D.need_init[e]) D.hist_cnt[e] = 0;
+    if (D.need_init[e]) D.compact[e] = 0;   // init_kernel has written the live buffer as 64-byte records
     if (P.mh && D.need_init[e]) {  // MHwithinGibbs::initiate :277-294
         D.mh_n_ep[e] = 1;
         D.mh_ep_len[(size_t)e * (P.episodes + 1)] = 0;
@@ -2693,10 +2755,11 @@ __global__ void __launch_bounds__(256) flush_kernel(Problem P, DeviceState D)
     __syncthreads();
     const SlotRecs r = slot_recs(P, D, e);
     const bool lazy  = slot_lazy(D, e);
+    const bool cmp   = D.compact[e] != 0;   // a compact filter (fba_state.h): records of four words, read through CompactTigerWords
     unsigned long long local = 0;
     for (int i = tid; i < P.N; i += 256) {
-        const float* cnt = r.rec + (size_t)i * r.stride;
-        const int st = lazy ? lazy_state(P, D, e, i) : rec_state(cnt, P.C);
+        const float* cnt = r.rec + (size_t)i * (cmp ? 4 : r.stride);
+        const int st = lazy ? lazy_state(P, D, e, i) : (cmp ? (int)(__float_as_uint(cnt[3]) >> 31) : rec_state(cnt, P.C));
         if (hist_on && (unsigned)st < (unsigned)FBA_TRACE_HIST_BINS) atomicAdd(&s_hist[st], 1u);
         uint64_t h = mix64((uint64_t)i * 0x9E3779B97F4A7C15ull + (uint64_t)(uint32_t)st);
         const double w = (P.belief == FBA_BELIEF_IMPORTANCE) ? D.p_weight[r.wb + i] : 0.0;
@@ -2715,8 +2778,9 @@ __global__ void __launch_bounds__(256) flush_kernel(Problem P, DeviceState D)
         else if (P.hist) h = hist_hash_counts(P, reinterpret_cast<const uint32_t*>(cnt), r.cnt, h);
         else if (P.packed) {  // the checksum is over the counts themselves, whatever the storage (PackedView)
             const PackedView<GlobalView> pv{GlobalView{cnt}, D.prior_dense};
+            const PackedView<CompactTigerWords> cv{CompactTigerWords{cnt}, D.prior_dense};
             const int dense = P.phi_len + P.A * P.S * P.O;
-            for (int k = 0; k < dense; ++k) h = mix64(h ^ ((uint64_t)__float_as_uint(pv.at(k)) + ((uint64_t)k << 32)));
+            for (int k = 0; k < dense; ++k) h = mix64(h ^ ((uint64_t)__float_as_uint(cmp ? cv.at(k) : pv.at(k)) + ((uint64_t)k << 32)));
         } else
             for (int k = 0; k < P.C; ++k) h = mix64(h ^ ((uint64_t)__float_as_uint(cnt[k]) + ((uint64_t)k << 32)));
         local += h;
@@ -3033,6 +3097,14 @@ void launch_materialize_reset(const Problem& P, const DeviceState& D, hipStream_
 {
     hipLaunchKernelGGL(materialize_reset_kernel, dim3(ceil_div(P.N, PARTICLE_TILE), P.E), dim3(256), 0, st, P, D);
     hipLaunchKernelGGL(post_materialize_kernel, dim3(ceil_div(P.E, 256)), dim3(256), 0, st, P, D);
+}
+// launch_materialize_reset for a context whose experiment loop may have left compact filters (the host knows: fba_engine.hip
+// materialize_records): those first, then the pending lazy resets, so that every slot holds 64-byte records with their real states
+void launch_materialize_records(const Problem& P, const DeviceState& D, hipStream_t st)
+{
+    hipLaunchKernelGGL(expand_compact_kernel, dim3(ceil_div(P.N, PARTICLE_TILE), P.E), dim3(256), 0, st, P, D);
+    hipLaunchKernelGGL(post_expand_kernel, dim3(ceil_div(P.E, 256)), dim3(256), 0, st, P, D);
+    launch_materialize_reset(P, D, st);
 }
 void launch_reset(const Problem& P, const DeviceState& D, hipStream_t st)
 {

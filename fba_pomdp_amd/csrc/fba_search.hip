@@ -175,7 +175,16 @@ __global__ void __launch_bounds__(SEARCH_BLOCK) search_kernel(Problem P, DeviceS
     int4* tab      = hash_table(D, e);
     const uint32_t epoch = D.hash ? hash_begin_search(D, e, tab, 0, 1) : 0;
 
-    const bool lazy = slot_lazy(D, e);  // particle states are still the episode's start-state draws (lazy_state)
+    // bit 0: particle states are still the episode's start-state draws (lazy_state); bit 1 (packed episodic tiger only): the slot's
+    // filter is compact (fba_state.h) -- a root sample is ONE 16-byte load, its four `listen` words staged where tiger_step_packed reads
+    // them.  The other count words of such a record are zero by construction: staged once, here
+    constexpr bool COMPACT = TIGER_TABLE == 2 && ETIGER;
+    const int lazy_c = (slot_lazy(D, e) ? 1 : 0) | (COMPACT && D.compact[e] ? 2 : 0);
+    if (COMPACT && (lazy_c & 2)) {
+#pragma unroll
+        for (int w = 0; w < 10; ++w)
+            if (w != 2 && w != 5) stage[w * SEARCH_BLOCK] = 0.f;
+    }
     // -P ts: TSPlanner / BATSPlanner (src/planners/ts/TSPlanner.cpp:16-29, bayes-adaptive/BATSPlanner.cpp:19-34) sample
     // the belief once and plan on that point estimate, whose sample() draws nothing: every simulation starts
     // from the same particle and its stream begins with the UCB tie-break.
@@ -199,7 +208,15 @@ __global__ void __launch_bounds__(SEARCH_BLOCK) search_kernel(Problem P, DeviceS
             int nest_state = ts_state;
             const int src = ts_src >= 0 ? ts_src : (nested ? nested_sample(P, D, e, g, nest_state) : belief_sample_uniform(P, D, g));
             cnt = prec + (size_t)src * P.Cs;
-            if (STAGE) {
+            if (COMPACT && (lazy_c & 2)) {
+                const uint4 v = reinterpret_cast<const uint4*>(prec)[src];
+                stage[2 * SEARCH_BLOCK]  = __uint_as_float(v.x);
+                stage[5 * SEARCH_BLOCK]  = __uint_as_float(v.y);
+                stage[10 * SEARCH_BLOCK] = __uint_as_float(v.z);
+                stage[11 * SEARCH_BLOCK] = __uint_as_float(v.w & 0x7fffffffu);
+                s = (int)(v.w >> 31);
+                stage[12 * SEARCH_BLOCK] = __int_as_float(s);
+            } else if (STAGE) {
                 const float4* rp = reinterpret_cast<const float4*>(cnt);
                 const int n4 = (P.C + 4) >> 2;  // counts and the state word; the padding behind them is not needed
                 // up to twelve 16-byte loads in flight before the first of them is waited for: with a trip count the compiler does
@@ -224,7 +241,7 @@ __global__ void __launch_bounds__(SEARCH_BLOCK) search_kernel(Problem P, DeviceS
             } else {
                 s = rec_state(cnt, P.C);
             }
-            if (lazy) s = lazy_state(P, g, src);   // (from g's own registers: no load behind the record's)
+            if (lazy_c & 1) s = lazy_state(P, g, src);   // (from g's own registers: no load behind the record's)
             if (nested) s = nest_state;
             node = 0; dtg = max_tree_depth; plen = 0; mode = 1;
         }
@@ -1161,6 +1178,15 @@ void launch_search(const Problem& P, const DeviceState& D, hipStream_t st)
     else FBA_LAUNCH_SEARCH_M(false, 24, FBA_MODEL_POMDP);  // agr (23 actions) is a POMDP-only domain
 #undef FBA_LAUNCH_SEARCH_M
 #undef FBA_LAUNCH_SEARCH
+}
+// launch_search's own conditions for search_kernel<true, 4, false, 2, FBA_MODEL_BA_TABLE, 0, false, false, true>, the one instantiation
+// that reads compact filters (fba_state.h): fba_create asks before it lets a context keep them
+bool search_takes_compact(const Problem& P, const DeviceState& D)
+{
+    const bool stage = P.model != FBA_MODEL_POMDP && P.Cs <= SEARCH_STAGE_WORDS;
+    const bool tiger_table = P.model == FBA_MODEL_BA_TABLE && P.planner == FBA_PLANNER_POUCT && !P.dirichlet_regular && stage &&
+                             (P.domain == FBA_DOM_TIGER_EPISODIC || P.domain == FBA_DOM_TIGER_CONTINUOUS) && !D.hash;
+    return tiger_table && P.packed && !D.ab_no_etiger && !P.hist && etiger_ok(P, D) && P.search_budget <= 0;
 }
 #ifdef FBA_PROFILE_SEARCH
 extern "C" int fba_debug_search_profile(unsigned long long* out, int reset)

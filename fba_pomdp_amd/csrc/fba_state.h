@@ -53,6 +53,15 @@ struct DeviceState {
     uint8_t* bufsel_fc; // [E]
     double* lik;        // [E] cheating belief: CheatingReinvigoration::_likelihood; [E] holds the threshold
     uint8_t* lazy_reset;  // [E] rejection filter: resetDomainStateDistribution is pending -- particle i's state is the RESET-stream draw, not the record's word
+    // Between two updates of the experiment loop an episodic-tiger slot may hold its filter COMPACT: one 16-byte record per particle in the
+    // first 16 N bytes of the live buffer -- the four `listen` words {T(0,L,.), T(1,L,.), O(L,0,.), O(L,1,.)} of the packed record (words 2,
+    // 5, 10, 11), the state in bit 31 of the fourth (free: compact_on needs episodes * horizon <= 32767).  Only reject_tiger_once_kernel
+    // writes one, only it, the ETIGER packed search and flush_kernel read one; launch_materialize_records turns every such slot back into
+    // 64-byte records in front of everything else that touches p_rec
+    uint8_t* compact;   // [E] the slot's filter is compact
+    int8_t compact_on;  // this launch may leave slots compact (set by tick() in a context that fba_create found eligible; 0 in every per-call launch)
+    unsigned long long* upd_compact_full;  // [E] particles written compact from 64-byte sources
+    unsigned long long* upd_compact;       // [E] particles written compact from compact sources
     int32_t* fault;     // [1] 0, or 1 + the slot whose rejection update exceeded REJECT_MAX_ATTEMPTS (host reports it)
     uint8_t* cheat_pending;  // [E] the update of this tick pushed log(likelihood) below the threshold (mh-within-gibbs: an update has run, mh_kernel has work)
     // mh-within-gibbs belief: the run's (action, observation) history by episode; lik[e] is the log likelihood, lik[E] the threshold

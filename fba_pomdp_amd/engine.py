@@ -149,6 +149,12 @@ class Engine:
         self._chk(self.L.fba_get_kernel_times(self.h, kt))
         return {N.KERNEL_NAMES[i]: kt[i] for i in range(N.K_COUNT)}
 
+    def debug_compact_slots(self):
+        """Diagnostic: how many slots hold their filter as 16-byte records right now."""
+        n = C.c_int32(0)
+        self._chk(self.L.fba_debug_compact_slots(self.h, C.byref(n)))
+        return n.value
+
     def reset_kernel_times(self):
         self._chk(self.L.fba_reset_kernel_times(self.h))
 
