@@ -71,6 +71,7 @@ struct fba_ctx {
     double k_ms[FBA_K_COUNT]          = {0};
     uint64_t k_launches[FBA_K_COUNT]  = {0};
     uint64_t base_sim = 0, base_attempts = 0, base_particles = 0, base_entries = 0, base_compact_full = 0, base_compact = 0;
+    uint64_t restored_particles = 0, restored_bytes = 0;   // resumed spans since fba_reset_kernel_times: particles taken from blocks, bytes read and written
     std::vector<fba_trace_rec> trace_host;
     // compact filters (fba_state.h): the experiment loop of this context may keep them (plan_filters), and a tick has run that way since
     // the last materialize_records
@@ -1082,6 +1083,13 @@ void materialize_records(fba_ctx* c, bool reset = false)
     c->D.compact_on  = 0;   // the per-call launches never leave a slot compact
 }
 
+// Belief::initiate of the slots that start a run: drawn from the prior, or -- in a resumed span -- taken from the snapshot store
+void launch_initiate(fba_ctx* c)
+{
+    if (c->D.restore_store) launch_restore(c->P, c->D, c->stream);
+    else launch_init(c->P, c->D, c->stream);
+}
+
 // one real time-step of every active slot
 int tick(fba_ctx* c)
 {
@@ -1094,7 +1102,7 @@ int tick(fba_ctx* c)
     if ((rc = timed(c, k_update_kind(c), [&] { launch_belief_update(c->P, c->D, c->stream); }))) return rc;
     if (c->D.trace_on) launch_flush(c->P, c->D, c->stream);
     launch_advance(c->P, c->D, c->d_n_active, c->stream);
-    if ((rc = timed(c, FBA_K_BELIEF_INIT, [&] { launch_init(c->P, c->D, c->stream); }))) return rc;
+    if ((rc = timed(c, FBA_K_BELIEF_INIT, [&] { launch_initiate(c); }))) return rc;
     if (c->P.model != FBA_MODEL_POMDP)
         if ((rc = timed(c, FBA_K_BELIEF_RESET, [&] { launch_reset(c->P, c->D, c->stream); }))) return rc;
     HIPCHK(c, hipGetLastError());
@@ -1162,13 +1170,16 @@ int clear_parked_searches(fba_ctx* c)
     return FBA_OK;
 }
 
-int start_experiment(fba_ctx* c, int runs_total)
+// first_episode, stop_episode: the span of every run (stop_episode < 0: to the last episode)
+int start_experiment(fba_ctx* c, int runs_total, int first_episode = 0, int stop_episode = -1)
 {
     int rc;
     if ((rc = clear_parked_searches(c))) return rc;
     materialize_records(c);   // (bufsel is rewritten below)
     c->D.runs_total = runs_total;
     c->D.run_offset = c->cfg.run_offset;
+    c->D.first_episode = first_episode;
+    c->D.stop_episode  = stop_episode < 0 ? c->P.episodes : stop_episode;
     const int32_t n_active = runs_total < 0 ? c->P.E : std::min(c->P.E, runs_total);
     HIPCHK(c, hipMemcpyAsync(c->d_n_active, &n_active, sizeof n_active, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(c->D.bufsel, 0, (size_t)c->P.E, c->stream));
@@ -1176,7 +1187,7 @@ int start_experiment(fba_ctx* c, int runs_total)
     if (c->D.bufsel_fc) HIPCHK(c, hipMemsetAsync(c->D.bufsel_fc, 0, (size_t)c->P.E, c->stream));
     if (c->D.bufsel_sh) HIPCHK(c, hipMemsetAsync(c->D.bufsel_sh, 0, (size_t)c->P.E, c->stream));
     launch_start(c->P, c->D, c->stream);
-    if ((rc = timed(c, FBA_K_BELIEF_INIT, [&] { launch_init(c->P, c->D, c->stream); }))) return rc;
+    if ((rc = timed(c, FBA_K_BELIEF_INIT, [&] { launch_initiate(c); }))) return rc;
     if (c->P.model != FBA_MODEL_POMDP)
         if ((rc = timed(c, FBA_K_BELIEF_RESET, [&] { launch_reset(c->P, c->D, c->stream); }))) return rc;
     HIPCHK(c, hipGetLastError());
@@ -1184,13 +1195,15 @@ int start_experiment(fba_ctx* c, int runs_total)
     return FBA_OK;
 }
 
-int run_experiment(fba_ctx* c, fba_stat* stats)
+// Episodes [first, stop) of every run (stop < 0: all of them).  block_updates: what the blocks of a resumed span had counted (SpanStore), or null
+int run_experiment(fba_ctx* c, fba_stat* stats, int first = 0, int stop = -1, const std::vector<uint32_t>* block_updates = nullptr)
 {
     int rc;
     const int runs = c->cfg.runs, E = c->P.E, eps = c->P.episodes;
+    if (stop < 0) stop = eps;
     if ((rc = ensure_outputs(c, runs))) return rc;
-    if ((rc = start_experiment(c, runs))) return rc;
-    long long max_ticks = (long long)((runs + E - 1) / E) * eps * c->P.horizon + 2;
+    if ((rc = start_experiment(c, runs, first, stop))) return rc;
+    long long max_ticks = (long long)((runs + E - 1) / E) * (stop - first) * c->P.horizon + 2;
     if (c->P.search_budget > 0)   // budgeted launches: a real step takes as many launches as its search needs (<= horizon + 1 iterations per simulation)
         max_ticks *= ((long long)c->P.sims * (c->P.horizon + 1)) / c->P.search_budget + 2;
     for (long long k = 0; k < max_ticks; ++k) {
@@ -1205,7 +1218,20 @@ int run_experiment(fba_ctx* c, fba_stat* stats)
     HIPCHK(c, hipMemcpy(ret.data(), c->D.returns, ret.size() * sizeof(double), hipMemcpyDeviceToHost));
     std::memset(stats, 0, sizeof(fba_stat) * (size_t)eps);
     for (int r = 0; r < runs; ++r)
-        for (int ep = 0; ep < eps; ++ep) fba_stat_add(&stats[ep], ret[(size_t)r * eps + ep]);
+        for (int ep = first; ep < stop; ++ep) fba_stat_add(&stats[ep], ret[(size_t)r * eps + ep]);
+    if (c->P.packed || c->P.ft_packed) {
+        // what a snapshot header says of a slot's uint16 increments (fba_snapshot_head::updates): the filter a slot is left with is that of
+        // its last run, which has made one update per real step at most, on top of what its block had counted
+        std::vector<int32_t> len((size_t)runs * eps);
+        HIPCHK(c, hipMemcpy(len.data(), c->D.lengths, len.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (c->packed_updates.size() != (size_t)E) c->packed_updates.assign((size_t)E, 0);
+        for (int e = 0; e < E && e < runs; ++e) {
+            const int r = e + E * ((runs - 1 - e) / E);
+            uint32_t n = block_updates ? (*block_updates)[(size_t)r % block_updates->size()] : 0u;
+            for (int ep = first; ep < stop; ++ep) n += (uint32_t)len[(size_t)r * eps + ep];
+            c->packed_updates[(size_t)e] = n;
+        }
+    }
     c->started = false;
     return FBA_OK;
 }
@@ -3203,6 +3229,111 @@ int fba_run_bapomdp(fba_ctx* c, fba_stat* stats)
     return run_experiment(c, stats);
 }
 
+namespace {
+// the device-resident blocks of a resumed span: the context's DeviceState points into them while the call runs, and on no way out beyond it
+struct SpanStore {
+    fba_ctx* c;
+    uint8_t* p = nullptr;
+    explicit SpanStore(fba_ctx* ctx) : c(ctx) {}
+    ~SpanStore()
+    {
+        c->D.restore_store = nullptr; c->D.restore_pitch = 0; c->D.restore_nblocks = 0;
+        if (p) { (void)hipStreamSynchronize(c->stream); (void)hipFree(p); }
+    }
+};
+}  // namespace
+
+int fba_run_bapomdp_span(fba_ctx* c, int32_t first, int32_t stop, const void* blocks, int32_t nblocks, int64_t bytes, fba_stat* stats)
+{
+    static const char* const call = "fba_run_bapomdp_span";
+    if (!c || !stats) return FBA_EINVAL;
+    if (c->P.model == FBA_MODEL_POMDP) return fail(c, FBA_EINVAL, "%s: bapomdp::run needs a Bayes-adaptive model", call);
+    if (const char* extra = snapshot_extra_state(c))
+        return fail(c, FBA_EINVAL, "%s: a span is continued from snapshots, a snapshot holds the main filter of a slot, and %s", call, extra);
+    const Problem& P = c->P;
+    if (first < 0 || stop <= first || stop > P.episodes)
+        return fail(c, FBA_EINVAL, "%s: episodes [%d, %d) are not a span within the context's %d", call, first, stop, P.episodes);
+    if (!blocks) {
+        if (first != 0 || nblocks != 0)
+            return fail(c, FBA_EINVAL, "%s: without blocks a run starts from the prior, at episode 0 (first_episode %d, nblocks %d)", call, first, nblocks);
+        return run_experiment(c, stats, 0, stop);
+    }
+    if (nblocks != 1 && nblocks != c->cfg.runs)
+        return fail(c, FBA_EINVAL, "%s: nblocks %d: one block for every run (1) or one per run (%d)", call, nblocks, c->cfg.runs);
+    int rc;
+    BeliefSnapshotArgs a;
+    ScratchBuf<uint32_t> d_limit;
+    if ((rc = snapshot_args(c, a, d_limit))) return rc;
+    const int64_t per = a.per_slot;
+    const uint8_t* in = static_cast<const uint8_t*>(blocks);
+    const fba_snapshot::Accepts acc = snapshot_accepts(c);
+    if (bytes != (int64_t)nblocks * per) {
+        char msg[256];
+        if (bytes >= (int64_t)sizeof(fba_snapshot_head) && fba_snapshot::check_head(in, per, acc, msg, sizeof msg))
+            return fail(c, FBA_EINVAL, "%s: block 0: %s", call, msg);
+        return fail(c, FBA_EINVAL, "%s: bytes %lld / %lld (%d blocks of %lld)", call, (long long)bytes, (long long)nblocks * per, nblocks, (long long)per);
+    }
+    // ---- host pass: every header, and the room the span needs in every block ----
+    std::vector<fba_snapshot_head> heads((size_t)nblocks);
+    for (int b = 0; b < nblocks; ++b) {
+        char msg[320];
+        if (fba_snapshot::check_head(in + (size_t)b * (size_t)per, per, acc, msg, sizeof msg)) return fail(c, FBA_EINVAL, "%s: block %d: %s", call, b, msg);
+        if (fba_snapshot::check_span_room(in + (size_t)b * (size_t)per, b, first, stop, P.episodes, P.horizon, msg, sizeof msg))
+            return fail(c, FBA_EINVAL, "%s: %s", call, msg);
+        std::memcpy(&heads[(size_t)b], in + (size_t)b * (size_t)per, sizeof(fba_snapshot_head));
+    }
+    // ---- the store, and the device pass over it a chunk at a time: checksum and every record of every block ----
+    const int64_t pad = snapshot_store_pad(a.weighted, P.N), pitch = snapshot_store_pitch(per, a.weighted, P.N);
+    SpanStore store(c);
+    if (hipMalloc(reinterpret_cast<void**>(&store.p), (size_t)nblocks * (size_t)pitch) != hipSuccess) {
+        (void)hipGetLastError();
+        store.p = nullptr;
+        return fail(c, FBA_EHIP, "%s: no device memory for a store of %lld bytes (%d blocks of %lld)", call, (long long)nblocks * (long long)pitch, nblocks,
+                    (long long)pitch);
+    }
+    const int chunk = snapshot_chunk(per, nblocks);
+    ScratchBuf<unsigned long long> d_check;   // [chunk] checksums, then the error word
+    HIPCHK(c, d_check.alloc((size_t)chunk + 1));
+    std::vector<unsigned long long> h_check((size_t)chunk + 1);
+    const int inc_words = P.packed ? P.C : (P.ft_packed ? c->fdesc.ncounts / 2 : 0);   // the words of a packed record that hold two uint16 increments
+    for (int done = 0; done < nblocks; done += chunk) {
+        const int n = std::min(chunk, nblocks - done);
+        a.first = 0; a.count = n; a.stage = store.p + (size_t)done * (size_t)pitch + (size_t)pad; a.per_slot = pitch;
+        a.check = d_check.p; a.bad = d_check.p + chunk;
+        HIPCHK(c, hipMemcpy2DAsync(a.stage, (size_t)pitch, in + (size_t)done * (size_t)per, (size_t)per, (size_t)per, (size_t)n, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemsetAsync(d_check.p, 0, (size_t)chunk * 8, c->stream));
+        HIPCHK(c, hipMemsetAsync(a.bad, 0xff, 8, c->stream));
+        launch_snapshot_validate(P, c->D, a, c->stream);
+        launch_span_increments(P, a, inc_words, c->stream);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(h_check.data(), d_check.p, ((size_t)chunk + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (int b = 0; b < n; ++b)
+            if (h_check[(size_t)b] != heads[(size_t)(done + b)].checksum)
+                return fail(c, FBA_EINVAL, "%s: block %d: checksum %016llx in the header, %016llx over the payload", call, done + b,
+                            (unsigned long long)heads[(size_t)(done + b)].checksum, h_check[(size_t)b]);
+        const unsigned long long bad = h_check[(size_t)chunk];
+        if (bad != ~0ull) {
+            static const char* const what_names[] = {"", "a weight that is negative or not finite", "a state outside the domain", "an illegal parent-set word",
+                                                     "a history entry outside the domain's tables", "a count that is negative or not finite",
+                                                     "an increment beyond the updates its header counts"};
+            const int b = done + (int)(bad >> 40), what = (int)(bad & 0xffu);
+            return fail(c, FBA_EINVAL, "%s: block %d, particle %lld: %s", call, b, (long long)((bad >> 8) & 0xffffffffull),
+                        what >= 1 && what <= 6 ? what_names[what] : "an invalid record");
+        }
+    }
+    // ---- every block is one this context can run from: the experiment, with the store in Belief::initiate's place ----
+    c->D.restore_store = store.p; c->D.restore_pitch = pitch; c->D.restore_nblocks = nblocks;
+    std::vector<uint32_t> updates((size_t)nblocks);
+    for (int b = 0; b < nblocks; ++b) updates[(size_t)b] = heads[(size_t)b].updates;
+    if ((rc = run_experiment(c, stats, first, stop, &updates))) return rc;
+    for (int r = 0; r < c->cfg.runs; ++r) {   // every run has taken its block once
+        c->restored_particles += (uint64_t)P.N;
+        c->restored_bytes += 2 * (uint64_t)P.N * ((uint64_t)heads[(size_t)(r % nblocks)].stride + (a.weighted ? 8u : 0u));
+    }
+    return FBA_OK;
+}
+
 int fba_run_ticks(fba_ctx* c, int32_t ticks)
 {
     if (!c || ticks < 0) return FBA_EINVAL;
@@ -3310,6 +3441,9 @@ int fba_get_kernel_times(fba_ctx* c, fba_kernel_time* out)
         out[k].bytes = 0;
     }
     out[FBA_K_SEARCH].units = sim;
+    // restore_kernel (resumed spans): a particle's record at the block's stride and its weight, read from the store and written to the slot
+    out[FBA_K_BELIEF_INIT].units = c->restored_particles;
+    out[FBA_K_BELIEF_INIT].bytes = c->restored_bytes;
     if (P.belief == FBA_BELIEF_REJECTION) {
         out[FBA_K_BELIEF_RS].units = particles;
         out[FBA_K_BELIEF_RS].bytes = attempts * (Pb + Rt + Ro) + particles * Pb;
@@ -3381,6 +3515,7 @@ int fba_reset_kernel_times(fba_ctx* c)
     int rc = flush_events(c);
     if (rc) return rc;
     for (int k = 0; k < FBA_K_COUNT; ++k) { c->k_ms[k] = 0; c->k_launches[k] = 0; }
+    c->restored_particles = c->restored_bytes = 0;
     c->base_sim       = sum_counter(c, c->D.sim_steps, c->P.E, &rc);
     c->base_attempts  = sum_counter(c, c->D.upd_attempts, c->P.E, &rc);
     c->base_particles = sum_counter(c, c->D.upd_particles, c->P.E, &rc);

@@ -134,7 +134,7 @@ void launch_belief_probe(const Problem& P, const DeviceState& D, const BeliefPro
 // states it (fba_snapshot_head, weights, records); slot first + b owns block b.  All state of the feature is in these arguments
 constexpr int SNAPSHOT_MAX_SLOTS = 32768;            // slots of one launch (a grid row each)
 constexpr size_t SNAPSHOT_STAGE_BYTES = (size_t)256 << 20;   // staging memory of one export / import chunk (one block at least)
-enum { SNAP_BAD_WEIGHT = 1, SNAP_BAD_STATE = 2, SNAP_BAD_STRUCTURE = 3, SNAP_BAD_ENTRY = 4, SNAP_BAD_COUNT = 5 };
+enum { SNAP_BAD_WEIGHT = 1, SNAP_BAD_STATE = 2, SNAP_BAD_STRUCTURE = 3, SNAP_BAD_ENTRY = 4, SNAP_BAD_COUNT = 5, SNAP_BAD_INCREMENT = 6 };
 struct BeliefSnapshotArgs {
     int32_t first, count;
     uint8_t* stage;                 // [count][per_slot]
@@ -151,6 +151,16 @@ void launch_snapshot_pack(const Problem& P, const DeviceState& D, const BeliefSn
 void launch_snapshot_validate(const Problem& P, const DeviceState& D, const BeliefSnapshotArgs& a, hipStream_t st);  // import, first pass
 void launch_snapshot_commit(const Problem& P, const DeviceState& D, const BeliefSnapshotArgs& a, hipStream_t st);    // import, second pass
 void launch_snapshot_replicate(const Problem& P, const DeviceState& D, int src, int first, int count, hipStream_t st);
+// where block b of a snapshot store stands (DeviceState::restore_store): b * pitch + pad, so that the record part of every block starts at a
+// multiple of 16 bytes -- the weights of an odd particle count would leave it at 8
+__host__ __device__ inline int64_t snapshot_store_pad(int weighted, int64_t particles) { return weighted && (particles & 1) ? 8 : 0; }
+inline int64_t snapshot_store_pitch(int64_t per_slot, int weighted, int64_t particles) { return (per_slot + snapshot_store_pad(weighted, particles) + 15) & ~(int64_t)15; }
+// fba_restore.hip: the experiment loop's Belief::initiate of a resumed span, launched in launch_init's place while DeviceState::restore_store is set
+void launch_restore(const Problem& P, const DeviceState& D, hipStream_t st);
+// ... and the one thing a resumed span asks of a packed block beyond what an import judges: none of the 16-bit increments in the first
+// inc_words words of a record exceeds head.updates.  Over the `count` blocks validated last (a.stage, a.per_slot, a.bad as for
+// launch_snapshot_validate: the smallest block << 40 | particle << 8 | SNAP_BAD_INCREMENT met)
+void launch_span_increments(const Problem& P, const BeliefSnapshotArgs& a, int inc_words, hipStream_t st);
 void launch_uniform_scan(int n, double* w_tmp, double* out, double* total, double* ctot, hipStream_t st);
 
 }  // namespace fba

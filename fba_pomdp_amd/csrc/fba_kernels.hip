@@ -40,7 +40,7 @@ __global__ void start_kernel(Problem P, DeviceState D)
     const int run  = D.run_offset + e;
     const bool on  = D.runs_total < 0 || e < D.runs_total;
     D.run[e]       = run;
-    D.episode[e]   = 0;
+    D.episode[e]   = D.first_episode;
     D.active[e]    = on;
     D.need_update[e] = 0;
     D.adv[e]         = 0;
@@ -114,7 +114,7 @@ __global__ void advance_kernel(Problem P, DeviceState D, int32_t* n_active)
     if (adv == 1) { D.t[e] += 1; return; }
     if (adv != 2) return;
     int run = D.run[e], ep = D.episode[e] + 1;
-    if (ep < P.episodes) {
+    if (ep < D.stop_episode) {
         D.episode[e]    = ep;
         D.need_reset[e] = P.model != FBA_MODEL_POMDP;
     } else {
@@ -125,7 +125,7 @@ __global__ void advance_kernel(Problem P, DeviceState D, int32_t* n_active)
             return;
         }
         D.run[e]        = run;
-        D.episode[e]    = 0;
+        D.episode[e]    = D.first_episode;
         D.need_init[e]  = 1;
         D.need_reset[e] = P.model != FBA_MODEL_POMDP;
     }

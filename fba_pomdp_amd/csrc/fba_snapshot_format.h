@@ -143,4 +143,25 @@ inline int check_head(const void* block, int64_t avail, const Accepts& acc, char
     return 0;
 }
 
+// The room rule of a resumed span (fba_run_bapomdp_span): a run that continues from this block through episodes [first, stop) must never
+// hold more than an uninterrupted run of a context of `episodes` episodes of `horizon` steps could -- every bound fba_create derives from
+// episodes * horizon (the entries a history record has room for, the uint16 increments of a packed record, the 15 bits a 16-byte tiger
+// record keeps of one, the exactness of prior + j) then holds as it does there.  What the block holds already: the entries per record
+// of a history format, head.updates of a packed one; fp32 counts (format 0) have no such bound.  A step makes one update at most.
+// 0 = there is room; -1 = refused, with the block, both numbers and the span in msg.  Reads the 64 bytes of the header only.
+inline int check_span_room(const void* block, int block_index, int32_t first, int32_t stop, int32_t episodes, int32_t horizon, char* msg, size_t msg_len)
+{
+    fba_snapshot_head h;
+    memcpy(&h, block, sizeof h);
+    if (h.record_format == 0) return 0;
+    const bool hist     = h.record_format >= 5;
+    const int64_t held  = hist ? (int64_t)history_total(h.hist_cnt) : (int64_t)h.updates;
+    const int64_t more  = ((int64_t)stop - (int64_t)first) * (int64_t)horizon, room = (int64_t)episodes * (int64_t)horizon;
+    if (held + more <= room) return 0;
+    snprintf(msg, msg_len, "block %d holds %lld %s, episodes [%d, %d) of %d steps may add %lld: %lld / %lld (episodes * horizon) a run of this context holds",
+             block_index, (long long)held, hist ? "history entries per record" : "counted updates", (int)first, (int)stop, (int)horizon, (long long)more,
+             (long long)(held + more), (long long)room);
+    return -1;
+}
+
 }  // namespace fba_snapshot

@@ -149,6 +149,15 @@ struct DeviceState {
     int32_t* lengths;   // [runs][episodes]
     int32_t runs_total; // run indices >= run_offset + runs_total are not executed (<0: unbounded)
     int32_t run_offset;
+    // the episode span of the experiment loop (fba_run_bapomdp_span): a slot starts its runs at first_episode and ends them in front of
+    // stop_episode; start_experiment sets both, 0 and Problem::episodes unless a span was asked for
+    int32_t first_episode, stop_episode;
+    // the snapshot store of a resumed span, null otherwise: restore_nblocks (1 or the runs) blocks as include/fba_hip.h lays them out, block b
+    // at restore_store + b * restore_pitch, so placed that its record part stands at a multiple of 16 bytes.  While it is set, a slot
+    // with need_init takes block (run - run_offset) % restore_nblocks as its filter instead of drawing one (restore_kernel, fba_snapshot.hip)
+    const uint8_t* restore_store;
+    int64_t restore_pitch;
+    int32_t restore_nblocks;
     unsigned long long* sim_steps;    // [E]
     unsigned long long* belief_steps; // [E]
     unsigned long long* env_steps;    // [E]

@@ -21,6 +21,7 @@
 #include <chrono>
 #include <fstream>
 #include <iostream>
+#include <iterator>
 #include <map>
 #include <stdexcept>
 #include <string>
@@ -34,9 +35,9 @@ namespace {
 struct Options {
     std::string mode;
     std::string domain, planner = "po-uct", belief = "rejection_sampling", seed, output_file = "results.txt", structure_prior,
-                                dirichlet = "expected", id, belief_option, probe_file, probe_slots;
+                                dirichlet = "expected", id, belief_option, probe_file, probe_slots, belief_in, belief_out;
     int verbose = 0, runs = 1, horizon = 10, sims = 1000, max_depth = -1, particles = 100, size = 0, height = 0, width = 0,
-        episodes = 1, slots = 0, device = 0, resample_amount = 0;
+        episodes = 1, slots = 0, device = 0, resample_amount = 0, first_episode = 0, stop_episode = -1;
     double discount = .95, exploration = 100, threshold = 0;
     float noise = 0, counts_total = 10000;
     bool help = false;
@@ -78,7 +79,12 @@ void usage()
         "      --slots N  --device N      runs resident at once on the GPU (auto), HIP device (0)\n"
         "      --probe-file FILE          (bapomdp, fbapomdp) one line per real step that a belief update follows:\n"
         "                                 run episode t action obs state evidence next_true post_true (fba_probe)\n"
-        "      --probe-slots FIRST:COUNT  the slots whose steps are probed (all)");
+        "      --probe-slots FIRST:COUNT  the slots whose steps are probed (all)\n"
+        "      --first-episode K          (bapomdp, fbapomdp) run episodes [K, M) of every run only (0, --episodes): the result file\n"
+        "      --stop-episode M           has one line per episode of the span\n"
+        "      --belief-in FILE           the filters the runs continue from at episode K: one snapshot block for every run, or one\n"
+        "                                 per run, concatenated (what --belief-out of the span that ended at K wrote)\n"
+        "      --belief-out FILE          every run's filter when the span is over (needs runs <= slots)");
 }
 
 bool parse(int argc, char** argv, Options& o, std::string& err)
@@ -132,6 +138,10 @@ bool parse(int argc, char** argv, Options& o, std::string& err)
             else if (k == "--slots") o.slots = std::stoi(v);
             else if (k == "--device") o.device = std::stoi(v);
             else if (k == "--probe-file") o.probe_file = v;
+            else if (k == "--first-episode") o.first_episode = std::stoi(v);
+            else if (k == "--stop-episode") o.stop_episode = std::stoi(v);
+            else if (k == "--belief-in") o.belief_in = v;
+            else if (k == "--belief-out") o.belief_out = v;
             else if (k == "--probe-slots") {
                 const size_t colon = v.find(':');
                 if (colon == std::string::npos || std::stoi(v.substr(0, colon)) < 0 || std::stoi(v.substr(colon + 1)) < 1) throw std::invalid_argument(v);
@@ -341,10 +351,39 @@ int main(int argc, char** argv)
             return 1;
         }
     }
+    // a span of the experiment (--first-episode, --stop-episode, --belief-in, --belief-out: fba_run_bapomdp_span)
+    const bool span = o.first_episode != 0 || o.stop_episode >= 0 || !o.belief_in.empty() || !o.belief_out.empty();
+    const int first_episode = o.first_episode, stop_episode = o.stop_episode < 0 ? cfg.episodes : o.stop_episode;
+    std::vector<char> blocks;
+    int64_t per_block = 0;
+    if (span) {
+        const char* what = nullptr;
+        if (o.mode == "planning") what = "--first-episode, --stop-episode, --belief-in and --belief-out need a Bayes-adaptive experiment (bapomdp or fbapomdp)";
+        else if (fba_belief_snapshot_bytes(ctx, &per_block) != FBA_OK) what = fba_last_error(ctx);
+        else if (!o.belief_out.empty() && cfg.runs > fba_slots(ctx))
+            what = "--belief-out needs runs <= slots: a slot keeps the filter of the last run it executed only (shard the runs over processes instead)";
+        if (!what && !o.belief_in.empty()) {
+            std::ifstream in(o.belief_in, std::ios::binary);
+            if (in) blocks.assign(std::istreambuf_iterator<char>(in), std::istreambuf_iterator<char>());
+            if (!in || blocks.empty() || blocks.size() % (size_t)per_block) {
+                err = "--belief-in " + o.belief_in + ": not a file of snapshot blocks of this configuration (" + std::to_string(blocks.size()) + " bytes, " +
+                      std::to_string(per_block) + " per block)";
+                what = err.c_str();
+            }
+        }
+        if (what) {
+            std::fprintf(stderr, "ERROR: %s\n", what);
+            fba_destroy(ctx);
+            return 1;
+        }
+    }
     std::fprintf(stderr, "INFO: (%s): Starting %s experiment\n", o.id.c_str(), o.mode == "planning" ? "planning" : "BAPOMDP");
     std::vector<fba_stat> stats((size_t)cfg.episodes);
     const auto t0 = std::chrono::steady_clock::now();
-    const int rc  = o.mode == "planning" ? fba_run_planning(ctx, stats.data()) : fba_run_bapomdp(ctx, stats.data());
+    const int rc  = o.mode == "planning" ? fba_run_planning(ctx, stats.data())
+                    : !span             ? fba_run_bapomdp(ctx, stats.data())
+                                        : fba_run_bapomdp_span(ctx, first_episode, stop_episode, blocks.empty() ? nullptr : blocks.data(),
+                                                               blocks.empty() ? 0 : (int32_t)(blocks.size() / (size_t)per_block), (int64_t)blocks.size(), stats.data());
     const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (rc != FBA_OK) {
         std::fprintf(stderr, "ERROR: %s\n", fba_last_error(ctx));
@@ -368,6 +407,20 @@ int main(int argc, char** argv)
         fba_destroy(ctx);
         return 1;
     }
+    if (!o.belief_out.empty()) {   // run r's filter stands in slot r (runs <= slots)
+        std::vector<char> out((size_t)cfg.runs * (size_t)per_block);
+        bool ok = fba_belief_export(ctx, 0, cfg.runs, out.data(), (int64_t)out.size()) == FBA_OK;
+        if (ok) {
+            std::ofstream f(o.belief_out, std::ios::binary);
+            f.write(out.data(), (std::streamsize)out.size());
+            ok = (bool)f.flush();
+        }
+        if (!ok) {
+            std::fprintf(stderr, "ERROR: the filters could not be written to %s: %s\n", o.belief_out.c_str(), fba_last_error(ctx));
+            fba_destroy(ctx);
+            return 1;
+        }
+    }
     {
         std::ofstream f(o.output_file);
         f << "# version 1:\n# return mean, return var, return count, return stder, step duration mean\n";
@@ -375,8 +428,10 @@ int main(int argc, char** argv)
             f << stats[0].mean << ", " << fba_stat_var(&stats[0]) << ", " << stats[0].count << ", " << fba_stat_stder(&stats[0]) << ", "
               << step_duration;
         } else {
-            for (auto const& s : stats)
+            for (int e = span ? first_episode : 0; e < (span ? stop_episode : cfg.episodes); ++e) {
+                auto const& s = stats[(size_t)e];
                 f << s.mean << ", " << fba_stat_var(&s) << ", " << s.count << ", " << fba_stat_stder(&s) << ", " << step_duration << "\n";
+            }
         }
         f << std::endl;
     }

@@ -119,9 +119,21 @@ class Engine:
         self._chk(self.L.fba_run_planning(self.h, C.byref(st)))
         return st
 
-    def run_bapomdp(self):
+    def run_bapomdp(self, first_episode=0, stop_episode=None, beliefs=None):
+        """experiment::bapomdp::run.  With arguments, episodes [first_episode, stop_episode) of every run only (fba_run_bapomdp_span):
+        `beliefs` -- uint8[nblocks, belief_snapshot_bytes] as belief_export returns, one block for every run or one per run -- are the
+        filters the runs continue from, at the stream positions of the uninterrupted experiment; statistics outside the span have count 0."""
         st = (N.Stat * self.cfg.episodes)()
-        self._chk(self.L.fba_run_bapomdp(self.h, st))
+        if first_episode == 0 and stop_episode is None and beliefs is None:
+            self._chk(self.L.fba_run_bapomdp(self.h, st))
+            return list(st)
+        stop = self.cfg.episodes if stop_episode is None else stop_episode
+        if beliefs is None:
+            self._chk(self.L.fba_run_bapomdp_span(self.h, first_episode, stop, None, 0, 0, st))
+            return list(st)
+        b = np.ascontiguousarray(beliefs, np.uint8)
+        nblocks = b.shape[0] if b.ndim == 2 else b.size // self.belief_snapshot_bytes
+        self._chk(self.L.fba_run_bapomdp_span(self.h, first_episode, stop, b.ctypes.data, nblocks, b.nbytes, st))
         return list(st)
 
     def run_ticks(self, ticks):

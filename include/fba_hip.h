@@ -495,8 +495,8 @@ int fba_get_probe(const fba_ctx* ctx, fba_probe_rec* out, int32_t cap);
  * cheating (a second filter), incubator (second and shadow filters), mh-within-gibbs and mh-nips (the run's action-observation history and
  * log likelihood), nested (a filter of domain states per particle) -- for a slot range outside the context and for a buffer too small.
  * fba_run_planning and fba_run_bapomdp initiate a slot's belief at the start of every run, and so does fba_run_ticks when it first
- * sets the slots up and whenever a slot starts a run: an imported belief lives until its slot's run ends.  Warm-starting the
- * whole-experiment drivers from snapshots is not offered. */
+ * sets the slots up and whenever a slot starts a run: an imported belief lives until its slot's run ends.  fba_run_bapomdp_span (below)
+ * is the driver that starts its runs from snapshots; fba_run_ticks cannot be warm-started. */
 #define FBA_SNAPSHOT_MAGIC     0x53414246u              /* "FBAS" */
 #define FBA_SNAPSHOT_VERSION   1
 #define FBA_SNAPSHOT_CHECK_MUL 0x9E3779B97F4A7C15ull
@@ -525,6 +525,34 @@ int fba_belief_snapshot_bytes(const fba_ctx* ctx, int64_t* per_slot);
 int fba_belief_export   (fba_ctx* ctx, int32_t first, int32_t count, void* buf, int64_t cap);
 int fba_belief_import   (fba_ctx* ctx, int32_t first, int32_t count, const void* buf, int64_t bytes);
 int fba_belief_replicate(fba_ctx* ctx, int32_t src, int32_t first, int32_t count);
+
+/* A Bayes-adaptive experiment in spans, resumed from belief snapshots bit for bit.  The call runs episodes [first_episode, stop_episode)
+ * of every run of the experiment (0 <= first < stop <= episodes) at the stream positions of the uninterrupted experiment -- (run, episode, t)
+ * with the episode counted from 0 of the run -- so spans run one after the other, each from the blocks exported after the one before,
+ * give the trace records, returns, lengths, statistics and final filters of one fba_run_bapomdp, every bit of them.
+ *   blocks == NULL: first_episode and nblocks must be 0; every run starts from the prior, as in fba_run_bapomdp (which is unchanged).
+ *   blocks given:   Belief::initiate of a run is replaced by taking block (run - run_offset) % nblocks as that run's filter; nblocks is 1
+ *                   (one learned filter for every run) or `runs` (each run's own checkpoint), bytes == nblocks * fba_belief_snapshot_bytes.
+ *                   resetDomainStateDistribution at the start of episode first_episode follows as at every episode, so a block is the
+ *                   filter as it stood when the episode before ended -- what fba_belief_export gives after a span.
+ * After a span with runs <= slots, slot run - run_offset holds that run's filter as its last update left it (nothing touches a slot once
+ * it is inactive): fba_belief_export of those slots is the checkpoint for first_episode = this call's stop_episode.  With runs > slots a
+ * slot is left with the filter of the LAST run it executed only; checkpoints of more runs than slots are made by sharding with run_offset.
+ * stats[e] has count 0 outside the span, fba_get_returns gives 0 there, the trace holds the span's records only; counters, return sums,
+ * the probe and the kernel times behave as in fba_run_bapomdp (FBA_K_BELIEF_INIT: the restores, units = particles taken from blocks,
+ * bytes = particles * (block stride + 8 if weighted), read and written).
+ * Every block passes the two passes of fba_belief_import before anything runs -- host: every header field; device: checksum and every
+ * record -- and two rules of this call's: (host) what a block holds plus (stop - first) * horizon may not exceed episodes * horizon, where
+ * "holds" is the entries per record of a history format and head.updates of a packed one, so that a resumed run never holds more than an
+ * uninterrupted run of this context could and every bound fba_create derived from episodes * horizon keeps holding; (device) no 16-bit
+ * increment of a packed record exceeds head.updates.  After fba_run_bapomdp and after a span, head.updates of an exported packed filter
+ * is the real steps of the slot's run so far (an update follows every step but a terminal one), on top of its block's.  The blocks stand
+ * in device memory for the duration of the call, uploaded and judged a chunk at a time under the staging bound of fba_belief_import.
+ * FBA_EINVAL, with the context left as it was: a plain POMDP context, a belief that snapshots refuse, a span outside [0, episodes], blocks
+ * == NULL with first_episode or nblocks != 0, nblocks other than 1 or runs, wrong bytes, any block refused by a pass (the message names
+ * the block and what was wrong).  FBA_EHIP where the store does not fit (the message says how many bytes were asked for). */
+int fba_run_bapomdp_span(fba_ctx* ctx, int32_t first_episode, int32_t stop_episode, const void* blocks, int32_t nblocks, int64_t bytes,
+                         fba_stat* stats /* [episodes] */);
 
 /* diagnostic: out[i] = u * sqrt(L[i] / n[i]) evaluated on the device, to check that the
  * engine's fp64 divide and square root round like the host's (they must, for UCB parity) */
