@@ -376,9 +376,9 @@ __device__ __forceinline__ PackedFtigerView<FS, Base> packed_ftiger_view(const P
     return PackedFtigerView<FS, Base>{words, __float_as_uint(words.at(PackedFtigerView<FS, Base>::NC / 2)), P.ft_acc, P.ft_inacc, P.ft_unif};
 }
 
-__device__ __forceinline__ bool dom_is_tiger(int d) { return d == FBA_DOM_TIGER_EPISODIC || d == FBA_DOM_TIGER_CONTINUOUS; }
-__device__ __forceinline__ bool dom_is_ftiger(int d) { return d == FBA_DOM_FTIGER_EPISODIC || d == FBA_DOM_FTIGER_CONTINUOUS; }
-__device__ __forceinline__ bool dom_is_episodic(int d) { return d == FBA_DOM_TIGER_EPISODIC || d == FBA_DOM_FTIGER_EPISODIC; }
+__host__ __device__ __forceinline__ bool dom_is_tiger(int d) { return d == FBA_DOM_TIGER_EPISODIC || d == FBA_DOM_TIGER_CONTINUOUS; }
+__host__ __device__ __forceinline__ bool dom_is_ftiger(int d) { return d == FBA_DOM_FTIGER_EPISODIC || d == FBA_DOM_FTIGER_CONTINUOUS; }
+__host__ __device__ __forceinline__ bool dom_is_episodic(int d) { return d == FBA_DOM_TIGER_EPISODIC || d == FBA_DOM_FTIGER_EPISODIC; }
 __device__ __forceinline__ bool dom_is_grid(int d) { return d == FBA_DOM_GRIDWORLD; }
 __device__ __forceinline__ bool dom_is_ca(int d) { return d == FBA_DOM_COLLISION_AVOID || d == FBA_DOM_COLLISION_AVOID_CENTERED; }
 __device__ __forceinline__ bool dom_is_agr(int d) { return d == FBA_DOM_AGR; }
@@ -1293,6 +1293,9 @@ struct GlobalEntries {
 // or the table's padding and are not used) + this particle's increments
 // K = floats fetched (16-byte pieces); the loops over a row run to KL: a 12-float row holds at most 10 values (G <= 10 goals, N <= 8), and the
 // two padding places cost a sixth of every pass
+// the K a model whose longest Dirichlet row has hist_row values is instantiated for (Problem::hist_row; taken by reference, so that a kernel
+// that asks reads the field per comparison as it did when it spelled the expression out, and compiles to the code it had)
+__host__ __device__ __forceinline__ int hist_row_width(const int& hist_row) { return hist_row <= 8 ? 8 : (hist_row <= 10 ? 12 : 16); }
 template <int K>
 struct HistRow {
 #ifdef FBA_ROW_FULL   /* A/B builds: walk the padding too */

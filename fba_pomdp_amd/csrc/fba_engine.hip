@@ -16,7 +16,7 @@
 #include <vector>
 
 #include "fba_belief_factors.h"   // record_format
-#include "fba_kernels.h"
+#include "fba_launch_plan.h"
 #include "fba_snapshot_format.h"
 
 using namespace fba;
@@ -159,9 +159,6 @@ struct ScratchBuf {
     ~ScratchBuf() { if (p) (void)hipFree(p); }
     hipError_t alloc(size_t n) { return hipMalloc(&p, n * sizeof(T)); }
 };
-
-bool is_tiger(int d) { return d == FBA_DOM_TIGER_EPISODIC || d == FBA_DOM_TIGER_CONTINUOUS; }
-bool is_ftiger(int d) { return d == FBA_DOM_FTIGER_EPISODIC || d == FBA_DOM_FTIGER_CONTINUOUS; }
 
 bool is_ca(int d) { return d == FBA_DOM_COLLISION_AVOID || d == FBA_DOM_COLLISION_AVOID_CENTERED; }
 bool is_sys(int d) { return d == FBA_DOM_SYSADMIN_INDEPENDENT || d == FBA_DOM_SYSADMIN_LINEAR; }
@@ -449,14 +446,14 @@ int build_tabular_prior(fba_ctx* c)
     float* phi = c->prior.data();
     float* psi = c->prior.data() + P.phi_len;
     const int listen = 2;
-    if (is_tiger(P.domain)) {
+    if (dom_is_tiger(P.domain)) {
         phi[1 * A * S + listen * S + 0] = 0;
         phi[0 * A * S + listen * S + 1] = 0;
         psi[listen * S * O + 1 * O + 1] = acc;
         psi[listen * S * O + 1 * O + 0] = inacc;
         psi[listen * S * O + 0 * O + 1] = inacc;
         psi[listen * S * O + 0 * O + 0] = acc;
-    } else if (is_ftiger(P.domain)) {
+    } else if (dom_is_ftiger(P.domain)) {
         for (int s = 0; s < S; ++s)
             for (int ns = 0; ns < S; ++ns)
                 if (s != ns) phi[s * A * S + listen * S + ns] = 0;
@@ -743,7 +740,7 @@ int build_factored_prior(fba_ctx* c)
 int build_ftiger_factored_prior(fba_ctx* c)
 {
     Problem& P = c->P;
-    if (!is_ftiger(P.domain)) return fail(c, FBA_EINVAL, "domain %d has no built-in factored prior", P.domain);
+    if (!dom_is_ftiger(P.domain)) return fail(c, FBA_EINVAL, "domain %d has no built-in factored prior", P.domain);
     const float noise = c->cfg.noise, total = c->cfg.counts_total;
     if (noise <= -.15 || noise > .3) return fail(c, FBA_EINVAL, "noise must be between -.15 and .3");
     FDesc& d = c->fdesc;
@@ -971,7 +968,7 @@ int upload_prior(fba_ctx* c)
         {
             // the same rows deduplicated (Problem::hist_lds): a row slot -> one byte, the distinct rows K floats each
             const HistRowIds I(N, G, A);
-            const int K = c->P.hist_row <= 8 ? 8 : (c->P.hist_row <= 10 ? 12 : 16);   // (a 12-float row is walked to 10: HistRow::KL)
+            const int K = hist_row_width(c->P.hist_row);   // (a 12-float row is walked to 10: HistRow::KL)
             const int rid_bytes = (I.total + 15) & ~15;
             std::vector<uint8_t> blob((size_t)rid_bytes, 0);
             std::vector<float> rows;
@@ -1316,7 +1313,7 @@ int check_arguments(const fba_config& cfg)
 // (GridWorldFactBAPrior::sampleFullyConnectedState throws "nyi"): all three are built
 bool has_fully_connected_prior(const fba_config& cfg)
 {
-    return cfg.model == FBA_MODEL_BA_FACTORED && (is_ftiger(cfg.domain) || is_ca(cfg.domain) || is_sys(cfg.domain)) &&
+    return cfg.model == FBA_MODEL_BA_FACTORED && (dom_is_ftiger(cfg.domain) || is_ca(cfg.domain) || is_sys(cfg.domain)) &&
            !(is_ca(cfg.domain) && cfg.structure_prior == FBA_SP_FULLY_CONNECTED);
 }
 
@@ -1341,7 +1338,7 @@ int map_mh(const fba_config& cfg, Problem& P)
     const bool nips  = cfg.belief == FBA_BELIEF_MH_NIPS;
     const char* name = nips ? "MHNIPS2018" : "MHwithinGibbs";
     if (cfg.model != FBA_MODEL_BA_FACTORED || cfg.dirichlet_regular ||
-        !(is_ftiger(cfg.domain) || is_ca(cfg.domain) || cfg.domain == FBA_DOM_GRIDWORLD || is_sys(cfg.domain)) ||
+        !(dom_is_ftiger(cfg.domain) || is_ca(cfg.domain) || cfg.domain == FBA_DOM_GRIDWORLD || is_sys(cfg.domain)) ||
         (is_ca(cfg.domain) && cfg.structure_prior == FBA_SP_FULLY_CONNECTED))
         return fail(nullptr, FBA_EINVAL, "%s belief: needs a factored model (fbapomdp) in the expected Dirichlet mode, at most %d structure words per particle",
                     nips ? "mh-nips" : "mh-within-gibbs", MH_MAXVAR);
@@ -1519,13 +1516,13 @@ bool bucket_tree_search(const fba_config& cfg, const CreateSwitches& sw, const P
 
 // Packed particles (PackedView, fba_device.h): the tabular tiger particle as 24 uint16 increment counts over
 // the shared prior -- 64 bytes instead of 128 in every belief update and every root sample.  Only where every
-// kernel that touches the records is a tiger-table instantiation (launch_search / launch_belief_update), the
-// prior is exact under "+ 65535" (TigerBAPrior: 5000, 0 and the two listen counts below) and one run cannot
-// add more than 65535 to a cell (one T and one O increment per real step).
+// kernel that touches the records is a tiger-table instantiation (check_packed_kernels below holds the launch
+// decisions to that), the prior is exact under "+ 65535" (TigerBAPrior: 5000, 0 and the two listen counts below)
+// and one run cannot add more than 65535 to a cell (one T and one O increment per real step).
 void try_packed_tiger(fba_ctx* c, const CreateSwitches& sw)
 {
     const fba_config& cfg = c->cfg;
-    if (!(cfg.model == FBA_MODEL_BA_TABLE && is_tiger(cfg.domain) && !cfg.dirichlet_regular && cfg.planner == FBA_PLANNER_POUCT &&
+    if (!(tiger_table_model(c->P) && cfg.planner == FBA_PLANNER_POUCT &&
           (cfg.belief == FBA_BELIEF_REJECTION || cfg.belief == FBA_BELIEF_IMPORTANCE) && cfg.particles <= IS_MAX_CHUNKS * 256 &&
           !sw.is_multi_min_set && !sw.dense_particles && run_steps(cfg) <= 65535 && cfg.noise > -.15 && cfg.noise <= .3))
         return;
@@ -1537,13 +1534,14 @@ void try_packed_tiger(fba_ctx* c, const CreateSwitches& sw)
 // Packed factored-tiger particles (PackedFtigerView, fba_device.h): uint16 increments over a prior that is a function of
 // the cell and the particle's structure bits -- 144 B instead of 288 B at --size 3, so twice the beliefs per gigabyte and
 // per kilobyte of LDS.  Only where every kernel that touches the records is a factored-tiger instantiation (po-uct,
-// plain rejection filter, expected Dirichlet, --size 1..3) and the prior's five values are exact under "+ 65535".
+// plain rejection filter, expected Dirichlet, --size 1..3: check_packed_kernels below) and the prior's five values
+// are exact under "+ 65535".
 void try_packed_ftiger(fba_ctx* c, const CreateSwitches& sw)
 {
     const fba_config& cfg = c->cfg;
     Problem& P = c->P;
-    if (!(cfg.model == FBA_MODEL_BA_FACTORED && is_ftiger(cfg.domain) && cfg.belief == FBA_BELIEF_REJECTION && !P.point &&
-          cfg.planner == FBA_PLANNER_POUCT && !cfg.dirichlet_regular && cfg.size >= 1 && cfg.size <= 3 && !sw.dense_particles &&
+    if (!(ftiger_features(P) && cfg.belief == FBA_BELIEF_REJECTION && !P.point &&
+          cfg.planner == FBA_PLANNER_POUCT && cfg.size >= 1 && cfg.size <= 3 && !sw.dense_particles &&
           run_steps(cfg) <= 65535))
         return;
     const float acc = (.85f - cfg.noise) * cfg.counts_total, inacc = (.15f + cfg.noise) * cfg.counts_total, unif = .5f * cfg.counts_total;
@@ -1671,7 +1669,7 @@ int plan_tree(fba_ctx* c, const CreateSwitches& sw, TreePlan& t)
     // two children and the tree of a search of depth D is at most the complete binary tree with levels 0..D:
     // 2^(D+1) - 1 nodes, whatever the number of simulations (2047 at the default depth 10 against 4098 / 16386
     // records for 4096 / 16384 simulations).  search_kernel refuses to go past max_nodes (fault -> FBA_ESTATE).
-    if ((cfg.domain == FBA_DOM_TIGER_EPISODIC || cfg.domain == FBA_DOM_FTIGER_EPISODIC) && P.max_depth >= 0 && P.max_depth < 24)
+    if (dom_is_episodic(cfg.domain) && P.max_depth >= 0 && P.max_depth < 24)
         D.max_nodes = std::min(D.max_nodes, (1 << (P.max_depth + 1)) + 1);  // (+1: odd, so that the slots' trees are not a power of two
                                                                              // of bytes apart -- at exactly 128 KB the search ran 45 % slower)
     if (sw.node_bound) D.max_nodes = sw.node_bound;
@@ -1743,14 +1741,27 @@ int plan_filters(fba_ctx* c, const CreateSwitches& sw)
 }
 
 // Compact filters between the updates of the experiment loop (fba_state.h; FBA_NO_COMPACT=1 keeps 64-byte records, for A/B runs and
-// tests): where the update is reject_tiger_once_kernel on the episodic tiger's plain rejection filter and the search the one
-// instantiation that reads them, and a run cannot carry a count into bit 15 of its half.  Asked once the tree is planned
+// tests): where the launch decisions (fba_launch_plan.h) name the one update that writes them and the one search that reads them, on the
+// episodic tiger's plain rejection filter without a search budget, and a run cannot carry a count into bit 15 of its half.  Asked once
+// the tree is allocated
 bool compact_filters_ok(const fba_ctx* c, const CreateSwitches& sw)
 {
     const Problem& P = c->P;
-    return P.packed && c->cfg.domain == FBA_DOM_TIGER_EPISODIC && P.belief == FBA_BELIEF_REJECTION && !P.reinvig && !P.incub && !P.cheat &&
-           !P.nested && !P.point && P.N >= TIGER_ONCE_MIN_N && P.N <= TIGER_LDS_MAX_N && run_steps(c->cfg) <= 32767 && !sw.tiger_gather &&
-           !sw.dense_particles && !sw.no_compact && search_takes_compact(P, c->D);
+    return c->cfg.domain == FBA_DOM_TIGER_EPISODIC && P.belief == FBA_BELIEF_REJECTION && !P.reinvig && !P.incub && !P.cheat && !P.nested &&
+           !P.point && run_steps(c->cfg) <= 32767 && !sw.dense_particles && !sw.no_compact && P.search_budget <= 0 &&
+           kernel_name(update_plan(P, c->D).filter) == K_REJECT_TIGER_ONCE && search_plan(P, c->D).kernel == SEARCH_READS_COMPACT;
+}
+
+// What try_packed_tiger and try_packed_ftiger promise: every tick kernel that touches packed records is one of the format's instantiations
+int check_packed_kernels(fba_ctx* c)
+{
+    const Problem& P = c->P;
+    const uint32_t search = search_plan(P, c->D).kernel, update = update_plan(P, c->D).filter;
+    if (P.packed && !(reads_packed_tiger(search) && reads_packed_tiger(update)))
+        return fail(c, FBA_ESTATE, "packed tiger records met a kernel that does not read them (search %#x, update %#x)", search, update);
+    if (P.ft_packed && !(reads_packed_ftiger(search) && reads_packed_ftiger(update)))
+        return fail(c, FBA_ESTATE, "packed factored-tiger records met a kernel that does not read them (search %#x, update %#x)", search, update);
+    return FBA_OK;
 }
 
 // ---- stage 5: the device buffers, grouped as the data is, and the uploads
@@ -2026,7 +2037,7 @@ int make_context(fba_ctx* c, const CreateSwitches& sw)
     TRY(upload_regular_dirichlet(c));
     TRY(upload_model(c));
     c->compact_ok = compact_filters_ok(c, sw);
-    return FBA_OK;
+    return check_packed_kernels(c);
 }
 
 struct CtxDestroy { void operator()(fba_ctx* c) const { fba_destroy(c); } };
@@ -3416,6 +3427,7 @@ int fba_get_kernel_times(fba_ctx* c, fba_kernel_time* out)
     int rc = flush_events(c);
     if (rc) return rc;
     const Problem& P = c->P;
+    const uint32_t update    = update_plan(P, c->D).filter;   // the kernel that ran picks each alternative byte formula below
     const uint64_t sim       = sum_counter(c, c->D.sim_steps, P.E, &rc) - c->base_sim;
     const uint64_t attempts  = sum_counter(c, c->D.upd_attempts, P.E, &rc) - c->base_attempts;
     const uint64_t particles = sum_counter(c, c->D.upd_particles, P.E, &rc) - c->base_particles;
@@ -3452,11 +3464,11 @@ int fba_get_kernel_times(fba_ctx* c, fba_kernel_time* out)
         // filter once to park it, reads the N accepted sources and writes N records, 64 bytes each
         // ... and where the experiment loop keeps compact filters (fba_state.h), what those launches moved: a particle written compact
         // was read as 64 or as 16 bytes and written as 16 -- 80 or 32 bytes
-        if (P.packed && P.N <= TIGER_LDS_MAX_N)
+        if (tiger_filter_in_lds(update))
             out[FBA_K_BELIEF_RS].bytes = (particles - compact_full - compact) * 3 * (uint64_t)(P.Cs * 4) + compact_full * 80 + compact * 32;
         // packed factored-tiger records (reject_kernel on 144-byte records at --size 3): SURVEY's formula on the bytes a packed particle has --
         // an attempt reads its source record and one 4-byte word per two-cell Dirichlet row it samples, an accepted one writes a record
-        if (P.ft_packed) {
+        if (reads_packed_ftiger(update)) {
             const uint64_t rec = (uint64_t)P.Cs * 4, rows = 4 * (uint64_t)(c->fdesc.FS + c->fdesc.FO);
             out[FBA_K_BELIEF_RS].bytes = attempts * (rec + rows) + particles * rec;
         }
@@ -3464,7 +3476,7 @@ int fba_get_kernel_times(fba_ctx* c, fba_kernel_time* out)
         // of the real action, an accepted one is gathered -- its source record read (8 + 4 per entry) and written with the new entry
         // (8 + 4 per entry + 4); `entries` counts the 4-byte entries of both (fba_state.h upd_entries); the Dirichlet rows come from LDS
         // (tabular records, reject_tab_hist_kernel: the same formula; their sparse prior rows are L2-resident, 380 KB at N = 7, and not counted)
-        if (P.hist) out[FBA_K_BELIEF_RS].bytes = attempts * 8 + particles * 20 + entries * 4;
+        if (updates_history_records(update)) out[FBA_K_BELIEF_RS].bytes = attempts * 8 + particles * 20 + entries * 4;
     } else {
         out[FBA_K_BELIEF_IS].units = particles;
         out[FBA_K_BELIEF_IS].bytes = particles * (32 + Rt + Ro) + particles * (8 + 2 * Pb);
@@ -3472,17 +3484,17 @@ int fba_get_kernel_times(fba_ctx* c, fba_kernel_time* out)
         // weight read and written (16), the record -- 8 bytes + 4 per entry -- read once by the update, once as a
         // resample source, written once with its new entry (+4); the Dirichlet rows come from the shared tables
         // (tabular records, is_multi_tab_step_kernel: the same formula; their sparse prior rows are L2-resident and not counted)
-        if (P.hist) out[FBA_K_BELIEF_IS].bytes = particles * 44 + entries * 12;
+        if (updates_history_records(update)) out[FBA_K_BELIEF_IS].bytes = particles * 44 + entries * 12;
         // collision-avoidance records (is_multi_ca_step_kernel and the launches behind it, at every filter size): per particle the weight read
         // and written by the step (16), read by the normalisation (8), read again and its prefix sum written by the scan (16), one prefix sum
         // read per draw at least and the new weight written (16), the side row {state, entry} written and read (16) = 72; the record -- 8
         // bytes + 4 per entry -- read by the step, read as a resample source, written with its new entry (3 * 8 + 4 = 28 + 12 per entry).
         // The prior and its sequence table sit in LDS and are not counted.
-        if (P.hist == 3) out[FBA_K_BELIEF_IS].bytes = particles * 100 + entries * 12;
+        if (kernel_name(update) == K_IS_MULTI_CA_STEP) out[FBA_K_BELIEF_IS].bytes = particles * 100 + entries * 12;
         // packed tiger particles (64-byte records): the same formula on the bytes a packed particle has -- the update reads
         // state + weight + its two rows and writes state + weight + two counts (32 + Rt + Ro = 48), the resample reads the
         // weight and moves a record in and out (8 + 2 * 64)
-        if (P.packed) out[FBA_K_BELIEF_IS].bytes = particles * (32 + Rt + Ro) + particles * (8 + 2 * (uint64_t)(P.Cs * 4));
+        if (reads_packed_tiger(update)) out[FBA_K_BELIEF_IS].bytes = particles * (32 + Rt + Ro) + particles * (8 + 2 * (uint64_t)(P.Cs * 4));
     }
     return FBA_OK;
 }

@@ -11,6 +11,7 @@ constexpr int SEARCH_BLOCK  = 64;    // one wave per workgroup, one tree per lan
 constexpr int SEARCH_STAGE_WORDS = 128; // particle records up to this many words are staged in LDS by the search
 constexpr int ROOT_CHILDREN = 8;        // root child pointers are kept in LDS when A*O is at most this
 constexpr int REJECT_BLOCK  = 256;   // attempts per chunk of the rejection filter
+// (which kernel a tick launch runs under these limits: search_plan / update_plan / reset_plan, fba_launch_plan.h)
 constexpr int TIGER_LDS_MAX_N = 4096;  // reject_tiger_lds_kernel: filters up to this many packed tiger particles are parked in LDS
 constexpr int TIGER_ONCE_MIN_N = 3584;  // reject_tiger_once_kernel from here up: 13 N + 8.3 KB of reject_tiger_lds_kernel no longer fit three times into a CU's 160 KB
 constexpr int REJECT_MAX_ATTEMPTS = 1 << 28;  // per update: beyond this the observation is taken to be impossible under the filter
@@ -32,7 +33,6 @@ inline size_t ca_hist_search_lds(const Problem& P)
 }
 
 void launch_search(const Problem& P, const DeviceState& D, hipStream_t st);
-bool search_takes_compact(const Problem& P, const DeviceState& D);   // launch_search would launch the instantiation that reads compact filters (fba_state.h)
 void launch_start(const Problem& P, const DeviceState& D, hipStream_t st);
 void launch_env(const Problem& P, const DeviceState& D, int32_t* n_active, hipStream_t st);
 void launch_advance(const Problem& P, const DeviceState& D, int32_t* n_active, hipStream_t st);

@@ -1842,7 +1842,7 @@ __global__ void __launch_bounds__(256) nested_update_kernel(Problem P, DeviceSta
 // WLDS: the slot's weights live in LDS from the update pass to the last draw (N <= IS_LDS_MAX_N: 8 bytes each): the
 // normalised weights and their prefix sums never go to HBM, the N searches read LDS.  Same sums, same order.
 // history particles: all N sources are drawn before the gather when their 16-bit indices fit the workgroup's LDS beside the weights
-__host__ __device__ __forceinline__ bool hist_all_draws_first(int N) { return N <= 16384; }
+// (hist_all_draws_first, fba_launch_plan.h)
 template <bool REG, int TIGER_TABLE, bool HIST = false, bool WLDS = false>
 __global__ void __launch_bounds__(IS_BLOCK) importance_kernel(Problem P, DeviceState D)
 {
@@ -2859,37 +2859,6 @@ void launch_advance(const Problem& P, const DeviceState& D, int32_t* n_active, h
 {
     hipLaunchKernelGGL(advance_kernel, dim3(ceil_div(P.E, 256)), dim3(256), 0, st, P, D, n_active);
 }
-// importance_kernel of one slot per workgroup, the instantiation the problem calls for
-static void launch_importance_single(const Problem& P, const DeviceState& D, hipStream_t st)
-{
-    const bool tiger_table = P.model == FBA_MODEL_BA_TABLE && !P.dirichlet_regular &&
-                             (P.domain == FBA_DOM_TIGER_EPISODIC || P.domain == FBA_DOM_TIGER_CONTINUOUS);
-    // weights and prefix sums of a slot in LDS while its workgroup works on them (8 bytes per particle)
-    const bool wlds = P.N <= IS_LDS_MAX_N && !P.dirichlet_regular;
-    const size_t wl = (wlds ? (size_t)P.N * (sizeof(double) + ((tiger_table && P.packed) ? 4 : 0)) : 0) +  // (packed tiger: + pending updates and sources, 16 bits each)
-                      ((P.hist && hist_all_draws_first(P.N)) ? (size_t)P.N * 2 : 0);                       // (history particles: the drawn sources)
-    const int grid_e = D.use_list ? D.scratch_slots /* (set to the chunk's count by the caller) */
-                                  : (D.single_rec ? std::min(D.scratch_slots, P.E - D.slot_base) : P.E);   // (single_rec: one chunk of slots per launch)
-#define FBA_LAUNCH_IS(...)                                                                                         \
-    do {                                                                                                           \
-    static unsigned long long raised = 0;   /* one bit per device: function attributes are per device */          \
-    int dev_ = 0;                                                                                              \
-    (void)hipGetDevice(&dev_);                                                                                 \
-    if (wl > 16384 && !((raised >> (dev_ & 63)) & 1ull)) {                                                      \
-        /* (a refused attribute leaves the bit clear and the launch below fails: the engine reads hipGetLastError after every tick / update) */ \
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&importance_kernel<__VA_ARGS__>),                \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, IS_LDS_MAX_N * 12) == hipSuccess)  \
-            raised |= 1ull << (dev_ & 63);                                                                     \
-    }                                                                                                          \
-    hipLaunchKernelGGL((importance_kernel<__VA_ARGS__>), dim3(grid_e), dim3(IS_BLOCK), wl, st, P, D);          \
-    } while (0)
-    if (P.hist) { if (wlds) FBA_LAUNCH_IS(false, 0, true, true); else FBA_LAUNCH_IS(false, 0, true, false); }
-    else if (P.dirichlet_regular) FBA_LAUNCH_IS(true, 0, false, false);
-    else if (tiger_table && P.packed) { if (wlds) FBA_LAUNCH_IS(false, 2, false, true); else FBA_LAUNCH_IS(false, 2, false, false); }
-    else if (tiger_table) { if (wlds) FBA_LAUNCH_IS(false, 1, false, true); else FBA_LAUNCH_IS(false, 1, false, false); }
-    else { if (wlds) FBA_LAUNCH_IS(false, 0, false, true); else FBA_LAUNCH_IS(false, 0, false, false); }
-#undef FBA_LAUNCH_IS
-}
 // the slots whose flag (need_update / need_reset == 1) is set, compacted; a listed slot's scratch place is its position in its chunk
 __global__ void __launch_bounds__(256) build_slot_list_kernel(Problem P, DeviceState D, const uint8_t* flag)
 {
@@ -2945,134 +2914,107 @@ static void for_each_chunk(const Problem& P, const DeviceState& D, hipStream_t s
         (void)hipMemsetAsync(D.copy_pending + e0, 0, (size_t)cnt, st);
     }
 }
-// the importance update of `count` slots (all of them, a chunk, or a chunk of the compacted list: chunk_slot) as seven launches, so that a slot's
-// particles spread over many workgroups
-static void launch_importance_multi(const Problem& P, const DeviceState& D, int count, hipStream_t st)
+// One launch of a belief update or a reset as update_plan / reset_plan describe it (fba_launch_plan.h: which kernel, and why), over `count`
+// slots: all of them, a chunk, or a chunk of the compacted list (chunk_slot).  Every instantiation stands once, behind its key
+static void launch_step(const Problem& P, const DeviceState& D, const LaunchStep& s, int count, hipStream_t st)
 {
+    const dim3 grid = s.grid(count), block(s.block);
     const int nchunks = (P.N + 255) / 256;
-    const dim3 cgrid(ceil_div(nchunks, 4), count), eg(ceil_div(count, 64));
-    const int32_t* list = D.use_list ? D.slot_list : nullptr;
-    if (P.hist == 2) hipLaunchKernelGGL(is_multi_tab_step_kernel, cgrid, dim3(256), 0, st, P, D);   // (tabular records: sparse prior rows from L2)
-    else if (P.hist == 3)   // (collision-avoidance records: the whole prior and its sequence table in LDS)
-        hipLaunchKernelGGL(is_multi_ca_step_kernel, cgrid, dim3(256), ca_hist_table_bytes(P.hist_row, P.hist_rid_bytes, P.hist_distinct, P.hist_cap), st, P, D);
-    else if (P.hist) {
-        // the prior's rows from LDS where the deduplicated blob exists (rows of K floats, K as upload_prior chose it) -- FBA_HIST_ROWS=hbm: from L2
-        const bool rows_hbm = D.ab_rows_hbm != 0;
-        const int K = P.hist_row <= 8 ? 8 : (P.hist_row <= 10 ? 12 : 0);
-        const size_t lds = (size_t)P.hist_rid_bytes + (size_t)P.hist_distinct * K * sizeof(float);
-        if (P.hist_lds && K == 8 && !rows_hbm) hipLaunchKernelGGL((is_multi_step_kernel<false, true, 8>), cgrid, dim3(256), lds, st, P, D);
-        else if (P.hist_lds && K == 12 && !rows_hbm) hipLaunchKernelGGL((is_multi_step_kernel<false, true, 12>), cgrid, dim3(256), lds, st, P, D);
-        else hipLaunchKernelGGL((is_multi_step_kernel<false, true>), cgrid, dim3(256), 0, st, P, D);
+#define FBA_STEP(...) { hipLaunchKernelGGL((__VA_ARGS__), grid, block, s.lds, st, P, D); return; }
+#define FBA_STEP_ARG(...) { hipLaunchKernelGGL((__VA_ARGS__), grid, block, s.lds, st, P, D, s.arg); return; }
+#define FBA_REJECT(...) case reject_key(__VA_ARGS__): FBA_STEP_ARG(reject_kernel<__VA_ARGS__>)
+#define FBA_IMPORTANCE(...)                                                                                        \
+    case importance_key(__VA_ARGS__): {                                                                            \
+        static unsigned long long raised = 0;   /* one bit per device: function attributes are per device */      \
+        int dev_ = 0;                                                                                              \
+        (void)hipGetDevice(&dev_);                                                                                 \
+        if (s.raise_lds && !((raised >> (dev_ & 63)) & 1ull)) {                                                    \
+            /* (a refused attribute leaves the bit clear and the launch below fails: the engine reads hipGetLastError after every tick / update) */ \
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&importance_kernel<__VA_ARGS__>),                \
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, s.raise_lds) == hipSuccess)        \
+                raised |= 1ull << (dev_ & 63);                                                                     \
+        }                                                                                                          \
+        FBA_STEP(importance_kernel<__VA_ARGS__>)                                                                   \
     }
-    else if (P.dirichlet_regular) hipLaunchKernelGGL((is_multi_step_kernel<true, false>), cgrid, dim3(256), 0, st, P, D);
-    else hipLaunchKernelGGL((is_multi_step_kernel<false, false>), cgrid, dim3(256), 0, st, P, D);
-    hipLaunchKernelGGL(scan_carry_kernel, dim3(count), dim3(256), 0, st, D.ctot, D.ctot_stride, nchunks, D.is_tot, 2, 0, D.need_update, count, list, D.slot_base);
-    hipLaunchKernelGGL(is_multi_norm_kernel, cgrid, dim3(256), 0, st, P, D);
-    hipLaunchKernelGGL(scan_carry_kernel, dim3(count), dim3(256), 0, st, D.ctot, D.ctot_stride, nchunks, D.is_tot, 2, 1, D.need_update, count, list, D.slot_base);
-    hipLaunchKernelGGL(is_multi_scan_kernel, cgrid, dim3(256), 0, st, P, D);
-    hipLaunchKernelGGL(is_multi_resample_kernel, dim3(ceil_div(P.N, 256), count), dim3(256), 0, st, P, D);
-    hipLaunchKernelGGL(is_multi_finish_kernel, eg, dim3(64), 0, st, P, D, count);
+    switch (s.kernel) {
+        case kernel_key(K_NESTED_UPDATE, true): FBA_STEP(nested_update_kernel<true>)
+        case kernel_key(K_NESTED_UPDATE, false): FBA_STEP(nested_update_kernel<false>)
+        case kernel_key(K_REINVIGORATE): FBA_STEP_ARG(reinvigorate_kernel)
+        case kernel_key(K_COPY_FLAGS): hipLaunchKernelGGL(copy_flags_kernel, grid, block, 0, st, D.need_update, D.need_update_sh, P.E); return;
+        FBA_IMPORTANCE(false, 0, true, true)
+        FBA_IMPORTANCE(false, 0, true, false)
+        FBA_IMPORTANCE(true, 0, false, false)
+        FBA_IMPORTANCE(false, 2, false, true)
+        FBA_IMPORTANCE(false, 2, false, false)
+        FBA_IMPORTANCE(false, 1, false, true)
+        FBA_IMPORTANCE(false, 1, false, false)
+        FBA_IMPORTANCE(false, 0, false, true)
+        FBA_IMPORTANCE(false, 0, false, false)
+        case kernel_key(K_REJECT_TAB_HIST): FBA_STEP(reject_tab_hist_kernel)
+        case kernel_key(K_REJECT_HIST, 8): FBA_STEP(reject_hist_kernel<8>)
+        case kernel_key(K_REJECT_HIST, 12): FBA_STEP(reject_hist_kernel<12>)
+        case kernel_key(K_REJECT_HIST, 0): FBA_STEP(reject_hist_kernel<0>)
+        FBA_REJECT(false, 0, 2, REJECT_BLOCK, true)
+        FBA_REJECT(false, 0, 3, REJECT_BLOCK, true)
+        FBA_REJECT(false, 0, 4, REJECT_BLOCK, true)
+        FBA_REJECT(false, 0, 2)
+        FBA_REJECT(false, 0, 3)
+        FBA_REJECT(false, 0, 4)
+        FBA_REJECT(true, 0)
+        FBA_REJECT(false, 2, 0, 512)
+        FBA_REJECT(false, 1)
+        FBA_REJECT(false, 0)
+        case kernel_key(K_REJECT_TIGER_ONCE_GATHER): FBA_STEP(reject_tiger_once_gather_kernel<512>)
+        case kernel_key(K_REJECT_TIGER_ONCE): FBA_STEP(reject_tiger_once_kernel<512>)
+        case kernel_key(K_REJECT_TIGER_LDS): FBA_STEP(reject_tiger_lds_kernel<512>)
+        case kernel_key(K_CHEAT): FBA_STEP(cheat_kernel)
+        case kernel_key(K_MH): FBA_STEP_ARG(mh_kernel)
+        case kernel_key(K_IS_MULTI_TAB_STEP): FBA_STEP(is_multi_tab_step_kernel)
+        case kernel_key(K_IS_MULTI_CA_STEP): FBA_STEP(is_multi_ca_step_kernel)
+        case kernel_key(K_IS_MULTI_STEP, false, true, 8): FBA_STEP(is_multi_step_kernel<false, true, 8>)
+        case kernel_key(K_IS_MULTI_STEP, false, true, 12): FBA_STEP(is_multi_step_kernel<false, true, 12>)
+        case kernel_key(K_IS_MULTI_STEP, false, true, 0): FBA_STEP(is_multi_step_kernel<false, true>)
+        case kernel_key(K_IS_MULTI_STEP, true, false, 0): FBA_STEP(is_multi_step_kernel<true, false>)
+        case kernel_key(K_IS_MULTI_STEP, false, false, 0): FBA_STEP(is_multi_step_kernel<false, false>)
+        case kernel_key(K_SCAN_CARRY):
+            hipLaunchKernelGGL(scan_carry_kernel, grid, block, 0, st, D.ctot, D.ctot_stride, nchunks, D.is_tot, 2, s.arg, D.need_update, count,
+                               D.use_list ? D.slot_list : nullptr, D.slot_base);
+            return;
+        case kernel_key(K_IS_MULTI_NORM): FBA_STEP(is_multi_norm_kernel)
+        case kernel_key(K_IS_MULTI_SCAN): FBA_STEP(is_multi_scan_kernel)
+        case kernel_key(K_IS_MULTI_RESAMPLE): FBA_STEP(is_multi_resample_kernel)
+        case kernel_key(K_IS_MULTI_FINISH): hipLaunchKernelGGL(is_multi_finish_kernel, grid, block, 0, st, P, D, count); return;
+        case kernel_key(K_RESET_HIST_FLAT): FBA_STEP(reset_hist_flat_kernel)
+        case kernel_key(K_POST_RESET): FBA_STEP(post_reset_kernel)
+        case kernel_key(K_LAZY_RESET): FBA_STEP(lazy_reset_kernel)
+        case kernel_key(K_NESTED_FILL): FBA_STEP_ARG(nested_fill_kernel)
+        case kernel_key(K_RESET): FBA_STEP_ARG(reset_kernel)
+    }
+#undef FBA_IMPORTANCE
+#undef FBA_REJECT
+#undef FBA_STEP_ARG
+#undef FBA_STEP
+    g_launch_err = hipErrorInvalidDeviceFunction;   // (the plan names a kernel this switch lacks: the engine hears of it, timed())
 }
-// history particles: several workgroups per slot from this many particles up (FBA_HIST_MULTI=1 / 0 forces / forbids it: tests, A/B runs)
-static bool hist_update_multi(const Problem& P, const DeviceState& D)
+// the steps of a plan in order; chunked steps that stand together share their chunks (for_each_chunk; `flag`: the request the compacted list is
+// built from).  Ps / Ds: what the steps on the incubator's shadow filter are launched with
+static void launch_plan(const LaunchPlan& pl, const Problem& P, const DeviceState& D, const Problem& Ps, const DeviceState& Ds, const uint8_t* flag, hipStream_t st)
 {
-    if (D.ab_hist_multi) return D.ab_hist_multi == 2;
-    return P.N >= 4096;
+    for (int i = 0, j; i < pl.n; i = j) {
+        const LaunchStep& s = pl.step[i];
+        j = i + 1;
+        if (!s.chunked) { launch_step(s.shadow ? Ps : P, s.shadow ? Ds : D, s, P.E, st); continue; }
+        while (j < pl.n && pl.step[j].chunked) ++j;
+        for_each_chunk(P, D, st, [&](const DeviceState& Dc, int cnt) { for (int k = i; k < j; ++k) launch_step(P, Dc, pl.step[k], cnt, st); }, flag);
+    }
 }
 void launch_belief_update(const Problem& P, const DeviceState& D, hipStream_t st)
 {
-    if (P.nested) {
-        if (P.dirichlet_regular) hipLaunchKernelGGL(nested_update_kernel<true>, dim3(P.E), dim3(256), 0, st, P, D);
-        else hipLaunchKernelGGL(nested_update_kernel<false>, dim3(P.E), dim3(256), 0, st, P, D);
-        return;
-    }
-    if (P.belief == FBA_BELIEF_REJECTION) {
-        const bool tiger_table = P.model == FBA_MODEL_BA_TABLE && !P.dirichlet_regular &&
-                                 (P.domain == FBA_DOM_TIGER_EPISODIC || P.domain == FBA_DOM_TIGER_CONTINUOUS);
-        if (P.reinvig) hipLaunchKernelGGL(reinvigorate_kernel, dim3(P.E), dim3(256), 0, st, P, D, 0);
-        if (P.incub) {
-            // StructureIncubatorSampling::updateEstimation (:105-131): breed the least likely shadow particles from the two
-            // rejection filters as they are now, importance-sample the shadow filter (it has its own copy of the request
-            // flags: its kernel clears them), then the two rejection updates below
-            hipLaunchKernelGGL(copy_flags_kernel, dim3(ceil_div(P.E, 256)), dim3(256), 0, st, D.need_update, D.need_update_sh, P.E);
-            hipLaunchKernelGGL(reinvigorate_kernel, dim3(P.E), dim3(256), 0, st, P, D, 1);
-            Problem Ps = P;
-            Ps.belief = FBA_BELIEF_IMPORTANCE; Ps.incub = 0;
-            DeviceState Ds = D;
-            Ds.p_rec = D.p_rec_sh; Ds.p_weight = D.p_weight_sh; Ds.bufsel = D.bufsel_sh; Ds.need_update = D.need_update_sh; Ds.shadow = 1;
-            launch_importance_single(Ps, Ds, st);
-        }
-        const int ft = (P.model == FBA_MODEL_BA_FACTORED && !P.dirichlet_regular &&
-                        (P.domain == FBA_DOM_FTIGER_EPISODIC || P.domain == FBA_DOM_FTIGER_CONTINUOUS))
-                           ? 31 - __builtin_clz((unsigned)P.S) : 0;  // S = 2^FS
-        if (P.hist == 2) {   // tabular history particles (fba_create: the plain filter, expected Dirichlet)
-            const auto launch = [&](const DeviceState& Dc, int cnt) { hipLaunchKernelGGL(reject_tab_hist_kernel, dim3(cnt), dim3(REJECT_BLOCK), 0, st, P, Dc); };
-            if (D.single_rec) for_each_chunk(P, D, st, launch, D.need_update);
-            else launch(D, P.E);
-            return;
-        }
-        if (P.hist) {   // (fba_create: the plain filter, expected Dirichlet)
-            const int K = P.hist_row <= 8 ? 8 : (P.hist_row <= 10 ? 12 : 0);
-            const bool lrows = P.hist_lds && K > 0 && !D.ab_rows_hbm;   // the prior's rows from LDS (FBA_HIST_ROWS=hbm: from L2)
-            const size_t lds = lrows ? (size_t)P.hist_rid_bytes + (size_t)P.hist_distinct * K * sizeof(float) : 0;
-            const auto launch = [&](const DeviceState& Dc, int cnt) {
-                if (lrows && K == 8) hipLaunchKernelGGL(reject_hist_kernel<8>, dim3(cnt), dim3(REJECT_BLOCK), lds, st, P, Dc);
-                else if (lrows) hipLaunchKernelGGL(reject_hist_kernel<12>, dim3(cnt), dim3(REJECT_BLOCK), lds, st, P, Dc);
-                else hipLaunchKernelGGL(reject_hist_kernel<0>, dim3(cnt), dim3(REJECT_BLOCK), 0, st, P, Dc);
-            };
-            if (D.single_rec) for_each_chunk(P, D, st, launch, D.need_update);
-            else launch(D, P.E);
-            return;
-        }
-        for (int fc = (P.reinvig || P.incub) ? 1 : 0; fc >= 0; --fc) {  // the main filter's launch clears the request flag: last
-            if (ft == 2 && P.ft_packed) hipLaunchKernelGGL((reject_kernel<false, 0, 2, REJECT_BLOCK, true>), dim3(P.E), dim3(REJECT_BLOCK), 0, st, P, D, fc);
-            else if (ft == 3 && P.ft_packed) hipLaunchKernelGGL((reject_kernel<false, 0, 3, REJECT_BLOCK, true>), dim3(P.E), dim3(REJECT_BLOCK), 0, st, P, D, fc);
-            else if (ft == 4 && P.ft_packed) hipLaunchKernelGGL((reject_kernel<false, 0, 4, REJECT_BLOCK, true>), dim3(P.E), dim3(REJECT_BLOCK), 0, st, P, D, fc);
-            else if (ft == 2) hipLaunchKernelGGL((reject_kernel<false, 0, 2>), dim3(P.E), dim3(REJECT_BLOCK), 0, st, P, D, fc);
-            else if (ft == 3) hipLaunchKernelGGL((reject_kernel<false, 0, 3>), dim3(P.E), dim3(REJECT_BLOCK), 0, st, P, D, fc);
-            else if (ft == 4) hipLaunchKernelGGL((reject_kernel<false, 0, 4>), dim3(P.E), dim3(REJECT_BLOCK), 0, st, P, D, fc);
-            else if (P.dirichlet_regular) hipLaunchKernelGGL((reject_kernel<true, 0>), dim3(P.E), dim3(REJECT_BLOCK), 0, st, P, D, fc);
-            else if (tiger_table && P.packed && P.N <= TIGER_LDS_MAX_N && P.N >= TIGER_ONCE_MIN_N && D.ab_tiger_gather)
-                hipLaunchKernelGGL((reject_tiger_once_gather_kernel<512>), dim3(P.E), dim3(512), (size_t)P.N * 17 + 16, st, P, D);
-            else if (tiger_table && P.packed && P.N <= TIGER_LDS_MAX_N && P.N >= TIGER_ONCE_MIN_N)
-                hipLaunchKernelGGL((reject_tiger_once_kernel<512>), dim3(P.E), dim3(512), (size_t)P.N * 17 + 16, st, P, D);
-            else if (tiger_table && P.packed && P.N <= TIGER_LDS_MAX_N)
-                hipLaunchKernelGGL((reject_tiger_lds_kernel<512>), dim3(P.E), dim3(512), (size_t)P.N * 13 + 16, st, P, D);
-            else if (tiger_table && P.packed)  // (chunks of 512 are 4 % faster than 256 / 1024 on packed records)
-                hipLaunchKernelGGL((reject_kernel<false, 2, 0, 512>), dim3(P.E), dim3(512), 0, st, P, D, fc);
-            else if (tiger_table) hipLaunchKernelGGL((reject_kernel<false, 1>), dim3(P.E), dim3(REJECT_BLOCK), 0, st, P, D, fc);
-            else hipLaunchKernelGGL((reject_kernel<false, 0>), dim3(P.E), dim3(REJECT_BLOCK), 0, st, P, D, fc);
-        }
-        return;
-    }
-    if (P.cheat) {  // rejectSample on the correct-graph filter first (CheatingReinvigoration.cpp:111)
-        if (P.dirichlet_regular) hipLaunchKernelGGL((reject_kernel<true, 0>), dim3(P.E), dim3(REJECT_BLOCK), 0, st, P, D, 1);
-        else hipLaunchKernelGGL((reject_kernel<false, 0>), dim3(P.E), dim3(REJECT_BLOCK), 0, st, P, D, 1);
-    }
-    if (P.hist >= 2) {   // tabular / collision-avoidance history particles: the update is always the multi-launch one (is_multi_tab_step_kernel,
-                         // is_multi_ca_step_kernel), one slot or many, 65 536 particles or a million
-        if (D.single_rec) for_each_chunk(P, D, st, [&](const DeviceState& Dc, int cnt) { launch_importance_multi(P, Dc, cnt, st); }, D.need_update);
-        else launch_importance_multi(P, D, P.E, st);
-        return;
-    }
-    if (!D.is_multi) {
-        if (D.single_rec)
-            for_each_chunk(P, D, st, [&](const DeviceState& Dc, int cnt) {
-                if (P.hist && hist_update_multi(P, D)) { launch_importance_multi(P, Dc, cnt, st); return; }
-                if (!Dc.use_list) { launch_importance_single(P, Dc, st); return; }
-                DeviceState Dl   = Dc;           // (list mode: the launch's grid is the chunk's count; scratch places were fixed against
-                Dl.scratch_slots = cnt;          //  the pool's size when the list was built)
-                launch_importance_single(P, Dl, st);
-            }, D.need_update);
-        else launch_importance_single(P, D, st);
-        if (P.cheat) hipLaunchKernelGGL(cheat_kernel, dim3(P.E), dim3(256), 0, st, P, D);
-        if (P.mh) {  // a wave per slot; the chain's scratch in LDS when it fits
-            const int in_lds = mh_scratch_in_lds(D.mh_scratch_words);
-            hipLaunchKernelGGL(mh_kernel, dim3(P.E), dim3(64), MH_LDS_HEAD + (in_lds ? (size_t)D.mh_scratch_words * 4 : 0), st, P, D, in_lds);
-        }
-        return;
-    }
-    launch_importance_multi(P, D, P.E, st);
+    Problem Ps = P;   // the incubator's shadow filter is importance-sampled; it has its own copy of the request flags: its kernel clears them
+    Ps.belief = FBA_BELIEF_IMPORTANCE; Ps.incub = 0;
+    DeviceState Ds = D;
+    Ds.p_rec = D.p_rec_sh; Ds.p_weight = D.p_weight_sh; Ds.bufsel = D.bufsel_sh; Ds.need_update = D.need_update_sh; Ds.shadow = 1;
+    launch_plan(update_plan(P, D), P, D, Ps, Ds, D.need_update, st);
 }
 #ifdef FBA_PROFILE_REJECT
 extern "C" int fba_debug_reject_profile(unsigned long long* out, int reset)
@@ -3108,32 +3050,9 @@ void launch_materialize_records(const Problem& P, const DeviceState& D, hipStrea
 }
 void launch_reset(const Problem& P, const DeviceState& D, hipStream_t st)
 {
-    if (P.belief == FBA_BELIEF_REJECTION && !P.reinvig && !P.cheat && !P.incub) {  // the plain rejection filter resets lazily
-        if (P.hist) {   // ... except on history particles, which keep a second copy of the state (reset_hist_flat_kernel)
-            hipLaunchKernelGGL(reset_hist_flat_kernel, dim3(ceil_div(P.N, PARTICLE_TILE), P.E), dim3(256), 0, st, P, D);
-            hipLaunchKernelGGL(post_reset_kernel, dim3(ceil_div(P.E, 256)), dim3(256), 0, st, P, D);
-            return;
-        }
-        hipLaunchKernelGGL(lazy_reset_kernel, dim3(ceil_div(P.E, 256)), dim3(256), 0, st, P, D);
-        return;
-    }
-    if (P.nested) {
-        hipLaunchKernelGGL(nested_fill_kernel, dim3(P.E), dim3(256), 0, st, P, D, 1);
-        hipLaunchKernelGGL(post_reset_kernel, dim3(ceil_div(P.E, 256)), dim3(256), 0, st, P, D);
-        return;
-    }
-    if (D.single_rec)
-        for_each_chunk(P, D, st, [&](const DeviceState& Dc, int cnt) {
-            hipLaunchKernelGGL(reset_kernel, dim3(ceil_div(P.N, PARTICLE_TILE), cnt), dim3(256), 0, st, P, Dc, 0);
-        }, D.need_reset);
-    else hipLaunchKernelGGL(reset_kernel, dim3(ceil_div(P.N, PARTICLE_TILE), P.E), dim3(256), 0, st, P, D, 0);
-    if (P.reinvig || P.cheat || P.incub) hipLaunchKernelGGL(reset_kernel, dim3(ceil_div(P.N, PARTICLE_TILE), P.E), dim3(256), 0, st, P, D, 1);
-    if (P.incub) {  // StructureIncubatorSampling::resetDomainStateDistribution (:46-61): the shadow filter too, in place
-        DeviceState Ds = D;
-        Ds.p_rec = D.p_rec_sh; Ds.p_weight = D.p_weight_sh; Ds.bufsel = D.bufsel_sh; Ds.shadow = 1;
-        hipLaunchKernelGGL(reset_kernel, dim3(ceil_div(P.N, PARTICLE_TILE), P.E), dim3(256), 0, st, P, Ds, 0);
-    }
-    hipLaunchKernelGGL(post_reset_kernel, dim3(ceil_div(P.E, 256)), dim3(256), 0, st, P, D);
+    DeviceState Ds = D;   // (the incubator's shadow filter, reset in place)
+    Ds.p_rec = D.p_rec_sh; Ds.p_weight = D.p_weight_sh; Ds.bufsel = D.bufsel_sh; Ds.shadow = 1;
+    launch_plan(reset_plan(P, D), P, D, P, Ds, D.need_reset, st);
 }
 void launch_flush(const Problem& P, const DeviceState& D, hipStream_t st)
 {

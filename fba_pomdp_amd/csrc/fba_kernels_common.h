@@ -5,7 +5,7 @@
 
 #include <float.h>
 
-#include "fba_kernels.h"
+#include "fba_launch_plan.h"
 
 namespace fba {
 

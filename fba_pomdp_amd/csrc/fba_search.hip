@@ -6,6 +6,7 @@
 // The search is latency bound and gets its throughput from running one independent tree per lane (or quad), all
 // lanes executing the common "simulate one step" body together.  No dense contraction, no MFMA.
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
@@ -27,11 +28,6 @@ namespace fba {
 // FTIGER > 0: the simulator is the factored-tiger FBA-POMDP with FTIGER binary state features (expected
 // Dirichlet mode); its step is ftiger_step<FTIGER>, the layout restated as literals.
 // TIGER_POMDP: planning on the tiger POMDP itself (BASELINE configs[0]); the sizes and the domain are literals.
-__host__ __device__ __forceinline__ bool root_children_in_lds(const Problem& P, const DeviceState& D)
-{
-    return P.A * P.O <= ROOT_CHILDREN && D.max_nodes <= 32767;
-}
-
 // FTP: the factored-tiger records are packed (PackedFtigerView).
 //
 // ETIGER: the episodic tiger family (tiger and factored tiger, POMDP or Bayes-adaptive simulator): A = 3, O = 2, and only
@@ -43,21 +39,7 @@ __host__ __device__ __forceinline__ bool root_children_in_lds(const Problem& P, 
 // child indices as uint16, Q as fp64), never in HBM.  The path itself shrinks to 16 bits per level -- node index (12 bits:
 // the host bounds the tree at 2^(depth+1) + 1 nodes), action (2), and the reward as a code (-1 / 10 / -100: the only
 // rewards of these domains) -- which is what pays for the room.  Same draws, same arithmetic, same results.
-constexpr int ET_NODE_WORDS = 9;   // an LDS node: n0 | n1 << 16, n2, child0 | child1 << 16, q0, q1, q2 (two words each)
-__host__ __device__ __forceinline__ bool etiger_ok(const Problem& P, const DeviceState& D)
-{
-    return (P.domain == FBA_DOM_TIGER_EPISODIC || P.domain == FBA_DOM_FTIGER_EPISODIC) && P.A == 3 && P.O == 2 && P.sims <= 65535 &&
-           D.max_nodes <= 4093 && !D.hash && P.planner != FBA_PLANNER_RANDOM;
-}
-// 32-bit words of the dynamic LDS allocation of one search workgroup in front of the staged model description
-__host__ __device__ __forceinline__ size_t search_lds_words(const Problem& P, const DeviceState& D, bool stage, bool etiger)
-{
-    const int depth_cap = P.max_depth > 0 ? P.max_depth : 1;
-    if (etiger)
-        return (size_t)((depth_cap + 1) / 2) * SEARCH_BLOCK + (stage ? (size_t)P.Cs * SEARCH_BLOCK : 0) + (size_t)2 * ET_NODE_WORDS * SEARCH_BLOCK;
-    return (size_t)depth_cap * SEARCH_BLOCK * 2 + (stage ? (size_t)P.Cs * SEARCH_BLOCK : 0) +
-           (root_children_in_lds(P, D) ? (size_t)P.A * P.O * SEARCH_BLOCK / 2 : 0);
-}
+// (ET_NODE_WORDS, etiger_ok and the LDS sizes of this file's kernels: fba_launch_plan.h)
 __device__ __forceinline__ int et_reward_code(double r) { return r == -1.0 ? 0 : (r == 10.0 ? 1 : 2); }
 __device__ __forceinline__ double et_reward(int code) { return code == 0 ? -1.0 : (code == 1 ? 10.0 : -100.0); }
 #ifdef FBA_PROFILE_SEARCH
@@ -481,7 +463,6 @@ __global__ void __launch_bounds__(SEARCH_BLOCK) search_kernel(Problem P, DeviceS
 // same draws, same order, same results as search_kernel on dense records.
 // LDS per wave: path [depth][16], the root particle's record [2 + entries][16].
 // ---------------------------------------------------------------------------------------------
-constexpr int HIST_TREES = SEARCH_BLOCK / HIST_QUAD;
 template <int K>
 __global__ void __launch_bounds__(SEARCH_BLOCK) search_hist_kernel(Problem P, DeviceState D)
 {
@@ -825,19 +806,7 @@ __device__ __forceinline__ uint32_t h2_home_line(uint32_t code, uint32_t nlines)
 #endif
 // LROWS: every Dirichlet row of the prior comes from LDS (Problem::hist_lds: row ids + the distinct rows, shared by the H2_WAVES waves of a
 // workgroup); otherwise the transition rows come from the padded tables in HBM and only the observation tables sit in LDS.
-constexpr int H2_WAVES = 4;                                   // waves per workgroup
-constexpr int H2_BLOCK = H2_WAVES * 64;
-__host__ __device__ __forceinline__ size_t h2_shared_bytes(const Problem& P, bool lrows)
-{
-    const int K = P.hist_row <= 8 ? 8 : (P.hist_row <= 10 ? 12 : 16);
-    return lrows ? (size_t)P.hist_rid_bytes + (size_t)P.hist_distinct * K * sizeof(float) : (size_t)4 * HistLayout(P.gw_N, P.gw_G, 4).ostride * sizeof(float);
-}
-__host__ __device__ __forceinline__ size_t h2_wave_bytes(const Problem& P)
-{
-    const int depth_cap = P.max_depth > 0 ? P.max_depth : 1;
-    return (size_t)depth_cap * HIST_TREES * (sizeof(double) + sizeof(int32_t) + sizeof(float) + sizeof(int32_t)) +
-           (size_t)(P.Cs > 2 * depth_cap ? P.Cs : 2 * depth_cap) * HIST_TREES * sizeof(float) + (size_t)14 * HIST_TREES * sizeof(float);   // (+ the root's statistics, the record geometry)
-}
+constexpr int H2_BLOCK = H2_WAVES * 64;   // (H2_WAVES, h2_shared_bytes, h2_wave_bytes: fba_launch_plan.h)
 // search_order (fba_state.h): a counting sort of the slots by the depth their searches have left (inactive slots first).  One workgroup; which of two
 // slots of equal depth comes first is left to the atomics -- every tree is independent, so no result can depend on it.
 __global__ void __launch_bounds__(1024) search_order_kernel(Problem P, DeviceState D)
@@ -1055,138 +1024,97 @@ __global__ void __launch_bounds__(SEARCH_BLOCK) search_ca_hist_kernel(Problem P,
 // ---------------------------------------------------------------------------------------------
 // host launcher
 // ---------------------------------------------------------------------------------------------
+// Which instantiation, with what block, grid and LDS, is search_plan's decision (fba_launch_plan.h); here every instantiation stands once, behind
+// its key -- spelled from the same template arguments -- and is launched the same way
 void launch_search(const Problem& P, const DeviceState& D, hipStream_t st)
 {
-    const bool stage = P.model != FBA_MODEL_POMDP && P.Cs <= SEARCH_STAGE_WORDS;
-    // the episodic tiger family on its own tree layout (ETIGER); FBA_NO_ETIGER=1 keeps the general layout, for A/B runs
-    const bool no_etiger = D.ab_no_etiger != 0;
-    // (the instantiations that exist on that layout: the tabular tiger BA-POMDP, planning on tiger itself, packed factored tiger)
-    const bool tiger_table = P.model == FBA_MODEL_BA_TABLE && P.planner == FBA_PLANNER_POUCT && !P.dirichlet_regular && stage &&
-                             (P.domain == FBA_DOM_TIGER_EPISODIC || P.domain == FBA_DOM_TIGER_CONTINUOUS) && !D.hash;
-    const bool tiger_pomdp = P.model == FBA_MODEL_POMDP && P.planner == FBA_PLANNER_POUCT && !D.hash &&
-                             (P.domain == FBA_DOM_TIGER_EPISODIC || P.domain == FBA_DOM_TIGER_CONTINUOUS);
-    const int ft_fs        = P.S > 0 ? 31 - __builtin_clz((unsigned)P.S) : 0;  // factored tiger: S = 2^FS
-    const bool ftiger      = P.model == FBA_MODEL_BA_FACTORED && (P.domain == FBA_DOM_FTIGER_EPISODIC || P.domain == FBA_DOM_FTIGER_CONTINUOUS) &&
-                             !P.dirichlet_regular && P.planner == FBA_PLANNER_POUCT && !D.hash;
-    const bool et = !no_etiger && !P.hist && etiger_ok(P, D) &&
-                    (tiger_table || tiger_pomdp || (ftiger && P.ft_packed && ft_fs >= 2 && ft_fs <= 4));
-    size_t lds = search_lds_words(P, D, stage, et) * sizeof(uint32_t);
-    if (P.model == FBA_MODEL_BA_FACTORED && !(ftiger && ft_fs >= 2 && ft_fs <= 4))
-        lds = ((lds + 15) & ~(size_t)15) + (((size_t)P.fd_bytes + 15) & ~(size_t)15);  // + the model description (not the factored-tiger instantiations: 0.9 KB
-                                                                                        //   that kept C3 at nine waves per CU where ten fit)
+    const SearchPlan pl = search_plan(P, D);
     static const size_t lds_pad = std::getenv("FBA_SEARCH_LDS_PAD") ? (size_t)std::atoi(std::getenv("FBA_SEARCH_LDS_PAD")) : 0;  // occupancy experiments
-    lds += lds_pad;
-    const int depth_cap = P.max_depth > 0 ? P.max_depth : 1;
-    const dim3 grid(ceil_div(P.E, SEARCH_BLOCK)), block(SEARCH_BLOCK);
-#define FBA_LAUNCH_SEARCH_M(STG, AM, MODEL)                                                                              \
-    do {                                                                                                                 \
-        if (P.dirichlet_regular && MODEL != FBA_MODEL_POMDP)                                                             \
-            hipLaunchKernelGGL((search_kernel<STG, AM, (MODEL != FBA_MODEL_POMDP), 0, MODEL>), grid, block, lds, st, P, D); \
-        else hipLaunchKernelGGL((search_kernel<STG, AM, false, 0, MODEL>), grid, block, lds, st, P, D);             \
-    } while (0)
-#define FBA_LAUNCH_SEARCH(STG, AM)                                                                  \
-    do {                                                                                            \
-        if (P.model == FBA_MODEL_BA_FACTORED) FBA_LAUNCH_SEARCH_M(STG, AM, FBA_MODEL_BA_FACTORED);  \
-        else if (P.model == FBA_MODEL_BA_TABLE) FBA_LAUNCH_SEARCH_M(STG, AM, FBA_MODEL_BA_TABLE);   \
-        else FBA_LAUNCH_SEARCH_M(false, AM, FBA_MODEL_POMDP);                                       \
-    } while (0)
-    if (P.hist == 3) {  // history particles of the collision-avoidance FBA-POMDP: one lane per tree, node records (A = 3)
-        const size_t lds3 = ca_hist_search_lds(P);   // (at most 64 KB: fba_create keeps other contexts dense)
-        hipLaunchKernelGGL(search_ca_hist_kernel<4>, grid, block, lds3, st, P, D);
-        return;
+    const size_t lds = pl.lds + (kernel_name(pl.kernel) == K_SEARCH ? lds_pad : 0);
+    const dim3 grid(pl.grid(P.E)), block(pl.block);
+    if (pl.order_first) hipLaunchKernelGGL(search_order_kernel, dim3(1), dim3(1024), 0, st, P, D);
+#define FBA_LAUNCH(...)                                                                                                                     \
+    {                                                                                                                                       \
+        if (pl.raise_lds) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&__VA_ARGS__), hipFuncAttributeMaxDynamicSharedMemorySize, pl.raise_lds); \
+        hipLaunchKernelGGL((__VA_ARGS__), grid, block, lds, st, P, D);                                                                      \
+        return;                                                                                                                             \
     }
-    if (P.hist) {  // history particles (gridworld FBA-POMDP): four lanes per tree
-        lds = (size_t)depth_cap * HIST_TREES * (sizeof(double) + sizeof(int32_t) + sizeof(float) + sizeof(int32_t)) + (size_t)P.Cs * HIST_TREES * sizeof(float);
-        const dim3 qgrid(ceil_div(P.E, HIST_TREES));
-        if (D.bkt && P.hist == 2) {   // tabular records (fba_create gives them the bucket tree only)
-            int nw = H2_WAVES;
-            while (nw > 1 && (size_t)nw * h2_wave_bytes(P) > 64 * 1024) nw >>= 1;
-            const size_t lds2 = (size_t)nw * h2_wave_bytes(P);
-            const dim3 grid2(ceil_div(P.E, HIST_TREES * nw)), block2(64 * nw);
-            if (D.ab_lockstep) hipLaunchKernelGGL(search_order_kernel, dim3(1), dim3(1024), 0, st, P, D);
-            const void* kfn = P.belief == FBA_BELIEF_REJECTION ? reinterpret_cast<const void*>(&search_tabhist_kernel<true>)
-                                                               : reinterpret_cast<const void*>(&search_tabhist_kernel<false>);
-            if (lds2 > 64 * 1024) (void)hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-            if (P.belief == FBA_BELIEF_REJECTION) hipLaunchKernelGGL(search_tabhist_kernel<true>, grid2, block2, lds2, st, P, D);
-            else hipLaunchKernelGGL(search_tabhist_kernel<false>, grid2, block2, lds2, st, P, D);
-            return;
-        }
-        if (D.bkt) {   // the tree as one table of buckets, trips to memory requested an iteration ahead
-            const bool no_lrows = D.ab_rows_hbm != 0;   // A/B: transition rows from the padded tables
-            const bool lrows = P.hist_lds != nullptr && !no_lrows;
-            int nw = H2_WAVES;   // waves per workgroup: as many as 64 KB of LDS hold beside the shared tables (deep horizons have long paths)
-            while (nw > 1 && h2_shared_bytes(P, lrows) + (size_t)nw * h2_wave_bytes(P) > 64 * 1024) nw >>= 1;
-            const size_t lds2 = h2_shared_bytes(P, lrows) + (size_t)nw * h2_wave_bytes(P);
-            const dim3 grid2(ceil_div(P.E, HIST_TREES * nw)), block2(64 * nw);
-            if (D.ab_lockstep) hipLaunchKernelGGL(search_order_kernel, dim3(1), dim3(1024), 0, st, P, D);
-#define FBA_LAUNCH_H2_K(KERNEL, KV)                                                                                    \
-    do {                                                                                                               \
-        if (lds2 > 64 * 1024) {   /* (one wave of a very deep horizon: past the default limit of a workgroup's dynamic LDS) */ \
-            if (lrows) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&KERNEL<KV, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2); \
-            else (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&KERNEL<KV, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2); \
-        }                                                                                                              \
-        if (lrows) hipLaunchKernelGGL((KERNEL<KV, true>), grid2, block2, lds2, st, P, D);                              \
-        else hipLaunchKernelGGL((KERNEL<KV, false>), grid2, block2, lds2, st, P, D);                                   \
-    } while (0)
-#define FBA_LAUNCH_H2(KV)                                                                                              \
-    do {                                                                                                               \
-        if (P.belief == FBA_BELIEF_REJECTION) FBA_LAUNCH_H2_K(hist2_flat_search, KV);   /* (a flat filter's root sample) */ \
-        else FBA_LAUNCH_H2_K(search_hist2_kernel, KV);                                                                 \
-    } while (0)
-            if (P.hist_row <= 8) FBA_LAUNCH_H2(8);
-            else if (P.hist_row <= 10) FBA_LAUNCH_H2(12);
-            else FBA_LAUNCH_H2(16);
-#undef FBA_LAUNCH_H2
-#undef FBA_LAUNCH_H2_K
-            return;
-        }
-        if (P.hist_row <= 8) hipLaunchKernelGGL((search_hist_kernel<8>), qgrid, block, lds, st, P, D);
-        else if (P.hist_row <= 10) hipLaunchKernelGGL((search_hist_kernel<12>), qgrid, block, lds, st, P, D);
-        else hipLaunchKernelGGL((search_hist_kernel<16>), qgrid, block, lds, st, P, D);
-        return;
+#define FBA_SEARCH(...) case search_key(__VA_ARGS__): FBA_LAUNCH(search_kernel<__VA_ARGS__>)
+#define FBA_HIST_SEARCH(NAME, KERNEL, ...) case kernel_key(NAME, __VA_ARGS__): FBA_LAUNCH(KERNEL<__VA_ARGS__>)
+    switch (pl.kernel) {
+        FBA_HIST_SEARCH(K_SEARCH_CA_HIST, search_ca_hist_kernel, 4)
+        FBA_HIST_SEARCH(K_SEARCH_TABHIST, search_tabhist_kernel, true)
+        FBA_HIST_SEARCH(K_SEARCH_TABHIST, search_tabhist_kernel, false)
+        FBA_HIST_SEARCH(K_HIST2_FLAT_SEARCH, hist2_flat_search, 8, true)
+        FBA_HIST_SEARCH(K_HIST2_FLAT_SEARCH, hist2_flat_search, 8, false)
+        FBA_HIST_SEARCH(K_HIST2_FLAT_SEARCH, hist2_flat_search, 12, true)
+        FBA_HIST_SEARCH(K_HIST2_FLAT_SEARCH, hist2_flat_search, 12, false)
+        FBA_HIST_SEARCH(K_HIST2_FLAT_SEARCH, hist2_flat_search, 16, true)
+        FBA_HIST_SEARCH(K_HIST2_FLAT_SEARCH, hist2_flat_search, 16, false)
+        FBA_HIST_SEARCH(K_SEARCH_HIST2, search_hist2_kernel, 8, true)
+        FBA_HIST_SEARCH(K_SEARCH_HIST2, search_hist2_kernel, 8, false)
+        FBA_HIST_SEARCH(K_SEARCH_HIST2, search_hist2_kernel, 12, true)
+        FBA_HIST_SEARCH(K_SEARCH_HIST2, search_hist2_kernel, 12, false)
+        FBA_HIST_SEARCH(K_SEARCH_HIST2, search_hist2_kernel, 16, true)
+        FBA_HIST_SEARCH(K_SEARCH_HIST2, search_hist2_kernel, 16, false)
+        FBA_HIST_SEARCH(K_SEARCH_HIST, search_hist_kernel, 8)
+        FBA_HIST_SEARCH(K_SEARCH_HIST, search_hist_kernel, 12)
+        FBA_HIST_SEARCH(K_SEARCH_HIST, search_hist_kernel, 16)
+        // the tabular tiger BA-POMDP: dense / packed records, general / ETIGER tree layout; planning on tiger itself
+        FBA_SEARCH(true, 4, false, 2, FBA_MODEL_BA_TABLE, 0, false, false, true)
+        FBA_SEARCH(true, 4, false, 2, FBA_MODEL_BA_TABLE, 0, false, false, false)
+        FBA_SEARCH(true, 4, false, 1, FBA_MODEL_BA_TABLE, 0, false, false, true)
+        FBA_SEARCH(true, 4, false, 1, FBA_MODEL_BA_TABLE, 0, false, false, false)
+        FBA_SEARCH(false, 4, false, 0, FBA_MODEL_POMDP, 0, true, false, true)
+        FBA_SEARCH(false, 4, false, 0, FBA_MODEL_POMDP, 0, true, false, false)
+        // factored tiger with FS state features: packed on the ETIGER / the general layout, dense staged / unstaged
+        FBA_SEARCH(true, 4, false, 0, FBA_MODEL_BA_FACTORED, 2, false, true, true)
+        FBA_SEARCH(true, 4, false, 0, FBA_MODEL_BA_FACTORED, 2, false, true, false)
+        FBA_SEARCH(true, 4, false, 0, FBA_MODEL_BA_FACTORED, 2)
+        FBA_SEARCH(false, 4, false, 0, FBA_MODEL_BA_FACTORED, 2)
+        FBA_SEARCH(true, 4, false, 0, FBA_MODEL_BA_FACTORED, 3, false, true, true)
+        FBA_SEARCH(true, 4, false, 0, FBA_MODEL_BA_FACTORED, 3, false, true, false)
+        FBA_SEARCH(true, 4, false, 0, FBA_MODEL_BA_FACTORED, 3)
+        FBA_SEARCH(false, 4, false, 0, FBA_MODEL_BA_FACTORED, 3)
+        FBA_SEARCH(true, 4, false, 0, FBA_MODEL_BA_FACTORED, 4, false, true, true)
+        FBA_SEARCH(true, 4, false, 0, FBA_MODEL_BA_FACTORED, 4, false, true, false)
+        FBA_SEARCH(true, 4, false, 0, FBA_MODEL_BA_FACTORED, 4)
+        FBA_SEARCH(false, 4, false, 0, FBA_MODEL_BA_FACTORED, 4)
+        // every other model, by action count: staged or not, regular or expected Dirichlet
+        FBA_SEARCH(true, 4, true, 0, FBA_MODEL_BA_FACTORED)
+        FBA_SEARCH(true, 4, false, 0, FBA_MODEL_BA_FACTORED)
+        FBA_SEARCH(true, 4, true, 0, FBA_MODEL_BA_TABLE)
+        FBA_SEARCH(true, 4, false, 0, FBA_MODEL_BA_TABLE)
+        FBA_SEARCH(false, 4, true, 0, FBA_MODEL_BA_FACTORED)
+        FBA_SEARCH(false, 4, false, 0, FBA_MODEL_BA_FACTORED)
+        FBA_SEARCH(false, 4, true, 0, FBA_MODEL_BA_TABLE)
+        FBA_SEARCH(false, 4, false, 0, FBA_MODEL_BA_TABLE)
+        FBA_SEARCH(false, 4, false, 0, FBA_MODEL_POMDP)
+        FBA_SEARCH(true, 8, true, 0, FBA_MODEL_BA_FACTORED)
+        FBA_SEARCH(true, 8, false, 0, FBA_MODEL_BA_FACTORED)
+        FBA_SEARCH(true, 8, true, 0, FBA_MODEL_BA_TABLE)
+        FBA_SEARCH(true, 8, false, 0, FBA_MODEL_BA_TABLE)
+        FBA_SEARCH(false, 8, true, 0, FBA_MODEL_BA_FACTORED)
+        FBA_SEARCH(false, 8, false, 0, FBA_MODEL_BA_FACTORED)
+        FBA_SEARCH(false, 8, true, 0, FBA_MODEL_BA_TABLE)
+        FBA_SEARCH(false, 8, false, 0, FBA_MODEL_BA_TABLE)
+        FBA_SEARCH(false, 8, false, 0, FBA_MODEL_POMDP)
+        FBA_SEARCH(true, 16, true, 0, FBA_MODEL_BA_FACTORED)
+        FBA_SEARCH(true, 16, false, 0, FBA_MODEL_BA_FACTORED)
+        FBA_SEARCH(true, 16, true, 0, FBA_MODEL_BA_TABLE)
+        FBA_SEARCH(true, 16, false, 0, FBA_MODEL_BA_TABLE)
+        FBA_SEARCH(false, 16, true, 0, FBA_MODEL_BA_FACTORED)
+        FBA_SEARCH(false, 16, false, 0, FBA_MODEL_BA_FACTORED)
+        FBA_SEARCH(false, 16, true, 0, FBA_MODEL_BA_TABLE)
+        FBA_SEARCH(false, 16, false, 0, FBA_MODEL_BA_TABLE)
+        FBA_SEARCH(false, 16, false, 0, FBA_MODEL_POMDP)
+        FBA_SEARCH(false, 24, false, 0, FBA_MODEL_POMDP)
     }
-    if (tiger_table) {
-        if (P.packed && et) hipLaunchKernelGGL((search_kernel<true, 4, false, 2, FBA_MODEL_BA_TABLE, 0, false, false, true>), grid, block, lds, st, P, D);
-        else if (P.packed) hipLaunchKernelGGL((search_kernel<true, 4, false, 2, FBA_MODEL_BA_TABLE>), grid, block, lds, st, P, D);
-        else if (et) hipLaunchKernelGGL((search_kernel<true, 4, false, 1, FBA_MODEL_BA_TABLE, 0, false, false, true>), grid, block, lds, st, P, D);
-        else hipLaunchKernelGGL((search_kernel<true, 4, false, 1, FBA_MODEL_BA_TABLE>), grid, block, lds, st, P, D);
-        return;
-    }
-    if (tiger_pomdp) {
-        if (et) hipLaunchKernelGGL((search_kernel<false, 4, false, 0, FBA_MODEL_POMDP, 0, true, false, true>), grid, block, lds, st, P, D);
-        else hipLaunchKernelGGL((search_kernel<false, 4, false, 0, FBA_MODEL_POMDP, 0, true>), grid, block, lds, st, P, D);
-        return;
-    }
-    if (ftiger) {
-        const int FS = ft_fs;
-#define FBA_LAUNCH_FTIGER(FSV)                                                                                                    \
-    do {                                                                                                                          \
-        if (P.ft_packed && et) hipLaunchKernelGGL((search_kernel<true, 4, false, 0, FBA_MODEL_BA_FACTORED, FSV, false, true, true>), grid, block, lds, st, P, D); \
-        else if (P.ft_packed) hipLaunchKernelGGL((search_kernel<true, 4, false, 0, FBA_MODEL_BA_FACTORED, FSV, false, true>), grid, block, lds, st, P, D); \
-        else if (stage) hipLaunchKernelGGL((search_kernel<true, 4, false, 0, FBA_MODEL_BA_FACTORED, FSV>), grid, block, lds, st, P, D); \
-        else hipLaunchKernelGGL((search_kernel<false, 4, false, 0, FBA_MODEL_BA_FACTORED, FSV>), grid, block, lds, st, P, D);      \
-        return;                                                                                                                   \
-    } while (0)
-        if (FS == 2) FBA_LAUNCH_FTIGER(2);
-        if (FS == 3) FBA_LAUNCH_FTIGER(3);
-        if (FS == 4) FBA_LAUNCH_FTIGER(4);
-#undef FBA_LAUNCH_FTIGER
-    }
-    if (P.A <= 4) { if (stage) FBA_LAUNCH_SEARCH(true, 4); else FBA_LAUNCH_SEARCH(false, 4); }
-    else if (P.A <= 8) { if (stage) FBA_LAUNCH_SEARCH(true, 8); else FBA_LAUNCH_SEARCH(false, 8); }
-    else if (P.A <= 16) { if (stage) FBA_LAUNCH_SEARCH(true, 16); else FBA_LAUNCH_SEARCH(false, 16); }
-    else FBA_LAUNCH_SEARCH_M(false, 24, FBA_MODEL_POMDP);  // agr (23 actions) is a POMDP-only domain
-#undef FBA_LAUNCH_SEARCH_M
-#undef FBA_LAUNCH_SEARCH
-}
-// launch_search's own conditions for search_kernel<true, 4, false, 2, FBA_MODEL_BA_TABLE, 0, false, false, true>, the one instantiation
-// that reads compact filters (fba_state.h): fba_create asks before it lets a context keep them
-bool search_takes_compact(const Problem& P, const DeviceState& D)
-{
-    const bool stage = P.model != FBA_MODEL_POMDP && P.Cs <= SEARCH_STAGE_WORDS;
-    const bool tiger_table = P.model == FBA_MODEL_BA_TABLE && P.planner == FBA_PLANNER_POUCT && !P.dirichlet_regular && stage &&
-                             (P.domain == FBA_DOM_TIGER_EPISODIC || P.domain == FBA_DOM_TIGER_CONTINUOUS) && !D.hash;
-    return tiger_table && P.packed && !D.ab_no_etiger && !P.hist && etiger_ok(P, D) && P.search_budget <= 0;
+#undef FBA_HIST_SEARCH
+#undef FBA_SEARCH
+#undef FBA_LAUNCH
+    std::fprintf(stderr, "launch_search: no instantiation behind kernel key %#x\n", pl.kernel);   // (search_plan names one this switch lacks)
+    std::abort();
 }
 #ifdef FBA_PROFILE_SEARCH
 extern "C" int fba_debug_search_profile(unsigned long long* out, int reset)

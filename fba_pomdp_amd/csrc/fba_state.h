@@ -56,8 +56,9 @@ struct DeviceState {
     // Between two updates of the experiment loop an episodic-tiger slot may hold its filter COMPACT: one 16-byte record per particle in the
     // first 16 N bytes of the live buffer -- the four `listen` words {T(0,L,.), T(1,L,.), O(L,0,.), O(L,1,.)} of the packed record (words 2,
     // 5, 10, 11), the state in bit 31 of the fourth (free: compact_on needs episodes * horizon <= 32767).  Only reject_tiger_once_kernel
-    // writes one, only it, the ETIGER packed search and flush_kernel read one; launch_materialize_records turns every such slot back into
-    // 64-byte records in front of everything else that touches p_rec
+    // writes one, only it, the ETIGER packed search (SEARCH_READS_COMPACT) and flush_kernel read one -- fba_create asks fba_launch_plan.h
+    // whether those two are the kernels this context launches; launch_materialize_records turns every such slot back into 64-byte records
+    // in front of everything else that touches p_rec
     uint8_t* compact;   // [E] the slot's filter is compact
     int8_t compact_on;  // this launch may leave slots compact (set by tick() in a context that fba_create found eligible; 0 in every per-call launch)
     unsigned long long* upd_compact_full;  // [E] particles written compact from 64-byte sources

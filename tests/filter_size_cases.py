@@ -5,7 +5,7 @@ Every other oracle comparison of the suite fixes the particle count at a few hun
 here the slots are few (E = 3, or 2 at the largest filters), the search is 8 simulations and the horizon 4 to 6, and N is the subject:
 
     switch-over                                   where                                        what changes
-    IS_LDS_MAX_N = 8192                           launch_importance_single                     weights and prefix sums in LDS or in HBM
+    IS_LDS_MAX_N = 8192                           plan_importance_single                       weights and prefix sums in LDS or in HBM
     hist_all_draws_first = 16384                  importance_kernel<HIST>                      all draws first (16-bit sources in LDS) or by rounds
     hist_update_multi = 4096 (N >= 4096)          launch_belief_update, history records        one launch or seven
     IS_MAX_CHUNKS * 256 = 65536                   fba_create, launch_uniform_scan              one workgroup per slot or seven launches; the format
@@ -32,7 +32,7 @@ SWITCHES = {
     "is_tiger_packed": ("IS_LDS_MAX_N", "IS_MAX_CHUNKS", "PARTICLE_TILE"),
     "is_tiger_dense": ("IS_LDS_MAX_N", "IS_MAX_CHUNKS"),
     "is_generic_dense": ("IS_LDS_MAX_N", "IS_MAX_CHUNKS", "PARTICLE_TILE"),
-    "is_regular_dirichlet": ("IS_MAX_CHUNKS",),                       # (never in LDS: launch_importance_single)
+    "is_regular_dirichlet": ("IS_MAX_CHUNKS",),                       # (never in LDS: plan_importance_single)
     "is_planning": ("IS_LDS_MAX_N", "IS_MAX_CHUNKS", "CARRY_TILE", "PARTICLE_TILE"),
     "is_gridworld_history": ("hist_update_multi", "IS_MAX_CHUNKS", "PARTICLE_TILE", "power_of_two"),
     "is_gridworld_history_one_launch": ("IS_LDS_MAX_N", "hist_all_draws_first", "power_of_two"),

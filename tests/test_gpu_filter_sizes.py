@@ -39,17 +39,20 @@ def _constants():
         header = f.read()
     with open(os.path.join(CSRC, "fba_kernels.hip")) as f:
         kernels = f.read()
+    with open(os.path.join(CSRC, "fba_launch_plan.h")) as f:
+        plan = f.read()
     k = {}
     for name in ("IS_LDS_MAX_N", "IS_MAX_CHUNKS", "TIGER_LDS_MAX_N", "PARTICLE_TILE", "CARRY_TILE", "REJECT_BLOCK"):
         (v,) = re.findall(r"constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % name, header)
         k[name] = int(v)
-    (v,) = re.findall(r"bool\s+hist_all_draws_first\s*\(\s*int\s+N\s*\)\s*\{\s*return\s+N\s*<=\s*(\d+)\s*;", kernels)
+    (v,) = re.findall(r"bool\s+hist_all_draws_first\s*\(\s*int\s+N\s*\)\s*\{\s*return\s+N\s*<=\s*(\d+)\s*;", plan)
     k["hist_all_draws_first"] = int(v)
-    (v,) = re.findall(r"bool\s+hist_update_multi\s*\([^)]*\)\s*\{[^}]*return\s+P\.N\s*>=\s*(\d+)\s*;", kernels)
+    (v,) = re.findall(r"bool\s+hist_update_multi\s*\([^)]*\)\s*\{[^}]*return\s+P\.N\s*>=\s*(\d+)\s*;", plan)
     k["hist_update_multi"] = int(v) - 1          # (N >= v takes the seven launches: the last one-launch filter is the c of this switch)
-    # the packed tiger rejection filter's block, both kernels (launch_belief_update)
-    (v,) = set(re.findall(r"reject_tiger_lds_kernel<(\d+)>\), dim3\(P\.E\), dim3\((?:\d+)\)", kernels))
-    assert re.search(r"reject_kernel<false, 2, 0, %s>\), dim3\(P\.E\), dim3\(%s\)" % (v, v), kernels)
+    # the packed tiger rejection filter's block, both kernels: the instantiation launched (launch_step) and the block update_plan gives it
+    (v,) = set(re.findall(r"reject_tiger_lds_kernel<(\d+)>", kernels))
+    assert re.search(r"kernel_key\(K_REJECT_TIGER_LDS\), %s," % v, plan)
+    assert re.search(r"reject_key\(false, 2, 0, %s\), %s," % (v, v), plan) and re.search(r"FBA_REJECT\(false, 2, 0, %s\)" % v, kernels)
     k["REJECT_512"] = int(v)
     return k
 

@@ -19,8 +19,13 @@ def test_once_kernels_fit_two_workgroups_per_cu(tmp_path):
                           stderr=subprocess.DEVNULL)
     with open(os.path.join(N.HERE, "csrc", "fba_kernels.h")) as f:
         assert re.search(r"constexpr\s+int\s+TIGER_LDS_MAX_N\s*=\s*%d\s*;" % TIGER_LDS_MAX_N, f.read())
-    with open(src) as f:      # the launcher's dynamic LDS of both entries, as the source states it
-        assert len(re.findall(r"reject_tiger_once(?:_gather)?_kernel<512>\), dim3\(P\.E\), dim3\(512\), \(size_t\)P\.N \* 17 \+ 16,", f.read())) == 2
+    with open(os.path.join(N.HERE, "csrc", "fba_launch_plan.h")) as f:      # the dynamic LDS and block of both entries, as update_plan states them ...
+        assert len(re.findall(r"kernel_key\(D\.ab_tiger_gather \? K_REJECT_TIGER_ONCE_GATHER : K_REJECT_TIGER_ONCE\), 512, 0, 1, \(size_t\)P\.N \* 17 \+ 16\)",
+                              f.read())) == 1
+    with open(src) as f:      # ... and the two instantiations the launcher has behind those keys, launched with the step's LDS
+        text = f.read()
+        assert len(re.findall(r"case kernel_key\(K_REJECT_TIGER_ONCE(?:_GATHER)?\): FBA_STEP\(reject_tiger_once(?:_gather)?_kernel<512>\)", text)) == 2
+        assert "#define FBA_STEP(...) { hipLaunchKernelGGL((__VA_ARGS__), grid, block, s.lds, st, P, D); return; }" in text
     meta = out.read_text()
     meta = meta[meta.index("amdhsa.kernels:"):]
     seen = {}
