@@ -110,6 +110,11 @@ class KernelTime(C.Structure):
     _fields_ = [("ms", C.c_double), ("launches", C.c_uint64), ("units", C.c_uint64), ("bytes", C.c_uint64)]
 
 
+class ArrayInfo(C.Structure):   # fba_array_info
+    _fields_ = [("name", C.c_char * 32), ("elem_bytes", C.c_uint64), ("elems", C.c_uint64), ("slot_elems", C.c_uint64),
+                ("buffers", C.c_int32), ("reserved", C.c_int32)]
+
+
 class BeliefSummaryHead(C.Structure):   # fba_belief_summary_head
     _fields_ = [("weight_total", C.c_double), ("weight_sq_total", C.c_double), ("particles", C.c_int32), ("weighted", C.c_int32)]
 
@@ -143,7 +148,7 @@ def snapshot_checksum(payload):
 # every symbol include/fba_hip.h declares
 EXPORTS = [
     "fba_abi_version", "fba_default_config", "fba_create", "fba_destroy", "fba_last_error",
-    "fba_domain_sizes", "fba_counts_len", "fba_slots", "fba_particle_bytes", "fba_set_model_tabular", "fba_set_model_factored", "fba_log_bd_score", "fba_selftest_lgamma", "fba_get_prior", "fba_get_factored_layout",
+    "fba_domain_sizes", "fba_counts_len", "fba_slots", "fba_device_arrays", "fba_particle_bytes", "fba_set_model_tabular", "fba_set_model_factored", "fba_log_bd_score", "fba_selftest_lgamma", "fba_get_prior", "fba_get_factored_layout",
     "fba_set_position", "fba_belief_init", "fba_belief_reset_domain_state", "fba_select_action",
     "fba_belief_update", "fba_belief_get", "fba_belief_get_particle", "fba_belief_set", "fba_belief_get_fully_connected", "fba_belief_get_nested", "fba_belief_get_shadow", "fba_belief_summary", "fba_predict_lens", "fba_belief_predict", "fba_belief_forecast", "fba_last_step_info",
     "fba_run_planning", "fba_run_bapomdp", "fba_run_ticks", "fba_get_returns", "fba_get_counters", "fba_get_return_sums",
@@ -221,6 +226,8 @@ def load():
     L.fba_counts_len.argtypes = [vp]
     L.fba_particle_bytes.argtypes = [vp]
     L.fba_slots.argtypes = [vp]
+    if not os.environ.get("FBA_LIB") or hasattr(L, "fba_device_arrays"):
+        L.fba_device_arrays.argtypes = [vp, P(ArrayInfo), C.c_int32]
     L.fba_set_model_tabular.argtypes = [vp, vp, vp]
     L.fba_set_model_factored.argtypes = [vp, vp, vp]
     L.fba_log_bd_score.argtypes = [vp, vp, vp, vp]

@@ -39,6 +39,8 @@ struct fba_ctx {
     hipStream_t stream = nullptr;
     std::string err;
     std::vector<void*> allocs;
+    struct ArrayEntry { const void* p; fba_array_info info; };
+    std::vector<ArrayEntry> arrays;   // fba_device_arrays: one entry per named dev_alloc, in allocation order
     std::vector<float> prior;  // host copy, dense_C floats
     int dense_C          = 0;   // length of a particle's count table as the API sees it (= P.C unless P.packed)
     float* d_prior       = nullptr;
@@ -121,6 +123,31 @@ int dev_alloc(fba_ctx* c, T** p, size_t n, bool zero = true)
     return FBA_OK;
 }
 
+// dev_alloc of an array that fba_device_arrays reports, under the name of the member that holds it: `buffers` buffers in which every
+// slot takes `slot_elems` elements (0: the array is not laid out by slot).  The entry is written here and nowhere else, from the very
+// numbers the allocation used
+template <typename T>
+int dev_alloc(fba_ctx* c, const char* name, T** p, size_t n, size_t slot_elems = 0, int buffers = 1, bool zero = true)
+{
+    TRY(dev_alloc(c, p, n, zero));
+    fba_array_info a{};
+    std::snprintf(a.name, sizeof a.name, "%s", name);
+    a.elem_bytes = sizeof(T);
+    a.elems      = n ? n : 1;
+    a.slot_elems = slot_elems;
+    a.buffers    = buffers;
+    c->arrays.push_back({*p, a});
+    return FBA_OK;
+}
+#define ARR(m) #m, &D.m   // a DeviceState member as (name, pointer)
+
+// ... of `buffers` buffers of E slots of slot_elems elements each
+template <typename T>
+int slot_alloc(fba_ctx* c, const char* name, T** p, size_t slot_elems, int buffers = 1, bool zero = true)
+{
+    return dev_alloc(c, name, p, (size_t)buffers * c->P.E * slot_elems, slot_elems, buffers, zero);
+}
+
 // gives a dev_alloc'ed buffer back before the ctx goes (buffers that are re-grown: the trace)
 template <typename T>
 void dev_free(fba_ctx* c, T*& p)
@@ -128,6 +155,7 @@ void dev_free(fba_ctx* c, T*& p)
     if (!p) return;
     auto it = std::find(c->allocs.begin(), c->allocs.end(), static_cast<void*>(p));
     if (it != c->allocs.end()) c->allocs.erase(it);
+    c->arrays.erase(std::remove_if(c->arrays.begin(), c->arrays.end(), [&](const fba_ctx::ArrayEntry& a) { return a.p == p; }), c->arrays.end());
     (void)hipFree(p);
     p = nullptr;
 }
@@ -143,9 +171,10 @@ int ensure_trace(fba_ctx* c, size_t want)
         HIPCHK(c, hipStreamSynchronize(c->stream));   // (nothing in flight reads the old buffers)
         dev_free(c, c->D.trace);
         dev_free(c, c->D.trace_hist);
-        if ((rc = dev_alloc(c, &c->D.trace, cap))) return rc;
+        DeviceState& D = c->D;
+        if ((rc = dev_alloc(c, ARR(trace), cap))) return rc;
         if (hist)
-            if ((rc = dev_alloc(c, &c->D.trace_hist, cap * FBA_TRACE_HIST_BINS))) return rc;
+            if ((rc = dev_alloc(c, ARR(trace_hist), cap * FBA_TRACE_HIST_BINS))) return rc;
         c->D.trace_cap = (int32_t)cap;
     }
     HIPCHK(c, hipMemsetAsync(c->D.trace_count, 0, sizeof(int32_t), c->stream));
@@ -1143,8 +1172,11 @@ int ensure_outputs(fba_ctx* c, int runs)
     const size_t need = (size_t)std::max(runs, 1) * c->P.episodes;
     if (need > c->returns_cap) {
         int rc;
-        if ((rc = dev_alloc(c, &c->D.returns, need))) return rc;
-        if ((rc = dev_alloc(c, &c->D.lengths, need))) return rc;
+        DeviceState& D = c->D;   // (re-grown like the trace: the old buffers go, and their entries of the report with them)
+        dev_free(c, D.returns);
+        dev_free(c, D.lengths);
+        if ((rc = dev_alloc(c, ARR(returns), need))) return rc;
+        if ((rc = dev_alloc(c, ARR(lengths), need))) return rc;
         c->returns_cap = need;
     } else {
         HIPCHK(c, hipMemsetAsync(c->D.returns, 0, need * sizeof(double), c->stream));
@@ -1765,12 +1797,12 @@ int check_packed_kernels(fba_ctx* c)
 }
 
 // ---- stage 5: the device buffers, grouped as the data is, and the uploads
-template <typename... T>
-int alloc_each(fba_ctx* c, size_t n, T**... p)   // n zeroed elements for every one of the pointers
+inline int alloc_each(fba_ctx*, size_t, size_t) { return FBA_OK; }
+template <typename T, typename... R>
+int alloc_each(fba_ctx* c, size_t n, size_t slot_elems, const char* name, T** p, R... rest)   // n zeroed elements for every one of the ARR()s
 {
-    int rc = FBA_OK;
-    ((rc = rc ? rc : dev_alloc(c, p, n)), ...);
-    return rc;
+    TRY(dev_alloc(c, name, p, n, slot_elems));
+    return alloc_each(c, n, slot_elems, rest...);
 }
 
 // per slot: where its run stands and what its last step was (slot bookkeeping), then its counters; the context's single words
@@ -1778,12 +1810,12 @@ int alloc_slot_state(fba_ctx* c)
 {
     DeviceState& D = c->D;
     const size_t E = (size_t)c->P.E;
-    TRY(alloc_each(c, E, &D.run, &D.episode, &D.t, &D.active, &D.need_update, &D.need_reset, &D.need_init, &D.adv, &D.env_state, &D.ret, &D.disc,
-                   &D.action, &D.obs, &D.bufsel, &D.cur, &D.lazy_reset, &D.compact));
-    TRY(alloc_each(c, E, &D.sim_steps, &D.belief_steps, &D.env_steps, &D.upd_particles, &D.upd_attempts, &D.upd_entries, &D.upd_compact_full,
-                   &D.upd_compact));
-    TRY(dev_alloc(c, &D.ep_sums, 3 * E));
-    TRY(alloc_each(c, 1, &D.trace_count, &c->d_n_active, &D.fault));
+    TRY(alloc_each(c, E, 1, ARR(run), ARR(episode), ARR(t), ARR(active), ARR(need_update), ARR(need_reset), ARR(need_init), ARR(adv), ARR(env_state),
+                   ARR(ret), ARR(disc), ARR(action), ARR(obs), ARR(bufsel), ARR(cur), ARR(lazy_reset), ARR(compact)));
+    TRY(alloc_each(c, E, 1, ARR(sim_steps), ARR(belief_steps), ARR(env_steps), ARR(upd_particles), ARR(upd_attempts), ARR(upd_entries),
+                   ARR(upd_compact_full), ARR(upd_compact)));
+    TRY(slot_alloc(c, ARR(ep_sums), 3));
+    TRY(alloc_each(c, 1, 0, ARR(trace_count), "n_active", &c->d_n_active, ARR(fault)));
     D.trace_on   = c->cfg.trace ? 1 : 0;
     D.runs_total = c->cfg.runs;
     D.run_offset = c->cfg.run_offset;
@@ -1796,23 +1828,25 @@ int alloc_filters(fba_ctx* c, const CreateSwitches& sw)
     DeviceState& D = c->D;
     const int E = P.E;
     const bool is = weighted_filters(P);
-    TRY(dev_alloc(c, &D.p_weight, is ? (size_t)2 * E * P.N : 1));
+    const size_t rec = (size_t)P.N * P.Cs;
+    TRY(is ? slot_alloc(c, ARR(p_weight), P.N, 2) : dev_alloc(c, ARR(p_weight), 1));
     if (D.single_rec) D.scratch_slots = sw.scratch_slots ? std::min(E, sw.scratch_slots) : std::min(E, 1024);
     // (zeroed: a slot whose belief was never initiated -- a slot of fba_run_bapomdp beyond the configured runs -- then holds all-zero records and weights, which is
     // what fba_belief_export writes for it and a block fba_belief_import takes in every record format; nothing else reads such a slot)
-    TRY(dev_alloc(c, &D.p_rec, (D.single_rec ? (size_t)E + D.scratch_slots : (size_t)2 * E) * P.N * P.Cs, true));
+    // (single_rec: reported as ONE buffer, the scratch places' records behind the E slots')
+    TRY(D.single_rec ? dev_alloc(c, ARR(p_rec), ((size_t)E + D.scratch_slots) * rec, rec) : slot_alloc(c, ARR(p_rec), rec, 2));
     if (D.single_rec) {   // E + scratch_slots buffers; a slot's filter and a scratch place's buffer change places after a resample / reset (swap_buffers_kernel)
-        TRY(dev_alloc(c, &D.rec_buf, (size_t)E + D.scratch_slots));
+        TRY(dev_alloc(c, ARR(rec_buf), (size_t)E + D.scratch_slots, 1));
         std::vector<int32_t> ids((size_t)E + D.scratch_slots);
         for (size_t i = 0; i < ids.size(); ++i) ids[i] = (int32_t)i;
         HIPCHK(c, hipMemcpy(D.rec_buf, ids.data(), ids.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        TRY(dev_alloc(c, &D.copy_pending, E));
+        TRY(slot_alloc(c, ARR(copy_pending), 1));
     }
-    TRY(dev_alloc(c, &D.wscan, is ? (size_t)E * P.N : 1, false));
-    TRY(dev_alloc(c, &D.hist_cnt, E));
-    TRY(dev_alloc(c, &D.p_side, is ? (size_t)E * P.N * D.side_w : 1, false));
-    TRY(dev_alloc(c, &D.ctot, is ? (size_t)E * D.ctot_stride : 1));
-    TRY(dev_alloc(c, &D.is_tot, (size_t)2 * E));
+    TRY(is ? slot_alloc(c, ARR(wscan), P.N, 1, false) : dev_alloc(c, ARR(wscan), 1, 0, 1, false));
+    TRY(slot_alloc(c, ARR(hist_cnt), 1));
+    TRY(is ? slot_alloc(c, ARR(p_side), (size_t)P.N * D.side_w, 1, false) : dev_alloc(c, ARR(p_side), 1, 0, 1, false));
+    TRY(is ? slot_alloc(c, ARR(ctot), D.ctot_stride) : dev_alloc(c, ARR(ctot), 1));
+    TRY(slot_alloc(c, ARR(is_tot), 2));
     return FBA_OK;
 }
 
@@ -1837,36 +1871,36 @@ int alloc_composite(fba_ctx* c)
     DeviceState& D = c->D;
     const int E = P.E;
     if (P.reinvig || P.cheat || P.incub) {
-        TRY(dev_alloc(c, &D.p_rec_fc, (size_t)2 * E * P.N * P.Cs, false));
-        TRY(dev_alloc(c, &D.bufsel_fc, E));
+        TRY(slot_alloc(c, ARR(p_rec_fc), (size_t)P.N * P.Cs, 2, false));
+        TRY(slot_alloc(c, ARR(bufsel_fc), 1));
     }
     if (P.incub) {
-        TRY(dev_alloc(c, &D.p_rec_sh, (size_t)2 * E * P.N * P.Cs, false));
-        TRY(dev_alloc(c, &D.p_weight_sh, (size_t)2 * E * P.N));
-        TRY(alloc_each(c, E, &D.bufsel_sh, &D.need_update_sh));
+        TRY(slot_alloc(c, ARR(p_rec_sh), (size_t)P.N * P.Cs, 2, false));
+        TRY(slot_alloc(c, ARR(p_weight_sh), P.N, 2));
+        TRY(alloc_each(c, E, 1, ARR(bufsel_sh), ARR(need_update_sh)));
         const std::vector<int32_t> order = incubator_breeding_order(P.incub);
         int32_t* d_order = nullptr;
-        TRY(dev_alloc(c, &d_order, order.size()));
+        TRY(dev_alloc(c, "inc_order", &d_order, order.size()));
         HIPCHK(c, hipMemcpy(d_order, order.data(), order.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         D.inc_order = d_order;
     }
     if (P.nested) {
-        TRY(dev_alloc(c, &D.nest_s, (size_t)2 * E * P.N * P.nested));
-        TRY(dev_alloc(c, &D.nest_scan, (size_t)E * P.N));
-        TRY(alloc_each(c, E, &D.nest_sel, &D.nest_total));
+        TRY(slot_alloc(c, ARR(nest_s), (size_t)P.N * P.nested, 2));
+        TRY(slot_alloc(c, ARR(nest_scan), P.N));
+        TRY(alloc_each(c, E, 1, ARR(nest_sel), ARR(nest_total)));
     }
     if (P.mh || P.cheat) {   // the log likelihood per slot, and the threshold behind them
-        TRY(dev_alloc(c, &D.lik, (size_t)E + 1));
-        TRY(dev_alloc(c, &D.cheat_pending, E));
+        TRY(dev_alloc(c, ARR(lik), (size_t)E + 1, 1));
+        TRY(slot_alloc(c, ARR(cheat_pending), 1));
         const double thr = c->cfg.threshold;
         HIPCHK(c, hipMemcpy(D.lik + E, &thr, sizeof thr, hipMemcpyHostToDevice));
     }
     if (P.mh) {
         const size_t cap = (size_t)P.episodes * P.horizon;
-        TRY(alloc_each(c, (size_t)E * cap, &D.mh_a, &D.mh_o));
-        TRY(dev_alloc(c, &D.mh_ep_len, (size_t)E * (P.episodes + 1)));
-        TRY(dev_alloc(c, &D.mh_n_ep, E));
-        if (!mh_scratch_in_lds(D.mh_scratch_words)) TRY(dev_alloc(c, &D.mh_scratch, (size_t)E * D.mh_scratch_words));  // (else the chain's scratch is LDS)
+        TRY(alloc_each(c, (size_t)E * cap, cap, ARR(mh_a), ARR(mh_o)));
+        TRY(slot_alloc(c, ARR(mh_ep_len), P.episodes + 1));
+        TRY(slot_alloc(c, ARR(mh_n_ep), 1));
+        if (!mh_scratch_in_lds(D.mh_scratch_words)) TRY(slot_alloc(c, ARR(mh_scratch), D.mh_scratch_words));  // (else the chain's scratch is LDS)
     }
     return FBA_OK;
 }
@@ -1878,25 +1912,25 @@ int alloc_tree(fba_ctx* c, const TreePlan& t)
     const size_t E = (size_t)c->P.E;
     if (t.bkt_lines) {
         D.bkt_lines = (int32_t)t.bkt_lines;
-        TRY(dev_alloc(c, &D.bkt, E * t.bkt_lines * 8));   // (zeroed: key 0 carries epoch 0, which no search uses)
-        TRY(dev_alloc(c, &D.epoch, E));
-        TRY(dev_alloc(c, &D.nodes, 16));
+        TRY(slot_alloc(c, ARR(bkt), t.bkt_lines * 8));   // (zeroed: key 0 carries epoch 0, which no search uses)
+        TRY(slot_alloc(c, ARR(epoch), 1));
+        TRY(dev_alloc(c, ARR(nodes), 16));
     } else {
-        TRY(dev_alloc(c, &D.nodes, E * D.max_nodes * D.node_words, false));
+        TRY(slot_alloc(c, ARR(nodes), (size_t)D.max_nodes * D.node_words, 1, false));
         if (t.hashed) {
-            TRY(dev_alloc(c, &D.hash, E * t.hcap * t.hash_entry / 16));
-            TRY(dev_alloc(c, &D.epoch, E));
+            TRY(slot_alloc(c, ARR(hash), t.hcap * t.hash_entry / 16));
+            TRY(slot_alloc(c, ARR(epoch), 1));
         }
     }
-    if (D.bkt && D.ab_lockstep) TRY(dev_alloc(c, &D.search_order, E));
+    if (D.bkt && D.ab_lockstep) TRY(slot_alloc(c, ARR(search_order), 1));
     if (!D.search_order) D.ab_lockstep = 0;   // (lock-step waves exist on the bucket tree only: search_hist2_kernel)
     if (c->P.search_budget <= 0) return FBA_OK;
     // budgeted searches: where a parked search stands
-    TRY(alloc_each(c, E, &D.s_sim, &D.s_nodes, &D.s_depth, &D.search_done));
-    if (D.bkt) TRY(dev_alloc(c, &D.s_root, 6 * E));
+    TRY(alloc_each(c, E, 1, ARR(s_sim), ARR(s_nodes), ARR(s_depth), ARR(search_done)));
+    if (D.bkt) TRY(slot_alloc(c, ARR(s_root), 6));
     if (D.single_rec) {   // the chunked belief launches run over compacted lists of the slots that have work (fba_state.h)
-        TRY(alloc_each(c, E, &D.slot_list, &D.scratch_idx));
-        TRY(dev_alloc(c, &D.list_count, 1));
+        TRY(alloc_each(c, E, 1, ARR(slot_list), ARR(scratch_idx)));
+        TRY(dev_alloc(c, ARR(list_count), 1));
         HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&D.list_count_host), sizeof(int32_t), hipHostMallocDefault));
     }
     return FBA_OK;
@@ -2117,6 +2151,14 @@ int fba_domain_sizes(const fba_ctx* c, int32_t* S, int32_t* A, int32_t* O)
 int fba_counts_len(const fba_ctx* c) { return c ? c->dense_C : FBA_EINVAL; }
 int fba_slots(const fba_ctx* c) { return c ? c->P.E : FBA_EINVAL; }
 int fba_particle_bytes(const fba_ctx* c) { return c ? c->P.Cs * 4 : FBA_EINVAL; }
+
+int fba_device_arrays(const fba_ctx* c, fba_array_info* out, int32_t cap)
+{
+    if (!c || cap < 0 || (cap > 0 && !out)) return FBA_EINVAL;
+    const int32_t n = (int32_t)c->arrays.size();
+    for (int32_t i = 0; i < std::min(n, cap); ++i) out[i] = c->arrays[(size_t)i].info;
+    return n;
+}
 
 int fba_set_model_tabular(fba_ctx* c, const float* phi, const float* psi)
 {

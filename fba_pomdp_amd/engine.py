@@ -6,6 +6,7 @@ BABelief::resetDomainStateDistribution (BABelief.hpp:34), `run_planning` / `run_
 experiment::planning::run / experiment::bapomdp::run.  Errors the reference throws as strings
 surface as ValueError with the same wording.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -68,6 +69,15 @@ class BeliefSummary:
         self.edge_prob = edge_prob                        # [slots][n_mask_words][FBA_MAX_FEATURES]
 
 
+class DeviceArray(collections.namedtuple("DeviceArray", "name elem_bytes elems slot_elems buffers")):
+    """One entry of Engine.device_arrays()."""
+    __slots__ = ()
+
+    @property
+    def bytes(self):
+        return self.elem_bytes * self.elems
+
+
 class Engine:
     """One fba_ctx: `slots` independent (planner, belief) pairs resident on one MI355X."""
 
@@ -112,6 +122,19 @@ class Engine:
         if rc != N.OK:
             msg = self.L.fba_last_error(self.h).decode()
             raise (ValueError if rc == N.EINVAL else FbaError)(msg)
+
+    def device_arrays(self):
+        """What the context holds on the device (fba_device_arrays): {name: DeviceArray}, in allocation order.  A per-slot array is
+        `buffers` buffers of `slots` slots of `slot_elems` elements; the sum of `bytes` is what a context of this configuration takes."""
+        n = self._count(self.L.fba_device_arrays(self.h, None, 0))
+        out = (N.ArrayInfo * n)()
+        n = min(n, self._count(self.L.fba_device_arrays(self.h, out, n)))
+        return {a.name.decode(): DeviceArray(a.name.decode(), a.elem_bytes, a.elems, a.slot_elems, a.buffers) for a in out[:n]}
+
+    def _count(self, n):
+        if n < 0:
+            self._chk(n)
+        return n
 
     # ---- experiments
     def run_planning(self):

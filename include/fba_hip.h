@@ -216,6 +216,25 @@ int fba_particle_bytes(const fba_ctx* ctx); /* HBM bytes of one particle record.
                                              * fp32 counts.  fba_belief_get / fba_belief_set always speak fp32 counts. */
 int fba_slots(const fba_ctx* ctx);      /* slots actually resident (cfg.slots, or the library's choice) */
 
+/* The device arrays the context holds for its slots, filters, composite beliefs, search trees and -- once an experiment has been
+ * started -- its per-run returns and trace, in allocation order: what a context of this configuration takes in HBM (the sum of
+ * elems * elem_bytes; the prior's tables and the probe, a few kilobytes to megabytes, are not listed) and where one slot's part of an
+ * array stands.  A per-slot array is `buffers` buffers of fba_slots slots of slot_elems
+ * elements each: the part of slot e in buffer b starts at element (b * fba_slots + e) * slot_elems.  History records keep one buffer
+ * (buffers = 1) with the scratch places' records behind the slots', so elems exceeds buffers * fba_slots * slot_elems there; which
+ * record buffer is whose changes while the context runs.  Arrays a configuration does not use are absent or one element long.  Host
+ * bookkeeping only: nothing is launched or copied.  Writes min(cap, n) entries to out (NULL with cap = 0) and returns n, the number of
+ * arrays, which grows when an experiment allocates its returns and trace. */
+typedef struct fba_array_info {
+    char     name[32];     /* the member of the engine's device state that holds the array: "p_rec", "nodes", "bkt", ... */
+    uint64_t elem_bytes;   /* bytes of one element                                                                       */
+    uint64_t elems;        /* elements allocated                                                                         */
+    uint64_t slot_elems;   /* elements one slot takes in one buffer; 0: the array is not laid out by slot                */
+    int32_t  buffers;      /* buffers of fba_slots slots each                                                            */
+    int32_t  reserved;
+} fba_array_info;
+int fba_device_arrays(const fba_ctx* ctx, fba_array_info* out, int32_t cap);
+
 /* Prior count tables.  fba_create builds the domain's own prior (TigerPriors.cpp:14-43,
  * FactoredTigerPriors.cpp:18-88); this call overrides it with tables built by the caller
  * (BAFlatModel layout: phi[s*A*S + a*S + s'], psi[a*S*O + s'*O + o]).  Takes effect at the next

@@ -179,7 +179,10 @@ def expected_particle_bytes(c, ncnt):
 
 def sample_runs(c):
     """The runs compared where the whole experiment is too long for the oracle: the first slot, both sides of lane 23 | 24 (all that the
-    other tests reach), of the wave boundary 63 | 64, the last slot and the first run of the second and third round, and the last run."""
+    other tests reach), of the wave boundary 63 | 64, the last slot and the first run of the second and third round, and the last run.
+    (A case that brings its own list under "sample_runs" has those compared: tests/far_slot_cases.py.)"""
+    if "sample_runs" in c:
+        return sorted(set(c["sample_runs"]))
     E, runs = c["E"], c["runs"]
     return sorted({0, 23, 24, 63, 64, 65, E - 1, E, 2 * E - 1, 2 * E, runs - 1})
 
