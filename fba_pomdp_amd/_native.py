@@ -12,8 +12,8 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB_PATH = os.environ.get("FBA_LIB") or os.path.join(HERE, "libfba_hip.so")   # (FBA_LIB: an instrumented build of the same sources, scripts/search_regions.py)
-SOURCES = [os.path.join(HERE, "csrc", f) for f in ("fba_search.hip", "fba_kernels.hip", "fba_summary.hip", "fba_predict.hip", "fba_forecast.hip", "fba_probe.hip", "fba_snapshot.hip", "fba_restore.hip", "fba_engine.hip")]
-HEADERS = [os.path.join(HERE, "csrc", f) for f in ("fba_device.h", "fba_state.h", "fba_kernels.h", "fba_launch_plan.h", "fba_kernels_common.h", "fba_belief_factors.h", "fba_snapshot_format.h", "fba_search_hist2.inc")] + [
+SOURCES = [os.path.join(HERE, "csrc", f) for f in ("fba_search.hip", "fba_kernels.hip", "fba_summary.hip", "fba_predict.hip", "fba_forecast.hip", "fba_probe.hip", "fba_structures.hip", "fba_snapshot.hip", "fba_restore.hip", "fba_engine.hip")]
+HEADERS = [os.path.join(HERE, "csrc", f) for f in ("fba_device.h", "fba_state.h", "fba_kernels.h", "fba_launch_plan.h", "fba_kernels_common.h", "fba_belief_factors.h", "fba_snapshot_format.h", "fba_structures.h", "fba_search_hist2.inc")] + [
     os.path.join(ROOT, "include", "fba_hip.h")]
 OBJ_DIR = os.path.join(HERE, "build")   # per-source objects (git-ignored): a change to one translation unit recompiles that one
 
@@ -121,6 +121,11 @@ class BeliefSummaryHead(C.Structure):   # fba_belief_summary_head
 
 SUMMARY_HEAD_DTYPE = np.dtype([("weight_total", "<f8"), ("weight_sq_total", "<f8"), ("particles", "<i4"), ("weighted", "<i4")], align=True)
 
+# fba_structure_head, and the limits of fba_belief_structures
+STRUCT_MAX_TOP, STRUCT_TABLE = 64, 2048
+STRUCTURE_HEAD_DTYPE = np.dtype([("weight_total", "<f8"), ("unplaced_mass", "<f8"), ("distinct", "<i4"), ("overflow", "<i4"), ("stored", "<i4"),
+                                 ("reserved", "<i4")], align=True)
+
 # fba_probe_rec
 PROBE_DTYPE = np.dtype([
     ("run", "<i4"), ("episode", "<i4"), ("t", "<i4"), ("slot", "<i4"),
@@ -150,7 +155,7 @@ EXPORTS = [
     "fba_abi_version", "fba_default_config", "fba_create", "fba_destroy", "fba_last_error",
     "fba_domain_sizes", "fba_counts_len", "fba_slots", "fba_device_arrays", "fba_particle_bytes", "fba_set_model_tabular", "fba_set_model_factored", "fba_log_bd_score", "fba_selftest_lgamma", "fba_get_prior", "fba_get_factored_layout",
     "fba_set_position", "fba_belief_init", "fba_belief_reset_domain_state", "fba_select_action",
-    "fba_belief_update", "fba_belief_get", "fba_belief_get_particle", "fba_belief_set", "fba_belief_get_fully_connected", "fba_belief_get_nested", "fba_belief_get_shadow", "fba_belief_summary", "fba_predict_lens", "fba_belief_predict", "fba_belief_forecast", "fba_last_step_info",
+    "fba_belief_update", "fba_belief_get", "fba_belief_get_particle", "fba_belief_set", "fba_belief_get_fully_connected", "fba_belief_get_nested", "fba_belief_get_shadow", "fba_belief_summary", "fba_predict_lens", "fba_belief_predict", "fba_belief_forecast", "fba_structure_lens", "fba_belief_structures", "fba_last_step_info",
     "fba_run_planning", "fba_run_bapomdp", "fba_run_ticks", "fba_get_returns", "fba_get_counters", "fba_get_return_sums",
     "fba_get_kernel_times", "fba_reset_kernel_times", "fba_trace_count", "fba_get_trace", "fba_get_trace_hist",
     "fba_probe_enable", "fba_probe_count", "fba_get_probe",
@@ -254,6 +259,10 @@ def load():
         L.fba_belief_predict.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp]   # four int32 query arrays; trans, obsp, joint
     if not os.environ.get("FBA_LIB") or hasattr(L, "fba_belief_forecast"):
         L.fba_belief_forecast.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]   # action, obs (int32); next_mass, post_mass, evidence
+    if not os.environ.get("FBA_LIB") or hasattr(L, "fba_belief_structures"):
+        L.fba_structure_lens.argtypes = [vp, P(C.c_int32), P(C.c_int32)]
+        # first, count, top_k, nq, query (uint32); head, set_mass, top_words (uint32), top_mass, query_mass
+        L.fba_belief_structures.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]
     L.fba_last_step_info.argtypes = [vp, vp]
     L.fba_run_planning.argtypes = [vp, P(Stat)]
     L.fba_run_bapomdp.argtypes = [vp, P(Stat)]

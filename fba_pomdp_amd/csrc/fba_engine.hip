@@ -2558,6 +2558,122 @@ int fba_belief_summary(fba_ctx* c, int32_t first, int32_t count, fba_belief_summ
     return check_fault(c);
 }
 
+// per parent-set word of a factored model: the word is legal below this (1 << n_candidates of every node it serves, the rule of
+// fba_belief_import); empty where the model has no words
+static void structure_limits(const fba_ctx* c, std::vector<uint32_t>& limit)
+{
+    limit.clear();
+    if (c->P.model != FBA_MODEL_BA_FACTORED || c->fdesc.nvar <= 0) return;
+    limit.assign((size_t)c->fdesc.nvar, 0xffffffffu);
+    const int nodes = c->P.A * (c->fdesc.FS + c->fdesc.FO);
+    for (int k = 0; k < nodes && k < MAXNODES; ++k) {
+        const FNode& nd = c->fdesc.nodes[k];
+        if (nd.var >= 0 && nd.var < c->fdesc.nvar && nd.nmax >= 0 && nd.nmax < 32) limit[(size_t)nd.var] = std::min(limit[(size_t)nd.var], 1u << nd.nmax);
+    }
+}
+
+int fba_structure_lens(const fba_ctx* c, int32_t* n_words, int32_t* n_sets)
+{
+    if (!c) return FBA_EINVAL;
+    int nw = 0, ns = 0;
+    if (c->P.model == FBA_MODEL_BA_FACTORED && c->fdesc.nvar > 0) {
+        nw = c->fdesc.nvar;
+        int most = 0;
+        const int nodes = c->P.A * (c->fdesc.FS + c->fdesc.FO);
+        for (int k = 0; k < nodes && k < MAXNODES; ++k)
+            if (c->fdesc.nodes[k].var >= 0) most = std::max(most, (int)c->fdesc.nodes[k].nmax);
+        ns = 1 << std::min(most, MAXF);
+    }
+    if (n_words) *n_words = nw;
+    if (n_sets) *n_sets = ns;
+    return FBA_OK;
+}
+
+// The parent-set word lists of slots [first, first + count) reduced on the device (fba_structures.hip), a chunk of slots at a time so that
+// the buffers of a chunk stay below 256 MB.  Reads the context only, as fba_belief_summary does.
+int fba_belief_structures(fba_ctx* c, int32_t first, int32_t count, int32_t top_k, int32_t nq, const uint32_t* query, fba_structure_head* head,
+                          double* set_mass, uint32_t* top_words, double* top_mass, double* query_mass)
+{
+    if (!c) return FBA_EINVAL;
+    const Problem& P = c->P;
+    if (P.nested)
+        return fail(c, FBA_EINVAL, "fba_belief_structures: the nested belief's particles are (model, state filter) pairs; read them with "
+                                   "fba_belief_get and fba_belief_get_nested");
+    int32_t nw = 0, ns = 0;
+    fba_structure_lens(c, &nw, &ns);
+    if (nw == 0)
+        return fail(c, FBA_EINVAL, "fba_belief_structures: the model has no parent-set words (fba_structure_lens is 0, 0): %s",
+                    P.model == FBA_MODEL_BA_FACTORED ? "its graph is fixed" : "only a factored model under a structure prior learns its graph");
+    if (first < 0 || count < 0 || (long long)first + count > P.E)
+        return fail(c, FBA_EINVAL, "fba_belief_structures: slots [%d, %lld) are not within the context's %d", first, (long long)first + count, P.E);
+    if (top_k < 0 || top_k > FBA_STRUCT_MAX_TOP) return fail(c, FBA_EINVAL, "fba_belief_structures: top_k %d (0 to %d are served)", top_k, FBA_STRUCT_MAX_TOP);
+    if (nq < 0 || nq > (1 << 16)) return fail(c, FBA_EINVAL, "fba_belief_structures: %d queries (0 to 65 536 are served)", nq);
+    if (nq > 0 && !query) return fail(c, FBA_EINVAL, "fba_belief_structures: %d queries and no query array", nq);
+    std::vector<uint32_t> limit;
+    structure_limits(c, limit);
+    for (int q = 0; q < nq; ++q)
+        for (int m = 0; m < nw; ++m)
+            if (query[(size_t)q * nw + m] >= limit[(size_t)m])
+                return fail(c, FBA_EINVAL, "fba_belief_structures: query %d, word %d: 0x%x names a parent beyond the node's candidates (legal below 0x%x)", q, m,
+                            query[(size_t)q * nw + m], limit[(size_t)m]);
+    if (top_k == 0) { top_words = nullptr; top_mass = nullptr; }
+    if (nq == 0) query_mass = nullptr;
+    if (count == 0 || (!head && !set_mass && !top_words && !top_mass && !query_mass)) return FBA_OK;
+    if (P.hist && (P.hist != 1 || nw != 2 * P.A || nw >= 32)) return fail(c, FBA_ESTATE, "fba_belief_structures: history records without their %d parent-set words", 2 * P.A);
+    if (P.ft_packed && nw != 1) return fail(c, FBA_ESTATE, "fba_belief_structures: packed factored-tiger records of %d parent-set words", nw);
+    // the queries as the records hold a structure: history records keep one bit per word (the word is 3 or 7, fba_belief_get expands it)
+    const int nk = P.hist ? 1 : nw;
+    std::vector<uint32_t> keys;
+    if (query_mass) {
+        keys.assign((size_t)nq * nk, 0u);
+        for (int q = 0; q < nq; ++q) {
+            const uint32_t* qw = query + (size_t)q * nw;
+            if (!P.hist) { std::copy(qw, qw + nw, keys.begin() + (size_t)q * nk); continue; }
+            uint32_t bits = 0;
+            for (int m = 0; m < nw; ++m) {
+                if (qw[m] == 7u) bits |= 1u << m;
+                else if (qw[m] != 3u) { bits = 0xffffffffu; break; }   // (legal for the node, but no record holds it: mass 0)
+            }
+            keys[(size_t)q] = bits;
+        }
+    }
+    uint64_t keep = ~0ull;   // (FBA_STRUCT_HASH_KEEP in the environment: the bits of the table's hash that count, read at every call -- the tests' way to equal hashes)
+    if (const char* ev = std::getenv("FBA_STRUCT_HASH_KEEP")) keep = std::strtoull(ev, nullptr, 0);
+    const size_t per_slot = sizeof(fba_structure_head) + (set_mass ? (size_t)nw * ns * 8 : 0) + (top_words ? (size_t)top_k * nw * 4 : 0) +
+                            (top_mass ? (size_t)top_k * 8 : 0) + (query_mass ? (size_t)nq * 8 : 0);
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>({(size_t)count, (size_t)32768, ((size_t)256 << 20) / per_slot}));
+    ScratchBuf<fba_structure_head> d_head;
+    ScratchBuf<double> d_set, d_tmass, d_qmass;
+    ScratchBuf<uint32_t> d_twords, d_query;
+    materialize_records(c);   // the kernel below reads 64-byte records
+    HIPCHK(c, d_head.alloc((size_t)chunk));
+    if (set_mass) HIPCHK(c, d_set.alloc((size_t)chunk * nw * ns));
+    if (top_words) HIPCHK(c, d_twords.alloc((size_t)chunk * top_k * nw));
+    if (top_mass) HIPCHK(c, d_tmass.alloc((size_t)chunk * top_k));
+    if (query_mass) {
+        HIPCHK(c, d_qmass.alloc((size_t)chunk * nq));
+        HIPCHK(c, d_query.alloc(keys.size()));
+        HIPCHK(c, hipMemcpyAsync(d_query.p, keys.data(), keys.size() * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    for (int done = 0; done < count; done += chunk) {
+        const int n = std::min(chunk, count - done);
+        BeliefStructuresArgs a{};
+        a.first = first + done; a.count = n; a.top_k = top_k; a.nq = query_mass ? nq : 0;
+        a.n_words = nw; a.n_sets = ns; a.n_keys = nk; a.ncounts = c->fdesc.ncounts; a.hash_keep = keep;
+        a.query = d_query.p; a.head = d_head.p; a.set_mass = d_set.p; a.top_words = d_twords.p; a.top_mass = d_tmass.p; a.query_mass = d_qmass.p;
+        if (query_mass && nq > STRUCT_QUERY_LDS) HIPCHK(c, hipMemsetAsync(d_qmass.p, 0, (size_t)n * nq * 8, c->stream));   // (those add to the output directly)
+        launch_belief_structures(P, c->D, a, c->stream);
+        HIPCHK(c, hipGetLastError());
+        if (head) HIPCHK(c, hipMemcpyAsync(head + done, d_head.p, (size_t)n * sizeof(fba_structure_head), hipMemcpyDeviceToHost, c->stream));
+        if (set_mass) HIPCHK(c, hipMemcpyAsync(set_mass + (size_t)done * nw * ns, d_set.p, (size_t)n * nw * ns * 8, hipMemcpyDeviceToHost, c->stream));
+        if (top_words) HIPCHK(c, hipMemcpyAsync(top_words + (size_t)done * top_k * nw, d_twords.p, (size_t)n * top_k * nw * 4, hipMemcpyDeviceToHost, c->stream));
+        if (top_mass) HIPCHK(c, hipMemcpyAsync(top_mass + (size_t)done * top_k, d_tmass.p, (size_t)n * top_k * 8, hipMemcpyDeviceToHost, c->stream));
+        if (query_mass) HIPCHK(c, hipMemcpyAsync(query_mass + (size_t)done * nq, d_qmass.p, (size_t)n * nq * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return check_fault(c);
+}
+
 int fba_predict_lens(const fba_ctx* c, int32_t* TL, int32_t* OL)
 {
     if (!c) return FBA_EINVAL;

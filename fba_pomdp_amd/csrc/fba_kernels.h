@@ -130,6 +130,26 @@ struct BeliefProbeArgs {
 // 64 -> 0.75, 32 -> 0.80, 16 -> 0.95)
 constexpr int PROBE_CHUNK = 64;
 void launch_belief_probe(const Problem& P, const DeviceState& D, const BeliefProbeArgs& a, hipStream_t st);
+// fba_belief_structures (fba_structures.hip): the parent-set word lists of slots [first, first + count) reduced into device buffers of the
+// caller's; a null output = not wanted (head is always).  The caller zeroes query_mass where nq > STRUCT_QUERY_LDS
+constexpr int STRUCT_TABLE      = FBA_STRUCT_TABLE;   // entries of a slot's table of distinct structures (open addressing, in LDS)
+constexpr int STRUCT_HIST_CELLS = 1024;   // fp64 cells of the per-word histogram one pass over the slot keeps in LDS: whole words of n_sets cells
+constexpr int STRUCT_QUERY_LDS  = 1024;   // query masses kept in LDS; queries beyond them add to the output directly
+struct BeliefStructuresArgs {
+    int32_t first, count;
+    int32_t top_k, nq;
+    int32_t n_words, n_sets;        // as fba_structure_lens gives them
+    int32_t n_keys;                 // words that identify a structure in the record: 1 for history records (the bits of rec[1]), else n_words
+    int32_t ncounts;                // counts of a particle's table: where the words stand (record_mask_word)
+    uint64_t hash_keep;             // struct_hash's `keep`
+    const uint32_t* query;          // [nq][n_keys] in key form; a first word of 0xffffffff: no record can hold this query
+    fba_structure_head* head;       // [count]
+    double* set_mass;               // [count][n_words][n_sets]
+    uint32_t* top_words;            // [count][top_k][n_words]
+    double* top_mass;               // [count][top_k]
+    double* query_mass;             // [count][nq]
+};
+void launch_belief_structures(const Problem& P, const DeviceState& D, const BeliefStructuresArgs& a, hipStream_t st);
 // belief snapshots (fba_snapshot.hip): the blocks of `count` slots stand in `stage` at per_slot bytes each, laid out as include/fba_hip.h
 // states it (fba_snapshot_head, weights, records); slot first + b owns block b.  All state of the feature is in these arguments
 constexpr int SNAPSHOT_MAX_SLOTS = 32768;            // slots of one launch (a grid row each)

@@ -35,7 +35,7 @@ namespace {
 struct Options {
     std::string mode;
     std::string domain, planner = "po-uct", belief = "rejection_sampling", seed, output_file = "results.txt", structure_prior,
-                                dirichlet = "expected", id, belief_option, probe_file, probe_slots, belief_in, belief_out;
+                                dirichlet = "expected", id, belief_option, probe_file, probe_slots, belief_in, belief_out, structure_out;
     int verbose = 0, runs = 1, horizon = 10, sims = 1000, max_depth = -1, particles = 100, size = 0, height = 0, width = 0,
         episodes = 1, slots = 0, device = 0, resample_amount = 0, first_episode = 0, stop_episode = -1;
     double discount = .95, exploration = 100, threshold = 0;
@@ -84,7 +84,10 @@ void usage()
         "      --stop-episode M           has one line per episode of the span\n"
         "      --belief-in FILE           the filters the runs continue from at episode K: one snapshot block for every run, or one\n"
         "                                 per run, concatenated (what --belief-out of the span that ended at K wrote)\n"
-        "      --belief-out FILE          every run's filter when the span is over (needs runs <= slots)");
+        "      --belief-out FILE          every run's filter when the span is over (needs runs <= slots)\n"
+        "      --structure-out FILE       (fbapomdp) one line per run when the experiment or span is over (needs runs <= slots):\n"
+        "                                 run weight_total distinct overflow stored, then per stored structure of the top 8\n"
+        "                                 its mass and its parent-set words, hexadecimal, joined by commas (fba_belief_structures)");
 }
 
 bool parse(int argc, char** argv, Options& o, std::string& err)
@@ -142,6 +145,7 @@ bool parse(int argc, char** argv, Options& o, std::string& err)
             else if (k == "--stop-episode") o.stop_episode = std::stoi(v);
             else if (k == "--belief-in") o.belief_in = v;
             else if (k == "--belief-out") o.belief_out = v;
+            else if (k == "--structure-out") o.structure_out = v;
             else if (k == "--probe-slots") {
                 const size_t colon = v.find(':');
                 if (colon == std::string::npos || std::stoi(v.substr(0, colon)) < 0 || std::stoi(v.substr(colon + 1)) < 1) throw std::invalid_argument(v);
@@ -308,6 +312,36 @@ void print_trace(fba_ctx* ctx, const Options& o, const fba_config& cfg, int A)
     }
 }
 
+// --structure-out: run r's filter stands in slot r (runs <= slots); the top 8 graphs of each, one line per run
+bool write_structures(fba_ctx* ctx, int runs, const std::string& path)
+{
+    constexpr int top = 8;
+    int32_t nw = 0, ns = 0;
+    if (fba_structure_lens(ctx, &nw, &ns) != FBA_OK) return false;
+    std::vector<fba_structure_head> head((size_t)runs);
+    std::vector<uint32_t> words((size_t)runs * top * (size_t)nw);
+    std::vector<double> mass((size_t)runs * top);
+    if (fba_belief_structures(ctx, 0, runs, top, 0, nullptr, head.data(), nullptr, words.data(), mass.data(), nullptr) != FBA_OK) return false;
+    std::ofstream f(path);
+    f << "# run weight_total distinct overflow stored, then per stored structure: mass words (hexadecimal, word 0 first)\n";
+    char buf[64];
+    for (int r = 0; r < runs; ++r) {
+        const fba_structure_head& h = head[(size_t)r];
+        std::snprintf(buf, sizeof buf, "%.17g", h.weight_total);
+        f << r << ' ' << buf << ' ' << h.distinct << ' ' << h.overflow << ' ' << h.stored;
+        for (int k = 0; k < h.stored; ++k) {
+            std::snprintf(buf, sizeof buf, "%.17g", mass[(size_t)r * top + k]);
+            f << ' ' << buf << ' ';
+            for (int m = 0; m < nw; ++m) {
+                std::snprintf(buf, sizeof buf, "%x", words[((size_t)r * top + k) * (size_t)nw + m]);
+                f << (m ? "," : "") << buf;
+            }
+        }
+        f << '\n';
+    }
+    return (bool)f.flush();
+}
+
 }  // namespace
 
 int main(int argc, char** argv)
@@ -347,6 +381,18 @@ int main(int argc, char** argv)
         const long long want = (long long)cfg.runs * cfg.episodes * cfg.horizon;
         if (fba_probe_enable(ctx, first, count, (int32_t)std::min<long long>(want, 1ll << 26)) != FBA_OK) {
             std::fprintf(stderr, "ERROR: %s\n", fba_last_error(ctx));
+            fba_destroy(ctx);
+            return 1;
+        }
+    }
+    if (!o.structure_out.empty()) {
+        const char* what = nullptr;
+        if (o.mode != "fbapomdp") what = "--structure-out needs a factored Bayes-adaptive experiment (fbapomdp): only its particles carry a graph";
+        else if (fba_belief_structures(ctx, 0, 0, 8, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) != FBA_OK) what = fba_last_error(ctx);
+        else if (cfg.runs > fba_slots(ctx))
+            what = "--structure-out needs runs <= slots: a slot keeps the filter of the last run it executed only (shard the runs over processes instead)";
+        if (what) {
+            std::fprintf(stderr, "ERROR: %s\n", what);
             fba_destroy(ctx);
             return 1;
         }
@@ -420,6 +466,11 @@ int main(int argc, char** argv)
             fba_destroy(ctx);
             return 1;
         }
+    }
+    if (!o.structure_out.empty() && !write_structures(ctx, cfg.runs, o.structure_out)) {
+        std::fprintf(stderr, "ERROR: the structures could not be written to %s: %s\n", o.structure_out.c_str(), fba_last_error(ctx));
+        fba_destroy(ctx);
+        return 1;
     }
     {
         std::ofstream f(o.output_file);

@@ -69,6 +69,23 @@ class BeliefSummary:
         self.edge_prob = edge_prob                        # [slots][n_mask_words][FBA_MAX_FEATURES]
 
 
+class BeliefStructures:
+    """What Engine.belief_structures returns: numpy arrays with one row per slot of the range.  All masses are unnormalised: divide by
+    `weight_total`."""
+
+    def __init__(self, head, set_mass, top_words, top_mass, query_mass):
+        self.head = head                                  # fba_structure_head per slot
+        self.weight_total = head["weight_total"]
+        self.unplaced_mass = head["unplaced_mass"]
+        self.distinct = head["distinct"]
+        self.overflow = head["overflow"]
+        self.stored = head["stored"]
+        self.set_mass = set_mass                          # [slots][n_words][n_sets]
+        self.top_words = top_words                        # [slots][top_k][n_words], uint32
+        self.top_mass = top_mass                          # [slots][top_k]
+        self.query_mass = query_mass                      # [slots][nq]
+
+
 class DeviceArray(collections.namedtuple("DeviceArray", "name elem_bytes elems slot_elems buffers")):
     """One entry of Engine.device_arrays()."""
     __slots__ = ()
@@ -331,6 +348,33 @@ class Engine:
         ptr = lambda a: None if a is None else a.ctypes.data
         self._chk(self.L.fba_belief_summary(self.h, first, count, ptr(head), ptr(sm), ptr(mc), ptr(ep)))
         return BeliefSummary(head, sm, mc, ep)
+
+    def structure_lens(self):
+        """(n_words, n_sets): parent-set words of a particle and parent sets a word can name (fba_structure_lens); (0, 0) where the
+        model has no parent-set words."""
+        nw, ns = C.c_int32(), C.c_int32()
+        self._chk(self.L.fba_structure_lens(self.h, C.byref(nw), C.byref(ns)))
+        return nw.value, ns.value
+
+    def belief_structures(self, first=0, count=None, top_k=8, queries=None):
+        """The posterior over whole model graphs of slots [first, first + count) reduced on the device (fba_belief_structures): per slot
+        the mass of every parent set of every word (`set_mass`), the `top_k` distinct structures of largest mass (`top_words`,
+        `top_mass`, `stored` of them), how many distinct structures the filter holds (`distinct`) and the mass on each of `queries`,
+        uint32[nq][n_words] word lists as belief_get shows them (`query_mass`).  No table is built anywhere.  Outside the parity
+        contract; exact and repeatable in a flat filter."""
+        count = self.slots - first if count is None else count
+        n = max(count, 0)
+        nw, ns = self.structure_lens()
+        q = None if queries is None else np.ascontiguousarray(queries, np.uint32).reshape(-1, max(nw, 1))
+        nq = 0 if q is None else q.shape[0]
+        head = np.zeros(n, N.STRUCTURE_HEAD_DTYPE)
+        sm = np.zeros((n, nw, ns), np.float64)
+        tw = np.zeros((n, max(top_k, 0), nw), np.uint32)
+        tm = np.zeros((n, max(top_k, 0)), np.float64)
+        qm = np.zeros((n, nq), np.float64)
+        self._chk(self.L.fba_belief_structures(self.h, first, count, top_k, nq, None if q is None else q.ctypes.data, head.ctypes.data, sm.ctypes.data,
+                                               tw.ctypes.data, tm.ctypes.data, qm.ctypes.data))
+        return BeliefStructures(head, sm, tw, tm, qm)
 
     def predict_lens(self):
         """(TL, OL): entries of one query's `trans` and `obsp` answer (fba_predict_lens)."""

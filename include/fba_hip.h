@@ -397,6 +397,52 @@ int fba_belief_forecast(fba_ctx* ctx, int32_t first, int32_t count,
                         double* next_mass,       /* [count][S] */
                         double* post_mass,       /* [count][S] */
                         double* evidence);       /* [count]    */
+/* The posterior over whole model graphs on the device: what edge_prob of fba_belief_summary, a marginal per (word, candidate), cannot
+ * say.  Everything is defined through what fba_belief_get returns: the STRUCTURE of particle i is the list of n_words = n_mask_words
+ * uint32 bit patterns at positions n_counts + m of its blob, w_i its weight (1.0 in a flat filter).  n_sets = 1 << the largest
+ * n_candidates over the nodes with mask_word >= 0 (at most 256); fba_structure_lens gives (0, 0) where the model has no parent-set words.
+ * All masses are UNNORMALISED: the caller divides by weight_total.
+ *   head      [count]
+ *   set_mass  [count][n_words][n_sets]  sum of w_i over the particles whose word m equals v; 0.0 for a v that never occurs (a value
+ *                                       >= n_sets cannot occur in a legal record and is counted nowhere)
+ *   top_words [count][top_k][n_words]   the `stored` distinct structures of largest mass, by mass descending and among equal masses by
+ *   top_mass  [count][top_k]            word list ascending (word 0 most significant); rows behind `stored` are zero
+ *   query_mass[count][nq]               sum of w_i over the particles whose whole word list equals query[q]
+ * Distinct structures are found in a per-slot table of FBA_STRUCT_TABLE entries.  Up to that many distinct structures everything is
+ * exact; beyond it overflow = 1, `distinct` counts the structures that found a place, the top list is taken among those, and
+ * unplaced_mass is the weight that found none.  set_mass and query_mass never depend on the table.  A particle of weight 0.0 still
+ * counts as a structure.
+ * Any output pointer may be NULL (all of them: FBA_OK, nothing is done).  top_k is 0..FBA_STRUCT_MAX_TOP (0: top_words and top_mass are
+ * ignored), nq is 0..65536 (query may be NULL iff nq is 0).  Serves what fba_belief_summary serves: the main filter of every belief but
+ * the nested one, in every record format, a lazily reset rejection filter included (words do not depend on states).  FBA_EINVAL for the
+ * nested belief, a context whose model has no parent-set words (a plain POMDP, a tabular model, a factored model of a fixed graph), a
+ * slot range outside the context, top_k or nq out of range, query == NULL with nq > 0, and a query word that is illegal for its node
+ * by the rule of fba_belief_import (word m < 1 << n_candidates of every node it serves; the message names the query and the word).
+ * Read-only: no buffer, flag, counter or Philox position of the context changes, so the call may stand between any two others, after
+ * fba_run_*, and on inactive slots.
+ * The call is OUTSIDE the parity contract: the order of its fp64 additions is the engine's choice and need not repeat bit for bit from
+ * call to call; nothing of it enters the trace or belief_hash.  Every mass is within 8 * particles * 2^-53 relative of the exact sum,
+ * and exactly 0.0 where every term is.  In a flat filter every mass is an integer below 2^53, hence exact, and the whole answer --
+ * the order of the top list included -- repeats bit for bit. */
+#define FBA_STRUCT_MAX_TOP 64
+#define FBA_STRUCT_TABLE 2048
+typedef struct fba_structure_head {
+    double  weight_total;   /* sum of w_i (N exactly in a flat filter), as in fba_belief_summary            */
+    double  unplaced_mass;  /* weight of the particles whose structure found no place in the table          */
+    int32_t distinct;       /* distinct structures found; exact when overflow == 0, a lower bound otherwise */
+    int32_t overflow;       /* 1: more than FBA_STRUCT_TABLE distinct structures in this slot               */
+    int32_t stored;         /* entries written to top_words / top_mass for this slot: min(top_k, distinct)  */
+    int32_t reserved;
+} fba_structure_head;
+int fba_structure_lens(const fba_ctx* ctx, int32_t* n_words, int32_t* n_sets);
+int fba_belief_structures(fba_ctx* ctx, int32_t first, int32_t count,
+                          int32_t top_k, int32_t nq,
+                          const uint32_t* query,    /* [nq][n_words], may be NULL iff nq == 0 */
+                          fba_structure_head* head, /* [count]                                */
+                          double*   set_mass,       /* [count][n_words][n_sets]               */
+                          uint32_t* top_words,      /* [count][top_k][n_words]                */
+                          double*   top_mass,       /* [count][top_k]                         */
+                          double*   query_mass);    /* [count][nq]                            */
 /* per-slot record of the last select_action / belief_update (root statistics, rejection count,
  * belief checksum) */
 int fba_last_step_info(fba_ctx* ctx, fba_trace_rec* recs /* [slots] */);
