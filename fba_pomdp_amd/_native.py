@@ -12,7 +12,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB_PATH = os.environ.get("FBA_LIB") or os.path.join(HERE, "libfba_hip.so")   # (FBA_LIB: an instrumented build of the same sources, scripts/search_regions.py)
-SOURCES = [os.path.join(HERE, "csrc", f) for f in ("fba_search.hip", "fba_kernels.hip", "fba_summary.hip", "fba_predict.hip", "fba_forecast.hip", "fba_probe.hip", "fba_structures.hip", "fba_snapshot.hip", "fba_restore.hip", "fba_engine.hip")]
+SOURCES = [os.path.join(HERE, "csrc", f) for f in ("fba_search.hip", "fba_kernels.hip", "fba_summary.hip", "fba_predict.hip", "fba_forecast.hip", "fba_probe.hip", "fba_structures.hip", "fba_snapshot.hip", "fba_convert.hip", "fba_restore.hip", "fba_engine.hip")]
 HEADERS = [os.path.join(HERE, "csrc", f) for f in ("fba_device.h", "fba_state.h", "fba_kernels.h", "fba_launch_plan.h", "fba_kernels_common.h", "fba_belief_factors.h", "fba_snapshot_format.h", "fba_structures.h", "fba_search_hist2.inc")] + [
     os.path.join(ROOT, "include", "fba_hip.h")]
 OBJ_DIR = os.path.join(HERE, "build")   # per-source objects (git-ignored): a change to one translation unit recompiles that one
@@ -160,6 +160,7 @@ EXPORTS = [
     "fba_get_kernel_times", "fba_reset_kernel_times", "fba_trace_count", "fba_get_trace", "fba_get_trace_hist",
     "fba_probe_enable", "fba_probe_count", "fba_get_probe",
     "fba_belief_snapshot_bytes", "fba_belief_export", "fba_belief_import", "fba_belief_replicate", "fba_run_bapomdp_span",
+    "fba_snapshot_block_bytes", "fba_belief_convert",
     "fba_selftest_ucb", "fba_stat_add", "fba_stat_var", "fba_stat_stder",
 ]
 
@@ -289,6 +290,14 @@ def load():
         L.fba_belief_replicate.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]     # src, first, count
     if not os.environ.get("FBA_LIB") or hasattr(L, "fba_run_bapomdp_span"):
         L.fba_run_bapomdp_span.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int64, P(Stat)]   # first, stop, blocks, nblocks, bytes, stats
+    if not os.environ.get("FBA_LIB") or hasattr(L, "fba_belief_convert"):
+        L.fba_snapshot_block_bytes.restype = C.c_int64
+        L.fba_snapshot_block_bytes.argtypes = [vp]
+        L.fba_belief_convert.argtypes = [vp, C.c_int32, vp, C.c_int64, C.c_uint64, C.c_uint32, vp, C.c_int64]   # count, src, src_bytes, seed, first_run, dst, dst_cap
+        L.fba_debug_convert_kernel_ms.restype = C.c_double   # diagnostic, not in include/fba_hip.h: the kernels of the last convert, by HIP events
+        L.fba_debug_convert_kernel_ms.argtypes = []
+        L.fba_debug_convert_validate_ms.restype = C.c_double   # ... and the validation of the source blocks among them
+        L.fba_debug_convert_validate_ms.argtypes = []
     L.fba_selftest_ucb.argtypes = [vp, vp, vp, C.c_int32, C.c_double, vp]
     L.fba_stat_add.argtypes = [P(Stat), C.c_double]
     L.fba_stat_var.restype = C.c_double

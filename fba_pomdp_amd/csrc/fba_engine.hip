@@ -3376,6 +3376,148 @@ int fba_belief_replicate(fba_ctx* c, int32_t src, int32_t first, int32_t count)
     return FBA_OK;
 }
 
+// what the kernels of the last fba_belief_convert of this thread took (HIP events around the launches of every chunk); kept outside the
+// context, which the call leaves untouched.  fba_debug_convert_kernel_ms: diagnostic, not in include/fba_hip.h (scripts/bench_belief_convert.py)
+// fba_debug_convert_validate_ms: the part of it that judged the source blocks (snapshot_validate_kernel)
+static thread_local double g_convert_kernel_ms = 0.0, g_convert_validate_ms = 0.0;
+extern "C" double fba_debug_convert_kernel_ms(void) { return g_convert_kernel_ms; }
+extern "C" double fba_debug_convert_validate_ms(void) { return g_convert_validate_ms; }
+namespace {
+struct ConvertEvents {
+    hipEvent_t a = nullptr, m = nullptr, b = nullptr;
+    ~ConvertEvents() { if (a) (void)hipEventDestroy(a); if (m) (void)hipEventDestroy(m); if (b) (void)hipEventDestroy(b); }
+};
+}  // namespace
+
+int64_t fba_snapshot_block_bytes(const fba_snapshot_head* head)
+{
+    if (!head) return 0;
+    fba_snapshot_head h;
+    std::memcpy(&h, head, sizeof h);   // (a header inside a caller's byte buffer may stand anywhere)
+    return fba_snapshot::block_bytes(h.weighted, h.particles, h.particle_bytes);
+}
+
+int fba_belief_convert(fba_ctx* c, int32_t count, const void* src, int64_t src_bytes, uint64_t seed, uint32_t first_run, void* dst, int64_t dst_cap)
+{
+    static const char* const call = "fba_belief_convert";
+    if (!c) return FBA_EINVAL;
+    if (const char* extra = snapshot_extra_state(c))
+        return fail(c, FBA_EINVAL, "%s: a snapshot holds the main filter of a slot, and %s", call, extra);
+    if (count < 1 || !src || !dst)
+        return fail(c, FBA_EINVAL, "%s: count %d, src %s, dst %s: one block at least, from a buffer into a buffer", call, count, src ? "set" : "null", dst ? "set" : "null");
+    const Problem& P = c->P;
+    const uint8_t* in = static_cast<const uint8_t*>(src);
+    uint8_t* out      = static_cast<uint8_t*>(dst);
+    const fba_snapshot::Accepts acc = snapshot_accepts(c);
+    const int weighted = snapshot_weighted(c) ? 1 : 0;
+    const int64_t dper = fba_snapshot::block_bytes(weighted, P.N, (int64_t)P.Cs * 4);
+    // ---- host pass: the first header says what the blocks of the call are, then every header against it and the context ----
+    if (src_bytes < (int64_t)sizeof(fba_snapshot_head))
+        return fail(c, FBA_EINVAL, "%s: bytes %lld: not even one header of %d", call, (long long)src_bytes, (int)sizeof(fba_snapshot_head));
+    fba_snapshot_head h0;
+    std::memcpy(&h0, in, sizeof h0);
+    char msg[256];
+    {
+        const int rc = fba_snapshot::check_convert_head(in, std::max<int64_t>(src_bytes, 0), acc, h0.particles, h0.particle_bytes, msg, sizeof msg);
+        // (a first block cut short: the size of the whole buffer is the better message, below)
+        if (rc && std::strncmp(msg, "bytes ", 6) != 0) return fail(c, FBA_EINVAL, rc == -2 ? "%s: block 0 %s" : "%s: block 0: %s", call, msg);
+    }
+    const int32_t n_src = h0.particles, src_cs = h0.particle_bytes / 4;
+    const int64_t sper = fba_snapshot::block_bytes(weighted, n_src, h0.particle_bytes);
+    if (src_bytes != (int64_t)count * sper)
+        return fail(c, FBA_EINVAL, "%s: bytes %lld / %lld (%d blocks of %lld)", call, (long long)src_bytes, (long long)count * sper, count, (long long)sper);
+    if (dst_cap < (int64_t)count * dper)
+        return fail(c, FBA_EINVAL, "%s: %d blocks of %lld bytes need %lld, the buffer has %lld", call, count, (long long)dper, (long long)count * dper, (long long)dst_cap);
+    if (in < out + dst_cap && out < in + src_bytes) return fail(c, FBA_EINVAL, "%s: src and dst overlap", call);
+    std::vector<fba_snapshot_head> heads((size_t)count);
+    std::vector<int64_t> strides((size_t)count);
+    for (int b = 0; b < count; ++b) {
+        const int rc = fba_snapshot::check_convert_head(in + (size_t)b * (size_t)sper, sper, acc, n_src, h0.particle_bytes, msg, sizeof msg, &strides[(size_t)b]);
+        if (rc) return fail(c, FBA_EINVAL, rc == -2 ? "%s: block %d %s" : "%s: block %d: %s", call, b, msg);
+        std::memcpy(&heads[(size_t)b], in + (size_t)b * (size_t)sper, sizeof(fba_snapshot_head));
+    }
+    const int mode = n_src == P.N ? CONVERT_SAME : (weighted ? CONVERT_WEIGHTED : CONVERT_FLAT);
+    if (mode == CONVERT_WEIGHTED && n_src > 256 * IS_MAX_CHUNKS)
+        return fail(c, FBA_EINVAL, "%s: %d weighted particles in a block / %d a weighted filter of this engine holds", call, n_src, 256 * IS_MAX_CHUNKS);
+    // ---- the kernels' arguments: the validation sees a Problem shaped like the source ----
+    BeliefSnapshotArgs va;
+    ScratchBuf<uint32_t> d_limit;
+    int rc;
+    if ((rc = snapshot_args(c, va, d_limit))) return rc;
+    Problem S = P;
+    S.N = n_src; S.Cs = src_cs;
+    if (P.hist) S.hist_cap = src_cs - 2;
+    const int64_t spad = snapshot_store_pad(weighted, n_src), spitch = snapshot_store_pitch(sper, weighted, n_src);
+    const int64_t dpad = snapshot_store_pad(weighted, P.N), dpitch = snapshot_store_pitch(dper, weighted, P.N);
+    const int chunk = snapshot_chunk(spitch + dpitch, count);   // both sides of a chunk within the staging bound, one block of each at least
+    ScratchBuf<uint8_t> d_src, d_dst;
+    ScratchBuf<double> d_incl;
+    ScratchBuf<unsigned long long> d_check;   // [chunk] source checksums, [chunk] destination checksums, then the error word
+    const size_t want[3] = {(size_t)chunk * (size_t)spitch, (size_t)chunk * (size_t)dpitch, mode == CONVERT_WEIGHTED ? (size_t)chunk * (size_t)n_src * 8 : 0};
+    if (d_src.alloc(want[0]) != hipSuccess || d_dst.alloc(want[1]) != hipSuccess || (want[2] && d_incl.alloc(want[2] / 8) != hipSuccess)) {
+        (void)hipGetLastError();
+        return fail(c, FBA_EHIP, "%s: no device memory for staging: %lld bytes (%d blocks: %lld of the source, %lld of the destination, %lld of prefix sums)", call,
+                    (long long)(want[0] + want[1] + want[2]), chunk, (long long)want[0], (long long)want[1], (long long)want[2]);
+    }
+    HIPCHK(c, d_check.alloc((size_t)2 * chunk + 1));
+    std::vector<unsigned long long> h_check((size_t)2 * chunk + 1);
+    ConvertEvents ev;
+    HIPCHK(c, hipEventCreate(&ev.a));
+    HIPCHK(c, hipEventCreate(&ev.m));
+    HIPCHK(c, hipEventCreate(&ev.b));
+    g_convert_kernel_ms = g_convert_validate_ms = 0.0;
+    static const char* const what_names[] = {"", "a weight that is negative or not finite", "a state outside the domain", "an illegal parent-set word",
+                                             "a history entry outside the domain's tables", "a count that is negative or not finite", "",
+                                             "weights whose total is zero or not finite: nothing to sample from"};
+    BeliefConvertArgs a{};
+    a.first_run = first_run; a.src_pitch = spitch; a.dst_pitch = dpitch; a.n_src = n_src; a.src_cs = src_cs; a.weighted = weighted; a.mode = mode;
+    a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
+    for (int done = 0; done < count; done += chunk) {
+        const int n = std::min(chunk, count - done);
+        va.first = 0; va.count = n; va.stage = d_src.p + (size_t)spad; va.per_slot = spitch; va.check = d_check.p; va.bad = d_check.p + 2 * chunk;
+        a.count = n; a.first_run = first_run + (uint32_t)done; a.src = va.stage; a.dst = d_dst.p + (size_t)dpad; a.incl = d_incl.p;
+        a.check = d_check.p + chunk; a.bad = va.bad;
+        HIPCHK(c, hipMemcpy2DAsync(va.stage, (size_t)spitch, in + (size_t)done * (size_t)sper, (size_t)sper, (size_t)sper, (size_t)n, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemsetAsync(d_check.p, 0, (size_t)2 * chunk * 8, c->stream));
+        HIPCHK(c, hipMemsetAsync(va.bad, 0xff, 8, c->stream));
+        HIPCHK(c, hipEventRecord(ev.a, c->stream));
+        launch_snapshot_validate(S, c->D, va, c->stream);
+        HIPCHK(c, hipEventRecord(ev.m, c->stream));
+        if (mode == CONVERT_WEIGHTED) launch_convert_scan(a, c->stream);
+        launch_snapshot_convert(P, a, c->stream);   // (in bounds whatever the payload holds: the headers are the host's, a source index is below n_src by construction)
+        HIPCHK(c, hipEventRecord(ev.b, c->stream));
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(h_check.data(), d_check.p, ((size_t)2 * chunk + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        {
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, ev.a, ev.b) == hipSuccess) g_convert_kernel_ms += (double)ms;
+            if (hipEventElapsedTime(&ms, ev.a, ev.m) == hipSuccess) g_convert_validate_ms += (double)ms;
+        }
+        for (int b = 0; b < n; ++b)
+            if (h_check[(size_t)b] != heads[(size_t)(done + b)].checksum)
+                return fail(c, FBA_EINVAL, "%s: block %d: checksum %016llx in the header, %016llx over the payload", call, done + b,
+                            (unsigned long long)heads[(size_t)(done + b)].checksum, h_check[(size_t)b]);
+        const unsigned long long bad = h_check[(size_t)2 * chunk];
+        if (bad != ~0ull) {
+            const int b = done + (int)(bad >> 40), what = (int)(bad & 0xffu);
+            if (what == SNAP_BAD_TOTAL) return fail(c, FBA_EINVAL, "%s: block %d: %s", call, b, what_names[what]);
+            return fail(c, FBA_EINVAL, "%s: block %d, particle %lld: %s", call, b, (long long)((bad >> 8) & 0xffffffffull),
+                        what >= 1 && what <= 5 ? what_names[what] : "an invalid record");
+        }
+        HIPCHK(c, hipMemcpy2D(out + (size_t)done * (size_t)dper, (size_t)dper, a.dst, (size_t)dpitch, (size_t)dper, (size_t)n, hipMemcpyDeviceToHost));
+        for (int b = 0; b < n; ++b) {
+            const fba_snapshot_head& s = heads[(size_t)(done + b)];
+            fba_snapshot_head h = acc.want;
+            h.hist_cnt = s.hist_cnt; h.updates = s.updates;
+            h.stride   = (uint32_t)strides[(size_t)(done + b)];
+            h.checksum = h_check[(size_t)chunk + (size_t)b];
+            std::memcpy(out + (size_t)(done + b) * (size_t)dper, &h, sizeof h);
+        }
+    }
+    return FBA_OK;
+}
+
 int fba_last_step_info(fba_ctx* c, fba_trace_rec* recs)
 {
     if (!c || !recs) return FBA_EINVAL;

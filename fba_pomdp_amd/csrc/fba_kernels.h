@@ -181,6 +181,26 @@ void launch_restore(const Problem& P, const DeviceState& D, hipStream_t st);
 // inc_words words of a record exceeds head.updates.  Over the `count` blocks validated last (a.stage, a.per_slot, a.bad as for
 // launch_snapshot_validate: the smallest block << 40 | particle << 8 | SNAP_BAD_INCREMENT met)
 void launch_span_increments(const Problem& P, const BeliefSnapshotArgs& a, int inc_words, hipStream_t st);
+// fba_belief_convert (fba_convert.hip): `count` staged source blocks (n_src particles, records of src_cs words) refitted into `count` staged
+// destination blocks of the Problem the launch is given; both sides stand as a span's store does, block b at b * pitch behind the pad, so
+// that record parts start at multiples of 16 bytes.  The headers of the destination are the host's.  All state of the feature is here
+enum { CONVERT_SAME = 0, CONVERT_FLAT = 1, CONVERT_WEIGHTED = 2 };   // the source of output particle j: j, uniform_int(n_src), the pick on incl
+constexpr int SNAP_BAD_TOTAL = 7;   // (beside SNAP_BAD_*: a weight total that is zero or not finite; particle 0)
+struct BeliefConvertArgs {
+    int32_t count;
+    uint32_t first_run;             // block b draws from the streams of run first_run + b
+    const uint8_t* src;             // [count] blocks at src_pitch, validated headers
+    uint8_t* dst;                   // [count] blocks at dst_pitch
+    int64_t src_pitch, dst_pitch;
+    int32_t n_src, src_cs;          // particles of a source block, words a source record has room for
+    int32_t weighted, mode;         // the blocks hold weights; CONVERT_*
+    uint32_t seed_lo, seed_hi;
+    double* incl;                   // CONVERT_WEIGHTED: [count][n_src] inclusive prefix sums of the source weights (launch_convert_scan writes them)
+    unsigned long long* check;      // [count] the destination payloads' checksums (the caller zeroes them)
+    unsigned long long* bad;        // [1] as BeliefSnapshotArgs::bad: block << 40 | SNAP_BAD_TOTAL
+};
+void launch_convert_scan(const BeliefConvertArgs& a, hipStream_t st);
+void launch_snapshot_convert(const Problem& P, const BeliefConvertArgs& a, hipStream_t st);
 void launch_uniform_scan(int n, double* w_tmp, double* out, double* total, double* ctot, hipStream_t st);
 
 }  // namespace fba

@@ -1652,75 +1652,7 @@ __global__ void __launch_bounds__(64) mh_kernel(Problem P, DeviceState D, int sc
     D.lik[e]    = 0.0;
 }
 
-// ---------------------------------------------------------------------------------------------
-// Device-order prefix sums (DESIGN.md "device-order sums"; oracle/orc.c dev_scan is the CPU twin):
-// each lane sums 4 consecutive elements sequentially, a 64-lane Kogge-Stone scan combines the
-// lane sums of one 256-element chunk, chunks are chained sequentially.
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_inclusive_scan(double v, int lane)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const double t = __shfl_up(v, d, 64);
-        if (lane >= d) v = v + t;
-    }
-    return v;
-}
-
-// in: n doubles; out_incl may be null.  s_carry: LDS, at least n/256 + 2 doubles.  Returns the
-// total to every thread.  All threads of the block must call.
-__device__ __forceinline__ double block_device_scan(const double* in, int n, double* out_incl, double* s_carry)  // (out_incl may be `in`)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
-    const int nchunks = (n + 255) >> 8;
-    for (int c = wave; c < nchunks; c += nwaves) {
-        const int i0 = c * 256 + lane * 4;
-        double s = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const double x = (i0 + k < n) ? in[i0 + k] : 0.0;
-            s = (k == 0) ? x : s + x;
-        }
-        const double incl = wave_inclusive_scan(s, lane);
-        if (lane == 63) s_carry[c + 1] = incl;  // chunk total
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double carry = 0;
-        s_carry[0]   = 0;
-        for (int c = 0; c < nchunks; ++c) {
-            const double t = s_carry[c + 1];
-            carry          = carry + t;
-            s_carry[c + 1] = carry;  // carry into chunk c + 1 (the last one is the total)
-        }
-    }
-    __syncthreads();
-    const double total = s_carry[nchunks];
-    if (out_incl) {
-        for (int c = wave; c < nchunks; c += nwaves) {
-            const int i0 = c * 256 + lane * 4;
-            double x[4], s = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                x[k] = (i0 + k < n) ? in[i0 + k] : 0.0;
-                s    = (k == 0) ? x[k] : s + x[k];
-            }
-            const double incl = wave_inclusive_scan(s, lane);
-            double excl       = __shfl_up(incl, 1, 64);
-            if (lane == 0) excl = 0.0;
-            double run = s_carry[c] + excl;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (i0 + k < n) {
-                    run += x[k];
-                    out_incl[i0 + k] = run;
-                }
-            }
-        }
-    }
-    __syncthreads();
-    return total;
-}
+// (device-order prefix sums -- wave_inclusive_scan, block_device_scan: fba_kernels_common.h)
 
 // uniform_scan_kernel: prefix sums of N weights 1/N, computed once per ctx.
 __global__ void __launch_bounds__(IS_BLOCK) uniform_scan_kernel(int n, double* w_tmp, double* out, double* total)

@@ -1,6 +1,7 @@
 // fba_kernels_common.h -- device helpers shared by the search kernels (fba_search.hip), the belief / episode kernels
 // (fba_kernels.hip) and the read-only calls (fba_summary.hip, fba_predict.hip): stream addressing, particle record accessors,
-// the slot locator of the readers, filter sampling, tree node records, UCB.
+// the slot locator of the readers, filter sampling, tree node records, UCB, the device-order prefix sums (the belief kernels and
+// fba_convert.hip) and the checksum of a snapshot block (fba_snapshot.hip, fba_convert.hip).
 #pragma once
 
 #include <float.h>
@@ -388,6 +389,101 @@ __device__ __forceinline__ int ucb_select(const Problem& P, const DeviceState& D
     return ucb_pick<AMAX>(P, g, D.log1p_tab, visits, cn, cq, explore);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Device-order prefix sums (DESIGN.md "device-order sums"; oracle/orc.c dev_scan is the CPU twin):
+// each lane sums 4 consecutive elements sequentially, a 64-lane Kogge-Stone scan combines the
+// lane sums of one 256-element chunk, chunks are chained sequentially.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ double wave_inclusive_scan(double v, int lane)
+{
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const double t = __shfl_up(v, d, 64);
+        if (lane >= d) v = v + t;
+    }
+    return v;
+}
+
+// in: n doubles; out_incl may be null.  s_carry: LDS, at least n/256 + 2 doubles.  Returns the
+// total to every thread.  All threads of the block must call.
+__device__ __forceinline__ double block_device_scan(const double* in, int n, double* out_incl, double* s_carry)  // (out_incl may be `in`)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
+    const int nchunks = (n + 255) >> 8;
+    for (int c = wave; c < nchunks; c += nwaves) {
+        const int i0 = c * 256 + lane * 4;
+        double s = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const double x = (i0 + k < n) ? in[i0 + k] : 0.0;
+            s = (k == 0) ? x : s + x;
+        }
+        const double incl = wave_inclusive_scan(s, lane);
+        if (lane == 63) s_carry[c + 1] = incl;  // chunk total
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double carry = 0;
+        s_carry[0]   = 0;
+        for (int c = 0; c < nchunks; ++c) {
+            const double t = s_carry[c + 1];
+            carry          = carry + t;
+            s_carry[c + 1] = carry;  // carry into chunk c + 1 (the last one is the total)
+        }
+    }
+    __syncthreads();
+    const double total = s_carry[nchunks];
+    if (out_incl) {
+        for (int c = wave; c < nchunks; c += nwaves) {
+            const int i0 = c * 256 + lane * 4;
+            double x[4], s = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                x[k] = (i0 + k < n) ? in[i0 + k] : 0.0;
+                s    = (k == 0) ? x[k] : s + x[k];
+            }
+            const double incl = wave_inclusive_scan(s, lane);
+            double excl       = __shfl_up(incl, 1, 64);
+            if (lane == 0) excl = 0.0;
+            double run = s_carry[c] + excl;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (i0 + k < n) {
+                    run += x[k];
+                    out_incl[i0 + k] = run;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    return total;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The checksum of a snapshot block (include/fba_hip.h), as the kernels of fba_snapshot.hip and fba_convert.hip accumulate it
+// ---------------------------------------------------------------------------------------------
+// sum of v over the workgroup (256 threads), modulo 2^64, added to *dst by one thread
+__device__ __forceinline__ void block_check_add(unsigned long long v, unsigned long long* dst)
+{
+    __shared__ unsigned long long s_part[4];
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        v = (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
+        if (v) atomicAdd(dst, v);
+    }
+}
+__device__ __forceinline__ unsigned long long check_term(uint32_t v, size_t w) { return (unsigned long long)v * (((unsigned long long)w + 1ull) * FBA_SNAPSHOT_CHECK_MUL); }
+
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+
+// workgroups per slot for `units` units of work each: enough to fill the chip at few slots, no more than 8 192 in all at many
+static inline int blocks_per_slot(size_t units, size_t per_block, int count)
+{
+    const size_t want = (units + per_block - 1) / per_block, cap = (size_t)ceil_div(8192, count > 1 ? count : 1);   // (cap >= 1)
+    const size_t n = want < cap ? want : cap;
+    return (int)(n > 1 ? n : 1);
+}
 
 }  // namespace fba

@@ -25,20 +25,6 @@ namespace {
 constexpr int SNAP_HEAD_WORDS = (int)(sizeof(fba_snapshot_head) / 4);
 static_assert(sizeof(fba_snapshot_head) == 64, "a snapshot block starts with 64 bytes of header");
 
-// sum of v over the workgroup (256 threads), modulo 2^64, added to *dst by one thread
-__device__ __forceinline__ void block_check_add(unsigned long long v, unsigned long long* dst)
-{
-    __shared__ unsigned long long s_part[4];
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        v = (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
-        if (v) atomicAdd(dst, v);
-    }
-}
-__device__ __forceinline__ unsigned long long check_term(uint32_t v, size_t w) { return (unsigned long long)v * (((unsigned long long)w + 1ull) * FBA_SNAPSHOT_CHECK_MUL); }
-
 // the live buffers of slot e (what slot_recs finds for a reader, writable)
 __device__ __forceinline__ float* live_records(const Problem& P, const DeviceState& D, int e) { return D.p_rec + rec_base(P, D, e, D.bufsel[e]) * (size_t)P.Cs; }
 __device__ __forceinline__ double* live_weights(const Problem& P, const DeviceState& D, int e) { return D.p_weight + pbase(P, e, D.bufsel[e]); }
@@ -192,12 +178,6 @@ __global__ void __launch_bounds__(256) snapshot_replicate_kernel(Problem P, Devi
     }
 }
 
-// workgroups per slot for `words` units of work each: enough to fill the chip at few slots, no more than 8 192 in all at many
-static int blocks_per_slot(size_t units, size_t per_block, int count)
-{
-    const size_t want = (units + per_block - 1) / per_block, cap = (size_t)std::max(1, ceil_div(8192, std::max(count, 1)));
-    return (int)std::max<size_t>(1, std::min(want, cap));
-}
 static size_t payload_words(const Problem& P, const BeliefSnapshotArgs& a) { return (a.weighted ? (size_t)2 * P.N : 0) + (size_t)P.N * (size_t)P.Cs; }
 
 void launch_snapshot_pack(const Problem& P, const DeviceState& D, const BeliefSnapshotArgs& a, hipStream_t st)

@@ -40,7 +40,8 @@ struct Options {
         episodes = 1, slots = 0, device = 0, resample_amount = 0, first_episode = 0, stop_episode = -1;
     double discount = .95, exploration = 100, threshold = 0;
     float noise = 0, counts_total = 10000;
-    bool help = false;
+    bool help = false, belief_fit = false;
+    unsigned long long belief_fit_seed = 0;
 };
 
 void usage()
@@ -84,6 +85,9 @@ void usage()
         "      --stop-episode M           has one line per episode of the span\n"
         "      --belief-in FILE           the filters the runs continue from at episode K: one snapshot block for every run, or one\n"
         "                                 per run, concatenated (what --belief-out of the span that ended at K wrote)\n"
+        "      --belief-fit SEED          with --belief-in: the file's blocks may be of another particle count or, for history records, of\n"
+        "                                 another episodes * horizon; they are refitted to this configuration first (fba_belief_convert:\n"
+        "                                 block b draws from the streams of run b under SEED where the particle count changes)\n"
         "      --belief-out FILE          every run's filter when the span is over (needs runs <= slots)\n"
         "      --structure-out FILE       (fbapomdp) one line per run when the experiment or span is over (needs runs <= slots):\n"
         "                                 run weight_total distinct overflow stored, then per stored structure of the top 8\n"
@@ -145,6 +149,7 @@ bool parse(int argc, char** argv, Options& o, std::string& err)
             else if (k == "--stop-episode") o.stop_episode = std::stoi(v);
             else if (k == "--belief-in") o.belief_in = v;
             else if (k == "--belief-out") o.belief_out = v;
+            else if (k == "--belief-fit") { o.belief_fit = true; o.belief_fit_seed = std::stoull(v); }
             else if (k == "--structure-out") o.structure_out = v;
             else if (k == "--probe-slots") {
                 const size_t colon = v.find(':');
@@ -411,7 +416,21 @@ int main(int argc, char** argv)
         if (!what && !o.belief_in.empty()) {
             std::ifstream in(o.belief_in, std::ios::binary);
             if (in) blocks.assign(std::istreambuf_iterator<char>(in), std::istreambuf_iterator<char>());
-            if (!in || blocks.empty() || blocks.size() % (size_t)per_block) {
+            if (in && !blocks.empty() && o.belief_fit) {   // blocks of another particle count or record room: refitted, then taken as any
+                const int64_t src_block = blocks.size() >= sizeof(fba_snapshot_head) ? fba_snapshot_block_bytes(reinterpret_cast<const fba_snapshot_head*>(blocks.data())) : 0;
+                if (src_block < (int64_t)sizeof(fba_snapshot_head) || blocks.size() % (size_t)src_block) {
+                    err = "--belief-in " + o.belief_in + ": not a file of snapshot blocks (" + std::to_string(blocks.size()) + " bytes, " + std::to_string(src_block) +
+                          " per block by its first header)";
+                    what = err.c_str();
+                } else {
+                    const size_t n = blocks.size() / (size_t)src_block;
+                    std::vector<char> fitted(n * (size_t)per_block);
+                    if (fba_belief_convert(ctx, (int32_t)n, blocks.data(), (int64_t)blocks.size(), o.belief_fit_seed, 0, fitted.data(), (int64_t)fitted.size()) != FBA_OK) {
+                        err = "--belief-in " + o.belief_in + " --belief-fit: " + fba_last_error(ctx);
+                        what = err.c_str();
+                    } else blocks.swap(fitted);
+                }
+            } else if (!in || blocks.empty() || blocks.size() % (size_t)per_block) {
                 err = "--belief-in " + o.belief_in + ": not a file of snapshot blocks of this configuration (" + std::to_string(blocks.size()) + " bytes, " +
                       std::to_string(per_block) + " per block)";
                 what = err.c_str();

@@ -26,6 +26,16 @@ def _enum(value, table, what):
     return int(value)
 
 
+def snapshot_block_bytes(head_bytes):
+    """Bytes of the snapshot block a 64-byte header starts (fba_snapshot_block_bytes): 64 + [particles * 8] + particles * particle_bytes.
+    Host arithmetic, no context: how a file of blocks of another context is cut into blocks before Engine.belief_convert."""
+    h = np.ascontiguousarray(np.frombuffer(head_bytes, np.uint8) if isinstance(head_bytes, (bytes, bytearray, memoryview)) else head_bytes, np.uint8).reshape(-1)
+    if h.size < N.SNAPSHOT_HEAD_DTYPE.itemsize:
+        raise ValueError(f"a snapshot header has {N.SNAPSHOT_HEAD_DTYPE.itemsize} bytes, not {h.size}")
+    h = np.ascontiguousarray(h[:N.SNAPSHOT_HEAD_DTYPE.itemsize])
+    return int(N.load().fba_snapshot_block_bytes(h.ctypes.data))
+
+
 class BeliefPrediction:
     """What Engine.belief_predict returns: numpy arrays [slot, query, ...] (None where not asked for) and, for a factored model, where
     each feature's segment starts: feature f of `trans` is trans[..., trans_offsets[f]:trans_offsets[f + 1]], likewise `obsp`."""
@@ -485,6 +495,18 @@ class Engine:
     def belief_replicate(self, src, first, count):
         """The filter of slot `src` into every slot of [first, first + count) on the device (fba_belief_replicate); `src` is skipped."""
         self._chk(self.L.fba_belief_replicate(self.h, src, first, count))
+
+    def belief_convert(self, blocks, seed=0, first_run=0):
+        """Blocks of a context that differs from this one in its particle count or, for history records, in the room of a record
+        (episodes * horizon), refitted to this context (fba_belief_convert): the bytes of as many blocks of belief_snapshot_bytes, which
+        belief_import and run_bapomdp(beliefs=...) then take.  Block b draws from the Philox streams of run first_run + b under `seed` where
+        the particle count changes.  Nothing of the context changes."""
+        b = np.ascontiguousarray(np.frombuffer(blocks, np.uint8) if isinstance(blocks, (bytes, bytearray, memoryview)) else blocks, np.uint8).reshape(-1)
+        per = snapshot_block_bytes(b[:64]) if b.size >= 64 else 0
+        count = b.size // per if per > 0 else 0
+        out = np.zeros(max(count, 1) * self.belief_snapshot_bytes, np.uint8)
+        self._chk(self.L.fba_belief_convert(self.h, count, b.ctypes.data if b.size else None, b.nbytes, seed, first_run, out.ctypes.data, out.nbytes))
+        return out.tobytes()
 
     def last_step_info(self):
         out = np.zeros(self.slots, N.TRACE_DTYPE)

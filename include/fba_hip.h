@@ -81,7 +81,8 @@ enum {
     FBA_PHASE_RESET_FC  = 10, /*   ... resetDomainStateDistribution                            */
     FBA_PHASE_REJECT_FC = 11, /*   ... rejection sampling, unit = attempt index                */
     FBA_PHASE_RESET_SH  = 12, /* incubator belief, shadow filter: resetDomainStateDistribution     */
-    FBA_PHASE_INIT_SH   = 13  /*   ... initiate, unit = index of the bred particle                 */
+    FBA_PHASE_INIT_SH   = 13, /*   ... initiate, unit = index of the bred particle                 */
+    FBA_PHASE_CONVERT   = 14  /* fba_belief_convert: run = first_run + block, episode 0, t 0, unit = index of the particle written */
 };
 
 enum {
@@ -590,6 +591,42 @@ int fba_belief_snapshot_bytes(const fba_ctx* ctx, int64_t* per_slot);
 int fba_belief_export   (fba_ctx* ctx, int32_t first, int32_t count, void* buf, int64_t cap);
 int fba_belief_import   (fba_ctx* ctx, int32_t first, int32_t count, const void* buf, int64_t bytes);
 int fba_belief_replicate(fba_ctx* ctx, int32_t src, int32_t first, int32_t count);
+
+/* Fitting snapshot blocks to another context.  fba_belief_import and fba_run_bapomdp_span take blocks of the context's own fingerprint only;
+ * fba_belief_convert makes such blocks out of the blocks of a context that differs from `ctx`, the DESTINATION, in two fields only:
+ *   particles       (N' in the blocks, N in the context) may differ in every record format;
+ *   particle_bytes  may differ in the history formats 5..7, where it is the room of a record: particle_bytes / 4 - 2 entries.  It follows
+ *                   episodes * horizon, so this is what lets a filter learned in a 20-episode context continue in a 40-episode one.
+ * Every other fingerprint field -- magic, layout version, record format, weighted, model, domain, size, width, height, counts length, S, A,
+ * O, prior hash -- and, in the formats 0..4, particle_bytes too must equal the context's: FBA_EINVAL names block, field and both values, as
+ * an import does.  A block's hist_cnt and stride are judged against the room of the block's OWN records, by the rule an import applies to a
+ * context's.  `src` holds `count` blocks of one size, fba_snapshot_block_bytes of block 0 (src_bytes == count * that); a block of another
+ * particle count or room than block 0 is refused by name.  `dst` takes count blocks of fba_belief_snapshot_bytes (dst_cap says how much
+ * room it has) and must not overlap src.  fba_snapshot_block_bytes is host arithmetic on a header, 64 + (weighted ? particles * 8 : 0) +
+ * particles * particle_bytes, and needs no context.
+ * An output block carries the context's own header with hist_cnt and updates copied, the stride the context stores records of that many
+ * entries at, and the checksum of the new payload.  It is canonical -- every byte behind a record's last entry, behind the last record and
+ * behind a state word is zero -- so export(import(convert(x))) == convert(x) byte for byte.  Output particle j of block b is
+ *   N == N':            particle j, its weight bits unchanged: a change of room and stride only, and the input itself where particle_bytes
+ *                       is equal as well;
+ *   N != N', flat:      particle uniform_int(N'), the first draw of the Philox stream keyed by `seed` at position (run first_run + b,
+ *                       episode 0, t 0), phase FBA_PHASE_CONVERT, unit j;
+ *   N != N', weighted:  the particle WeightedFilter::sample picks for the threshold u01 * total, u01 the first draw of the same stream, over
+ *                       the device-order inclusive prefix sums of the N' source weights, total = the last of them; every output weight is
+ *                       1.0 / N, what a resampling leaves.  A block whose total is 0 or not finite cannot be sampled from: FBA_EINVAL names
+ *                       it (with N == N' it is taken, as an import takes it).
+ * first_run makes blocks [0, k) and [k, n) converted in two calls (first_run 0 and k) the bytes of one call.  Records are copied whole in the
+ * formats 0..4; history records move as words [0, 2 + entries), read at the source's stride, written at the destination's.
+ * FBA_EINVAL, all with the context untouched (the content of dst is then unspecified): count < 1, a null or overlapping buffer, src_bytes
+ * other than count blocks, dst_cap too small, a belief that snapshots refuse, a fingerprint mismatch, more entries per record than the
+ * destination has room for ("block b holds t entries per record / room for r"), and a source block that fails the device pass of an import
+ * -- the checksum and every weight, state, parent-set word, count and history entry, judged against the source's own particle count and
+ * stride; the message names block, particle and what was wrong.  FBA_EHIP where the staging memory cannot be had, with the bytes asked for.
+ * The call reads nothing of the context but its configuration and writes nothing: no slot, flag, counter, Philox position or trace record
+ * changes, so it may stand between any two calls.  Source and destination blocks are staged a chunk at a time, both sides together under
+ * the bound of fba_belief_import (FBA_SNAPSHOT_STAGE_BYTES), one block of each at least; results do not depend on the chunking. */
+int64_t fba_snapshot_block_bytes(const fba_snapshot_head* head);
+int fba_belief_convert(fba_ctx* ctx, int32_t count, const void* src, int64_t src_bytes, uint64_t seed, uint32_t first_run, void* dst, int64_t dst_cap);
 
 /* A Bayes-adaptive experiment in spans, resumed from belief snapshots bit for bit.  The call runs episodes [first_episode, stop_episode)
  * of every run of the experiment (0 <= first < stop <= episodes) at the stream positions of the uninterrupted experiment -- (run, episode, t)
