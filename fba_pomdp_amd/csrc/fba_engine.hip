@@ -1293,6 +1293,7 @@ struct CreateSwitches {
     int is_multi_min;                                              // ... the particle count from which the importance filter takes several launches
     int scratch_slots, node_bound;                                 // 0 unset, else at least 1 / 2
     int node_words;                                                // 0 unset
+    int search_quorum;                                             // 0 unset or out of 1..64
 };
 CreateSwitches read_create_switches()
 {
@@ -1320,6 +1321,7 @@ CreateSwitches read_create_switches()
     s.scratch_slots   = at_least(std::getenv("FBA_SCRATCH_SLOTS"), 1);   // (tests: several chunks with a few slots)
     s.node_bound      = at_least(std::getenv("FBA_NODE_BOUND"), 2);      // (tests: exercise the overflow guard)
     s.node_words      = number(std::getenv("FBA_NODE_WORDS"), 0);        // (layout experiments: padded records)
+    s.search_quorum   = search_quorum_switch(std::getenv("FBA_SEARCH_QUORUM"));   // (A/B runs, tests: search_kernel's boundary quorum, fba_launch_plan.h)
     return s;
 }
 
@@ -1757,6 +1759,7 @@ int plan_filters(fba_ctx* c, const CreateSwitches& sw)
     D.single_rec      = P.hist && !sw.double_buffer ? 1 : 0;
     D.ab_rows_hbm = sw.rows_hbm ? 1 : 0; D.ab_hist_multi = sw.hist_multi; D.ab_no_etiger = sw.no_etiger ? 1 : 0; D.ab_tiger_gather = sw.tiger_gather ? 1 : 0;
     D.ab_lockstep = sw.hist_lockstep ? 1 : 0;   // (on; only the bucket tree has it: alloc_tree)
+    D.search_quorum = (int8_t)sw.search_quorum;   // (0: search_plan's default for the kernel it chooses)
     D.side_w = 1 + (P.model == FBA_MODEL_BA_FACTORED ? c->fdesc.FS + c->fdesc.FO : (P.model == FBA_MODEL_BA_TABLE ? 2 : 0));
     if (P.hist) D.side_w = 2;  // {new state, the step's entry}
     D.is_multi    = weighted_filters(P) && P.N >= sw.is_multi_min;

@@ -7,6 +7,8 @@
 // environment read.  tests/test_launch_plan_cpu.py pins every decision to a recording.
 #pragma once
 
+#include <cstdlib>
+
 #include "fba_kernels.h"
 
 namespace fba {
@@ -109,17 +111,35 @@ constexpr bool updates_history_records(uint32_t key)
 }
 
 // ---- launch_search
+// The share of a wave's live trees, in 64ths, that has to wait at a simulation boundary before search_kernel runs the boundary phase for
+// them (back-up, then the next root sample) -- 64: when all of them wait, so the wave's trees run simulation i together (what every
+// instantiation executed before the schedule was explicit); 1: as soon as one waits.  A value below 64 stands here only where a same-box
+// A/B run against 64 found it faster (profiles/r21_search_quorum.txt): 60 -- the wave goes on when at most four of 64 trees are still in
+// their simulation -- for the two instantiations the benchmarks run, 2 to 8 % of their ticks; 56 and 62 gain less, 48 and below lose.
+constexpr int SEARCH_QUORUM_LOCKSTEP = 64;
+constexpr uint32_t SEARCH_C3 = search_key(true, 4, false, 0, FBA_MODEL_BA_FACTORED, 3, false, true, true);   // packed factored tiger of size 3 on the ETIGER layout
+constexpr int search_quorum_default(uint32_t kernel)
+{
+    return kernel == SEARCH_READS_COMPACT /* packed tabular tiger: C1, C2 */ || kernel == SEARCH_C3 ? 60 : SEARCH_QUORUM_LOCKSTEP;
+}
+// FBA_SEARCH_QUORUM as fba_create reads it: 1..64, or 0 (search_plan's default) when unset, not a number or out of range
+inline int search_quorum_switch(const char* text)
+{
+    const int v = text ? std::atoi(text) : 0;
+    return v >= 1 && v <= SEARCH_QUORUM_LOCKSTEP ? v : 0;
+}
 struct SearchPlan {
     uint32_t kernel;
     int block, slots_per_block;
     size_t lds;            // dynamic LDS bytes (search_kernel: the launcher adds FBA_SEARCH_LDS_PAD)
     int raise_lds;         // > 0: the kernel's limit of dynamic LDS has to be raised to this first
     bool order_first;      // search_order_kernel goes first (DeviceState::search_order)
+    int quorum;            // search_kernel: DeviceState::search_quorum of the launch (search_quorum_default, or the context's override)
     int grid(int slots) const { return (slots + slots_per_block - 1) / slots_per_block; }
 };
 inline SearchPlan search_plan(const Problem& P, const DeviceState& D)
 {
-    SearchPlan pl{0, SEARCH_BLOCK, SEARCH_BLOCK, 0, 0, false};
+    SearchPlan pl{0, SEARCH_BLOCK, SEARCH_BLOCK, 0, 0, false, SEARCH_QUORUM_LOCKSTEP};
     const int depth_cap = P.max_depth > 0 ? P.max_depth : 1;
     if (P.hist == 3) {  // history particles of the collision-avoidance FBA-POMDP: one lane per tree, node records (A = 3)
         pl.kernel = kernel_key(K_SEARCH_CA_HIST, 4);
@@ -171,6 +191,7 @@ inline SearchPlan search_plan(const Problem& P, const DeviceState& D)
         const int model = amax < 24 && (P.model == FBA_MODEL_BA_FACTORED || P.model == FBA_MODEL_BA_TABLE) ? P.model : FBA_MODEL_POMDP;
         pl.kernel = search_key(stage && model != FBA_MODEL_POMDP, amax, P.dirichlet_regular && model != FBA_MODEL_POMDP, 0, model);
     }
+    pl.quorum = D.search_quorum >= 1 && D.search_quorum <= SEARCH_QUORUM_LOCKSTEP ? D.search_quorum : search_quorum_default(pl.kernel);
     return pl;
 }
 

@@ -19,8 +19,21 @@ namespace fba {
 // POUCT::selectAction POUCT.cpp:63-129, RBAPOUCT::selectAction RBAPOUCT.cpp:67-153 (the root
 // particle's counts are read and never written: StepType::KeepCounts).
 // The recursion traverseActionNode / traverseChanceNode / rollout (POUCT.cpp:183-303) is unrolled
-// into a state machine whose every iteration performs exactly one simulator.step, so the 64
-// trees of a wave execute the expensive part (Philox + Dirichlet-row sampling) in lock-step.
+// into a state machine: a lane is in the tree, in a rollout, or AT A BOUNDARY -- its simulation has
+// finished, the back-up is pending and the next simulation not yet started.  Every trip of the loop
+// performs at most one simulator.step per lane, for the lanes that are in a simulation; which of
+// its two phases a trip runs is decided for the whole wave, from two ballots:
+//   boundary phase   back-up of the finished simulation, ++sim, root sample + particle fetch of the
+//                    next -- run when waiting lanes x 64 >= quorum x live lanes (or nobody steps);
+//   step phase       select, step, resolve the child -- for every lane in a simulation.
+// DeviceState::search_quorum = 64 is the wave whose trees run simulation i together (a lane that has
+// finished idles until the longest of the 64 ends); 1 pays the boundary phase on nearly every trip for
+// the third of the lanes that need it.  The value is the launch plan's (fba_launch_plan.h), measured
+// per instantiation.  When a lane runs its simulation i is invisible to it: the lanes are independent
+// trees and every draw comes from the stream of (run, episode, t, phase, simulation).
+// (Before the schedule was explicit the source read as "a boundary as soon as any lane waits"; the
+// compiler had split its single loop into a loop per simulation around a loop per step, which is
+// quorum 64.  The conditions are scalar now, so there is no divergent exit to nest.)
 // LDS per lane: the path needed for the bottom-up back-up, [depth][lane], and -- when a particle
 // record fits SEARCH_STAGE_WORDS (STAGE) -- the root particle's whole count blob, [word][lane], fetched with
 // one burst of 16-byte loads per simulation so that no step waits on HBM for its Dirichlet rows.
@@ -43,8 +56,10 @@ namespace fba {
 __device__ __forceinline__ int et_reward_code(double r) { return r == -1.0 ? 0 : (r == 10.0 ? 1 : 2); }
 __device__ __forceinline__ double et_reward(int code) { return code == 0 ? -1.0 : (code == 1 ? 10.0 : -100.0); }
 #ifdef FBA_PROFILE_SEARCH
-// profiling build only (scripts/search_regions.py): shader-clock cycles a wave spends in each region of the search loop
-__device__ unsigned long long g_search_prof[8];
+// profiling build only (scripts/search_regions.py): shader-clock cycles a wave spends in each region of the search loop [0..4, 6], and --
+// search_kernel -- what its waves executed: loop trips [5], lanes that stepped summed over the trips [8], boundary phases run [9] and the
+// lanes that were waiting for them [10]
+__device__ unsigned long long g_search_prof[12];
 #define PROF_MARK(r) { const long long now_ = clock64(); prof_[r] += now_ - prev_; prev_ = now_; }
 #else
 #define PROF_MARK(r)
@@ -175,17 +190,108 @@ __global__ void __launch_bounds__(SEARCH_BLOCK) search_kernel(Problem P, DeviceS
         g.stream(FBA_PHASE_SEARCH, (uint32_t)P.sims + 2u);
         ts_src = nested ? nested_sample(P, D, e, g, ts_state) : belief_sample_uniform(P, D, g);
     }
-    int sim = 0, mode = 0;  // 0 = start a simulation, 1 = in the tree, 2 = rollout
+    // mode: 0 = at a boundary (simulation `sim` has finished: its back-up is pending -- `plen` path entries and the rollout's return in
+    // `rret` -- and the next one is to start; sim = -1: nothing to back up yet), 1 = in the tree, 2 = rollout.  A lane whose sim has
+    // reached P.sims is done and only waits for the wave.
+    int sim = -1, mode = 0;
     int s = 0, node = 0, dtg = 0, plen = 0, rdepth = 0;
     const float* cnt = prec;
     double rret = 0, rdisc = 1;
+    const int quorum = D.search_quorum;   // (a kernel argument: scalar)
 #ifdef FBA_PROFILE_SEARCH
-    long long prof_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, prev_ = clock64();
+    long long prof_[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, prev_ = clock64();
 #endif
     while (true) {
         PROF_MARK(6)
-        if (mode == 0) {
-            if (sim >= P.sims) break;
+        // which phases this trip runs is decided for the wave, from two ballots: every branch on it is scalar
+        const bool waiting = mode == 0 && sim < P.sims;
+        const int n_wait = __popcll(__ballot(waiting)), n_act = __popcll(__ballot(mode != 0));
+        if (n_wait + n_act == 0) break;
+        const bool boundary = n_act == 0 || n_wait * 64 >= quorum * (n_wait + n_act);
+#ifdef FBA_PROFILE_SEARCH
+        const bool lead_ = lane == __ffsll((unsigned long long)__ballot(true)) - 1;   // the trip is charged once per wave
+        if (lead_) { prof_[5] += 1; if (boundary) { prof_[9] += 1; prof_[10] += n_wait; } }
+#endif
+        if (boundary && waiting) {
+            // back-up, leaf to root: ret = r + gamma * delayed; ChanceNode::addVisit(ret)
+            // (MCTSTreeNodes.cpp:8-12); ActionNode::addVisit() (:59-62)
+            // (the root is entry 0 of every path and no other entry: the loop runs over the nodes below it, the root's
+            // register copy is updated once behind it -- one code path per level instead of two)
+            double del = rret;
+            for (int k = plen - 1; k >= (ETIGER ? 4 : 1); --k) {
+                const int na     = ETIGER ? (int)path16[(size_t)k * SEARCH_BLOCK] : path_na[(size_t)k * SEARCH_BLOCK];
+                const double ret = (ETIGER ? et_reward(na >> 14) : (double)path_r[(size_t)k * SEARCH_BLOCK]) + P.gamma * del;
+                const int act    = ETIGER ? ((na >> 12) & 3) : (na & 31);
+                int32_t* rec = tree + (size_t)(ETIGER ? (na & 0xfff) : (na >> 5)) * W;
+                double* q    = reinterpret_cast<double*>(rec + D.cq_off) + act;
+                int n;
+                if (P.A == 3) {  // {visits, n0, n1, n2} is one 16-byte word: one load, one store
+                    int4* hp = reinterpret_cast<int4*>(rec);
+                    int4 h   = *hp;
+                    n = act == 0 ? ++h.y : (act == 1 ? ++h.z : ++h.w);
+                    ++h.x;
+                    *hp = h;
+                } else {
+                    n = ++rec[D.cn_off + act];
+                    if (D.cn_off) ++rec[0];
+                }
+                *q += (ret - *q) / (double)n;
+                del = ret;
+            }
+            if (ETIGER) {   // levels 3 and 2: header and Q from the descent, two stores each, no load
+#pragma unroll
+                for (int lv = 3; lv >= 2; --lv)
+                    if (plen > lv) {
+                        const int na     = (int)path16[(size_t)lv * SEARCH_BLOCK];
+                        const double ret = et_reward(na >> 14) + P.gamma * del;
+                        const int act    = (na >> 12) & 3;
+                        int32_t* rec     = tree + (size_t)(na & 0xfff) * W;
+                        int4 h           = lv == 3 ? cy_h3 : cy_h2;
+                        const double q0  = lv == 3 ? cy_q3 : cy_q2;
+                        const int n      = act == 0 ? ++h.y : (act == 1 ? ++h.z : ++h.w);
+                        ++h.x;
+                        *reinterpret_cast<int4*>(rec) = h;
+                        reinterpret_cast<double*>(rec + D.cq_off)[act] = q0 + (ret - q0) / (double)n;
+                        del = ret;
+                    }
+            }
+            if (ETIGER && plen > 1) {   // the node below the root: in LDS
+                const int na     = (int)path16[1 * SEARCH_BLOCK];
+                const double ret = et_reward(na >> 14) + P.gamma * del;
+                const int act    = (na >> 12) & 3;
+                uint32_t* nd     = l1 + (size_t)(na & 0xfff) * ET_NODE_WORDS * SEARCH_BLOCK;
+                uint32_t* cw     = nd + (act >> 1) * SEARCH_BLOCK;   // n0 | n1 << 16, n2
+                const uint32_t w = *cw;
+                const int n      = (int)((act & 1) ? (w >> 16) : (w & 0xffffu)) + 1;
+                *cw              = (act & 1) ? ((w & 0xffffu) | ((uint32_t)n << 16)) : ((w & 0xffff0000u) | (uint32_t)n);
+                uint32_t* qw     = nd + (size_t)(3 + 2 * act) * SEARCH_BLOCK;
+                double q         = __hiloint2double((int)qw[SEARCH_BLOCK], (int)qw[0]);
+                q += (ret - q) / (double)n;
+                qw[0]            = (uint32_t)__double2loint(q);
+                qw[SEARCH_BLOCK] = (uint32_t)__double2hiint(q);
+                del = ret;
+            }
+            if (plen > 0) {
+                const double ret = (ETIGER ? et_reward((int)path16[0] >> 14) : (double)path_r[0]) + P.gamma * del;
+                const int act    = ETIGER ? (((int)path16[0] >> 12) & 3) : (path_na[0] & 31);
+                // register-array element `act`: select, ONE division, write back
+                int n = 0;
+                double q = 0.0;
+#pragma unroll
+                for (int a2 = 0; a2 < AMAX; ++a2)
+                    if (a2 == act) { n = r_cn[a2]; q = r_cq[a2]; }
+                ++n;
+                q += (ret - q) / (double)n;
+#pragma unroll
+                for (int a2 = 0; a2 < AMAX; ++a2)
+                    if (a2 == act) { r_cn[a2] = n; r_cq[a2] = q; }
+                ++r_vis;
+            }
+            ++sim;
+            plen = 0;
+        }
+        PROF_MARK(4)
+        if (boundary && waiting && sim < P.sims) {
             g.stream(FBA_PHASE_SEARCH, (uint32_t)sim);
             int nest_state = ts_state;
             const int src = ts_src >= 0 ? ts_src : (nested ? nested_sample(P, D, e, g, nest_state) : belief_sample_uniform(P, D, g));
@@ -228,7 +334,7 @@ __global__ void __launch_bounds__(SEARCH_BLOCK) search_kernel(Problem P, DeviceS
             node = 0; dtg = max_tree_depth; plen = 0; mode = 1;
         }
         PROF_MARK(0)
-        bool finish = false, do_step = true;
+        bool finish = false, do_step = mode != 0;   // (lanes at a boundary sit the rest of the trip out)
         double delayed = 0;
         int a = 0;
         if (mode == 1) {  // traverseActionNode
@@ -263,7 +369,7 @@ __global__ void __launch_bounds__(SEARCH_BLOCK) search_kernel(Problem P, DeviceS
             }
             else if (node == 0) a = ucb_pick<AMAX>(P, g, D.log1p_tab, r_vis, r_cn, r_cq, true);
             else a = ucb_select<AMAX>(P, D, g, tree + (size_t)node * W, true);
-        } else {          // rollout: uniformly random action
+        } else if (mode == 2) {  // rollout: uniformly random action
             a = domain_random_action(P, g, s);
         }
         PROF_MARK(1)
@@ -349,92 +455,19 @@ __global__ void __launch_bounds__(SEARCH_BLOCK) search_kernel(Problem P, DeviceS
             }
         }
         PROF_MARK(3)
-        if (finish) {
-            // back-up, leaf to root: ret = r + gamma * delayed; ChanceNode::addVisit(ret)
-            // (MCTSTreeNodes.cpp:8-12); ActionNode::addVisit() (:59-62)
-            // (the root is entry 0 of every path and no other entry: the loop runs over the nodes below it, the root's
-            // register copy is updated once behind it -- one code path per level instead of two)
-            double del = delayed;
-            for (int k = plen - 1; k >= (ETIGER ? 4 : 1); --k) {
-                const int na     = ETIGER ? (int)path16[(size_t)k * SEARCH_BLOCK] : path_na[(size_t)k * SEARCH_BLOCK];
-                const double ret = (ETIGER ? et_reward(na >> 14) : (double)path_r[(size_t)k * SEARCH_BLOCK]) + P.gamma * del;
-                const int act    = ETIGER ? ((na >> 12) & 3) : (na & 31);
-                int32_t* rec = tree + (size_t)(ETIGER ? (na & 0xfff) : (na >> 5)) * W;
-                double* q    = reinterpret_cast<double*>(rec + D.cq_off) + act;
-                int n;
-                if (P.A == 3) {  // {visits, n0, n1, n2} is one 16-byte word: one load, one store
-                    int4* hp = reinterpret_cast<int4*>(rec);
-                    int4 h   = *hp;
-                    n = act == 0 ? ++h.y : (act == 1 ? ++h.z : ++h.w);
-                    ++h.x;
-                    *hp = h;
-                } else {
-                    n = ++rec[D.cn_off + act];
-                    if (D.cn_off) ++rec[0];
-                }
-                *q += (ret - *q) / (double)n;
-                del = ret;
-            }
-            if (ETIGER) {   // levels 3 and 2: header and Q from the descent, two stores each, no load
-#pragma unroll
-                for (int lv = 3; lv >= 2; --lv)
-                    if (plen > lv) {
-                        const int na     = (int)path16[(size_t)lv * SEARCH_BLOCK];
-                        const double ret = et_reward(na >> 14) + P.gamma * del;
-                        const int act    = (na >> 12) & 3;
-                        int32_t* rec     = tree + (size_t)(na & 0xfff) * W;
-                        int4 h           = lv == 3 ? cy_h3 : cy_h2;
-                        const double q0  = lv == 3 ? cy_q3 : cy_q2;
-                        const int n      = act == 0 ? ++h.y : (act == 1 ? ++h.z : ++h.w);
-                        ++h.x;
-                        *reinterpret_cast<int4*>(rec) = h;
-                        reinterpret_cast<double*>(rec + D.cq_off)[act] = q0 + (ret - q0) / (double)n;
-                        del = ret;
-                    }
-            }
-            if (ETIGER && plen > 1) {   // the node below the root: in LDS
-                const int na     = (int)path16[1 * SEARCH_BLOCK];
-                const double ret = et_reward(na >> 14) + P.gamma * del;
-                const int act    = (na >> 12) & 3;
-                uint32_t* nd     = l1 + (size_t)(na & 0xfff) * ET_NODE_WORDS * SEARCH_BLOCK;
-                uint32_t* cw     = nd + (act >> 1) * SEARCH_BLOCK;   // n0 | n1 << 16, n2
-                const uint32_t w = *cw;
-                const int n      = (int)((act & 1) ? (w >> 16) : (w & 0xffffu)) + 1;
-                *cw              = (act & 1) ? ((w & 0xffffu) | ((uint32_t)n << 16)) : ((w & 0xffff0000u) | (uint32_t)n);
-                uint32_t* qw     = nd + (size_t)(3 + 2 * act) * SEARCH_BLOCK;
-                double q         = __hiloint2double((int)qw[SEARCH_BLOCK], (int)qw[0]);
-                q += (ret - q) / (double)n;
-                qw[0]            = (uint32_t)__double2loint(q);
-                qw[SEARCH_BLOCK] = (uint32_t)__double2hiint(q);
-                del = ret;
-            }
-            if (plen > 0) {
-                const double ret = (ETIGER ? et_reward((int)path16[0] >> 14) : (double)path_r[0]) + P.gamma * del;
-                const int act    = ETIGER ? (((int)path16[0] >> 12) & 3) : (path_na[0] & 31);
-                // register-array element `act`: select, ONE division, write back
-                int n = 0;
-                double q = 0.0;
-#pragma unroll
-                for (int a2 = 0; a2 < AMAX; ++a2)
-                    if (a2 == act) { n = r_cn[a2]; q = r_cq[a2]; }
-                ++n;
-                q += (ret - q) / (double)n;
-#pragma unroll
-                for (int a2 = 0; a2 < AMAX; ++a2)
-                    if (a2 == act) { r_cn[a2] = n; r_cq[a2] = q; }
-                ++r_vis;
-            }
-            ++sim;
-            mode = 0;
-        }
-        PROF_MARK(4)
+        if (finish) { rret = delayed; mode = 0; }   // (to the boundary: what the back-up needs beside the path is the rollout's return)
 #ifdef FBA_PROFILE_SEARCH
-        prof_[5] += 1;
+        {
+            const int n_step_ = __popcll(__ballot(do_step));
+            if (lead_) prof_[8] += n_step_;
+        }
 #endif
     }
 #ifdef FBA_PROFILE_SEARCH
-    if (lane == 0)
-        for (int r = 0; r < 8; ++r) atomicAdd(&g_search_prof[r], (unsigned long long)prof_[r]);
+    // cycles: lane 0's clock, as ever; trips [5], stepping lanes [8], boundary phases [9] and the lanes they served [10]: from whichever
+    // lane led its wave (the first active lane of a ballot -- lane 0 may belong to an inactive slot)
+    for (int r = 0; r < 12; ++r)
+        if ((r == 5 || r >= 8 ? prof_[r] != 0 : lane == 0) && r != 7 && r != 11) atomicAdd(&g_search_prof[r], (unsigned long long)prof_[r]);
 #endif
     g.stream(FBA_PHASE_SEARCH, (uint32_t)P.sims + 1u);
     if (n_nodes > D.max_nodes) atomicCAS(D.fault, 0, -(1 + e));  // -> FBA_ESTATE on the host
@@ -1026,9 +1059,11 @@ __global__ void __launch_bounds__(SEARCH_BLOCK) search_ca_hist_kernel(Problem P,
 // ---------------------------------------------------------------------------------------------
 // Which instantiation, with what block, grid and LDS, is search_plan's decision (fba_launch_plan.h); here every instantiation stands once, behind
 // its key -- spelled from the same template arguments -- and is launched the same way
-void launch_search(const Problem& P, const DeviceState& D, hipStream_t st)
+void launch_search(const Problem& P, const DeviceState& D0, hipStream_t st)
 {
-    const SearchPlan pl = search_plan(P, D);
+    const SearchPlan pl = search_plan(P, D0);
+    DeviceState D = D0;
+    D.search_quorum = (int8_t)pl.quorum;   // (the kernel's copy names the value itself, never "the default")
     static const size_t lds_pad = std::getenv("FBA_SEARCH_LDS_PAD") ? (size_t)std::atoi(std::getenv("FBA_SEARCH_LDS_PAD")) : 0;  // occupancy experiments
     const size_t lds = pl.lds + (kernel_name(pl.kernel) == K_SEARCH ? lds_pad : 0);
     const dim3 grid(pl.grid(P.E)), block(pl.block);
@@ -1119,9 +1154,9 @@ void launch_search(const Problem& P, const DeviceState& D, hipStream_t st)
 #ifdef FBA_PROFILE_SEARCH
 extern "C" int fba_debug_search_profile(unsigned long long* out, int reset)
 {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_search_prof), sizeof(unsigned long long) * 8) != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_search_prof), sizeof(unsigned long long) * 12) != hipSuccess) return -1;   // (out: 12 entries)
     if (reset) {
-        const unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        const unsigned long long z[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         if (hipMemcpyToSymbol(HIP_SYMBOL(g_search_prof), z, sizeof z) != hipSuccess) return -1;
     }
     return 0;

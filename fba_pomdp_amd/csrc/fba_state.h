@@ -89,6 +89,8 @@ struct DeviceState {
     int8_t ab_hist_multi;     // FBA_HIST_MULTI=0 / 1: 1 = never, 2 = always update a history-particle slot by several workgroups (0: from 4 096 particles)
     int8_t ab_no_etiger;      // FBA_NO_ETIGER=1: the episodic tiger family on the general tree layout
     int8_t ab_tiger_gather;   // FBA_TIGER_GATHER=1: the packed tiger rejection update copies every new filter from its source records (reject_tiger_once_gather_kernel)
+    int8_t search_quorum;     // search_kernel runs its boundary phase (back-up, next root sample) when waiting lanes x 64 >= search_quorum x live lanes of the
+                              // wave.  In a context: FBA_SEARCH_QUORUM=1..64, or 0 for search_plan's default; in the launch's copy: the value itself
     int8_t ab_lockstep;       // the trees of a search_hist2_kernel wave start their simulations together (FBA_HIST_LOCKSTEP=0: each on its own)
     int32_t* search_order;    // [E] (bucket-tree contexts): the slots sorted by the depth their searches have left, rewritten in front of every
                               // search launch -- tree k of the launch works on slot search_order[k], so a wave's trees run simulations of one length

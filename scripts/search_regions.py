@@ -1,7 +1,9 @@
 """Where a wave of search_kernel spends its cycles: an instrumented build of the same sources (-DFBA_PROFILE_SEARCH:
 clock64() marks between the regions of the search loop, summed per wave) run on the bench workload.
 python scripts/search_regions.py build   (here: hipcc, no GPU needed)  ->  fba_pomdp_amd/libfba_hip_prof.so
-python scripts/search_regions.py [slots] (on the GPU box)              ->  one JSON line"""
+python scripts/search_regions.py [slots] (on the GPU box)              ->  one JSON line
+search_kernel also counts, per wave, its loop trips, the lanes that step in each and the boundary phases (back-up + next root sample) it
+runs: lane-steps per wave-trip and boundary phases per simulation, under FBA_SEARCH_QUORUM=1..64 or the launch plan's default."""
 import ctypes as C
 import json
 import os
@@ -9,7 +11,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PROF = os.path.join(ROOT, "fba_pomdp_amd", "libfba_hip_prof.so")
+PROF = os.environ.get("FBA_PROF_LIB") or os.path.join(ROOT, "fba_pomdp_amd", "libfba_hip_prof.so")   # (FBA_PROF_LIB: another instrumented build, for A/B runs)
 sys.path.insert(0, ROOT)
 
 if len(sys.argv) > 1 and sys.argv[1] == "build":
@@ -36,18 +38,26 @@ else:
     kw = dict(sims=4096, particles=4096, horizon=10, episodes=64) if cfg == "c2" else dict(sims=1024, particles=1024, horizon=10, episodes=64)
     eng = fba.Engine("episodic-tiger", model=fba.MODEL_BA_TABLE, belief="rejection_sampling", runs=1 << 30, slots=slots, seed=20261003, **kw)
 L = N.load()
-out = (C.c_ulonglong * 8)()
+out = (C.c_ulonglong * 12)()
 eng.run_ticks(int(os.environ.get("FBA_WARM", "1")) if cfg in ("c3", "c4") else 2)
 L.fba_debug_search_profile(out, 1)
 c0 = eng.counters()
-eng.run_ticks(2 if cfg in ("c3", "c4") else 3)
+ticks = 2 if cfg in ("c3", "c4") else 3   # the measured ticks
+eng.run_ticks(ticks)
 L.fba_debug_search_profile(out, 0)
 c1 = eng.counters()
 names = ["root sample + particle fetch", "action (UCB / rollout draw)", "simulator step", "child lookup / expand / rollout sums", "back-up", "iterations", "loop head"]
 v = list(out)
 total = sum(v[i] for i in (0, 1, 2, 3, 4, 6))
 steps = c1.sim_steps - c0.sim_steps
-print(json.dumps({"slots": slots, "config": kw, "waves": slots // (16 if cfg == "c4" else 64), "sim_steps": steps, "wave_iterations": v[5],
-                  "steps_per_wave_iteration": steps / max(v[5], 1),
-                  "cycles_per_wave_iteration": total / max(v[5], 1),
-                  "share": {names[i]: round(v[i] / total, 4) for i in (0, 1, 2, 3, 4, 6)}}))
+line = {"slots": slots, "config": kw, "waves": slots // (16 if cfg == "c4" else 64), "sim_steps": steps, "wave_iterations": v[5],
+        "steps_per_wave_iteration": steps / max(v[5], 1),
+        "cycles_per_wave_iteration": total / max(v[5], 1),
+        "share": {names[i]: round(v[i] / total, 4) for i in (0, 1, 2, 3, 4, 6)}}
+if v[8]:   # search_kernel: what its waves executed.  A trip is charged once per wave, by the first active lane of a ballot, and the lanes that
+    # step in it are counted by another, so lane_steps_per_wave_trip is the step's lane utilisation x 64 whatever the schedule is
+    # (steps_per_wave_iteration above is that only while a wave's first lane runs as many trips as the wave)
+    launches = ticks * line["waves"] * kw["sims"]   # simulations of a wave's trees, as the wave sees them: one per tree and simulation index
+    line.update({"quorum": os.environ.get("FBA_SEARCH_QUORUM", "default"), "lane_steps": v[8], "lane_steps_per_wave_trip": v[8] / max(v[5], 1),
+                 "boundary_phases": v[9], "boundary_phases_per_simulation": v[9] / launches, "lanes_per_boundary_phase": v[10] / max(v[9], 1)})
+print(json.dumps(line))
