@@ -191,6 +191,11 @@ for belief_name, belief in (("importance", IS), ("rejection", REJ)):
     add(f"search_grid_tab_bucket_{belief_name}_no_lockstep", "s", grid_tab, bucket, P_belief=belief, D_ab_lockstep=0)
     for depth in (36, 37, 72, 73, 144, 145):     # 4 -> 2 -> 1 waves per workgroup, then one wave past 64 KB: 448 bytes per level + 896 per wave
         add(f"search_grid_tab_bucket_{belief_name}_depth{depth}", "s", grid_tab, bucket, P_belief=belief, P_max_depth=depth)
+for belief_name, belief in (("importance", IS), ("rejection", REJ)):
+    # (the halvings themselves: 4 * (448 * 34 + 896) = 64512 <= 64 KB < 4 * (448 * 35 + 896), 2 * (448 * 71 + 896) = 65408 <= 64 KB < 2 * (448 * 72 + 896);
+    #  36 | 37 and 72 | 73 above stand on one side each)
+    for depth in (34, 35, 71):
+        add(f"search_grid_tab_bucket_{belief_name}_depth{depth}", "s", grid_tab, bucket, P_belief=belief, P_max_depth=depth)
 for lds in (0, 1):
     for depth in (30, 40, 70, 80, 140, 150):
         add(f"search_grid_hist_bucket_lds{lds}_depth{depth}", "s", grid_hist, bucket, P_hist_lds=lds, P_max_depth=depth)

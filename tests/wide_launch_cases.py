@@ -57,10 +57,22 @@ def packed_ftiger_bytes(size):
     return 4 * ((nc // 2 + 2 + 3) // 4 * 4)       # uint16 increments, structure word, state
 
 
+def h2_wave_bytes_at(max_depth, cs):
+    """fba_launch_plan.h h2_wave_bytes for records of cs words: a wave's paths, its staged records, the roots' statistics"""
+    return max_depth * 16 * (8 + 4 + 4 + 4) + max(cs, 2 * max_depth) * 16 * 4 + 14 * 16 * 4
+
+
 def h2_wave_bytes(horizon, episodes):
-    """fba_search.hip h2_wave_bytes at max_depth = horizon: a wave's paths, its staged records, the roots' statistics"""
-    cs = (2 + episodes * horizon + 3) // 4 * 4
-    return horizon * 16 * (8 + 4 + 4 + 4) + max(cs, 2 * horizon) * 16 * 4 + 14 * 16 * 4
+    """... at max_depth = horizon"""
+    return h2_wave_bytes_at(horizon, (2 + episodes * horizon + 3) // 4 * 4)
+
+
+def h2_waves(max_depth, cs, shared=0, most=4, lds=64 * 1024):
+    """search_plan: (waves per workgroup of a bucket-tree search beside `shared` bytes of tables, whether the LDS limit has to be raised)"""
+    nw = most
+    while nw > 1 and shared + nw * h2_wave_bytes_at(max_depth, cs) > lds:
+        nw >>= 1
+    return nw, shared + nw * h2_wave_bytes_at(max_depth, cs) > lds
 
 
 def case(name, domain, model, belief, fmt, E=WIDE, runs=None, env=None, sample=False, **kw):
@@ -247,11 +259,13 @@ def oracle_side(c, whole=False):
     return dict(trace=tr, stats=stats, counters=counters, returns=ret, lengths=ln)
 
 
-def engine_side(c, fba):
-    """The same experiment on the engine, in E slots; the caller has set c["env"]."""
+def engine_side(c, fba, check=None):
+    """The same experiment on the engine, in E slots; the caller has set c["env"].  `check` sees the context before anything runs."""
     eng = fba.Engine(c["domain"], model=c["model"], belief=c["belief"], slots=c["E"], runs=c["runs"], trace=1, **c["kw"])
     assert eng.slots == c["E"]
     assert eng.particle_bytes == expected_particle_bytes(c, eng.ncnt), (eng.particle_bytes, eng.ncnt)
+    if check:
+        check(eng)
     stats = eng.run_bapomdp() if c["model"] != POMDP else [eng.run_planning()]
     cn = eng.counters()
     ret, ln = eng.returns()
