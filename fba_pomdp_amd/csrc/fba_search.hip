@@ -26,6 +26,19 @@ namespace fba {
 //   boundary phase   back-up of the finished simulation, ++sim, root sample + particle fetch of the
 //                    next -- run when waiting lanes x 64 >= quorum x live lanes (or nobody steps);
 //   step phase       select, step, resolve the child -- for every lane in a simulation.
+// In the episodic-tiger instantiations (ETIGER, below) the boundary phase also makes the new
+// simulation's first step, which is the same work for every lane it serves: at the root, statistics
+// in registers, the child one bit of l1_exists.  Its order for a waiting lane:
+//   1. start stream(sim + 1), draw the root particle; from a compact filter, request its 16-byte
+//      record (the back-up draws nothing, and the record is not needed before step 4);
+//   2. the back-up, ++sim;
+//   3. select at the root, from the registers as the back-up left them;
+//   4. wait for the record (the wider formats are fetched here), stage it for the deeper steps;
+//   5. the root's simulator.step -- a compact record's words straight from the load's registers;
+//   6. path entry 0, then the child: terminal or no depth left -> back to the boundary; the node
+//      after (listen, o) exists -> into the tree; else create it in LDS and start the rollout.
+// So the step phase of these instantiations never sees the root: no gather from registers, no root
+// case in the child lookup or the expansion, one trip fewer per simulation.
 // DeviceState::search_quorum = 64 is the wave whose trees run simulation i together (a lane that has
 // finished idles until the longest of the 64 ends); 1 pays the boundary phase on nearly every trip for
 // the third of the lanes that need it.  The value is the launch plan's (fba_launch_plan.h), measured
@@ -58,7 +71,8 @@ __device__ __forceinline__ double et_reward(int code) { return code == 0 ? -1.0 
 #ifdef FBA_PROFILE_SEARCH
 // profiling build only (scripts/search_regions.py): shader-clock cycles a wave spends in each region of the search loop [0..4, 6], and --
 // search_kernel -- what its waves executed: loop trips [5], lanes that stepped summed over the trips [8], boundary phases run [9] and the
-// lanes that were waiting for them [10]
+// lanes that were waiting for them [10]; the root block of the episodic-tiger boundary phase (selection, step, child) has its cycles in [7]
+// and the steps its lanes made in [11] (they are no part of [8])
 __device__ unsigned long long g_search_prof[12];
 #define PROF_MARK(r) { const long long now_ = clock64(); prof_[r] += now_ - prev_; prev_ = now_; }
 #else
@@ -212,6 +226,16 @@ __global__ void __launch_bounds__(SEARCH_BLOCK) search_kernel(Problem P, DeviceS
         const bool lead_ = lane == __ffsll((unsigned long long)__ballot(true)) - 1;   // the trip is charged once per wave
         if (lead_) { prof_[5] += 1; if (boundary) { prof_[9] += 1; prof_[10] += n_wait; } }
 #endif
+        int src = 0, nest_state = ts_state;
+        uint4 cv = make_uint4(0, 0, 0, 0);   // COMPACT: the next root particle's record, on its way while the back-up runs
+        if (ETIGER && boundary && waiting && sim + 1 < P.sims) {
+            // the next simulation's stream and its root sample first: the back-up draws nothing, and a compact record (one 16-byte
+            // load) is not needed before the back-up and the root's selection are done.  (The wider records keep their fetch behind
+            // the back-up: a burst of 4 to 12 float4 must not live across it.)
+            g.stream(FBA_PHASE_SEARCH, (uint32_t)(sim + 1));
+            src = ts_src >= 0 ? ts_src : (nested ? nested_sample(P, D, e, g, nest_state) : belief_sample_uniform(P, D, g));
+            if (COMPACT && (lazy_c & 2)) cv = reinterpret_cast<const uint4*>(prec)[src];
+        }
         if (boundary && waiting) {
             // back-up, leaf to root: ret = r + gamma * delayed; ChanceNode::addVisit(ret)
             // (MCTSTreeNodes.cpp:8-12); ActionNode::addVisit() (:59-62)
@@ -291,13 +315,19 @@ __global__ void __launch_bounds__(SEARCH_BLOCK) search_kernel(Problem P, DeviceS
             plen = 0;
         }
         PROF_MARK(4)
-        if (boundary && waiting && sim < P.sims) {
-            g.stream(FBA_PHASE_SEARCH, (uint32_t)sim);
-            int nest_state = ts_state;
-            const int src = ts_src >= 0 ? ts_src : (nested ? nested_sample(P, D, e, g, nest_state) : belief_sample_uniform(P, D, g));
+        const bool start = boundary && waiting && sim < P.sims;   // (ETIGER: the lanes that drew `src` above)
+        int a = 0;
+        if (ETIGER && start && max_tree_depth != 0)   // the root's selection, from the registers as the back-up left them
+            a = ucb_pick<AMAX>(P, g, D.log1p_tab, r_vis, r_cn, r_cq, true);
+        PROF_MARK(7)
+        if (start) {
+            if (!ETIGER) {
+                g.stream(FBA_PHASE_SEARCH, (uint32_t)sim);
+                src = ts_src >= 0 ? ts_src : (nested ? nested_sample(P, D, e, g, nest_state) : belief_sample_uniform(P, D, g));
+            }
             cnt = prec + (size_t)src * P.Cs;
             if (COMPACT && (lazy_c & 2)) {
-                const uint4 v = reinterpret_cast<const uint4*>(prec)[src];
+                const uint4 v = cv;
                 stage[2 * SEARCH_BLOCK]  = __uint_as_float(v.x);
                 stage[5 * SEARCH_BLOCK]  = __uint_as_float(v.y);
                 stage[10 * SEARCH_BLOCK] = __uint_as_float(v.z);
@@ -334,19 +364,57 @@ __global__ void __launch_bounds__(SEARCH_BLOCK) search_kernel(Problem P, DeviceS
             node = 0; dtg = max_tree_depth; plen = 0; mode = 1;
         }
         PROF_MARK(0)
+        if (ETIGER && start) {
+            // the root's step and its child, here and not in the step phase: every lane of the phase is at node 0, its statistics are
+            // in registers, its child is one bit of l1_exists -- none of what the deeper nodes need (below) is paid for
+            if (dtg == 0) { mode = 0; rret = 0; }   // no depth left: the simulation ends without a step
+            else {
+                int o;
+                double r;
+                bool term;
+                if (FTIGER > 0 && STAGE && FTP)
+                    term = ftiger_step_packed<(FTIGER > 0 ? FTIGER : 1)>(P, g, LdsView<SEARCH_BLOCK>{stage}, s, a, o, r, NoInc{});
+                else if (FTIGER > 0 && STAGE) term = ftiger_step<(FTIGER > 0 ? FTIGER : 1)>(P, g, LdsView<SEARCH_BLOCK>{stage}, s, a, o, r, NoInc{});
+                else if (FTIGER > 0) term = ftiger_step<(FTIGER > 0 ? FTIGER : 1)>(P, g, GlobalSearchView{cnt}, s, a, o, r, NoInc{});
+                else if (TIGER_TABLE == 2)   // (a compact record's words from the registers its load filled, not back from the stage)
+                    term = tiger_step_packed(P, g, [&](int w) {
+                        if (lazy_c & 2) return w == 2 ? cv.x : (w == 5 ? cv.y : (w == 10 ? cv.z : (w == 11 ? cv.w & 0x7fffffffu : 0u)));
+                        return __float_as_uint(stage[w * SEARCH_BLOCK]);
+                    }, s_prior, s, a, o, r, NoInc{});
+                else if (STAGE) term = sim_step<REG>(P, g, LdsView<SEARCH_BLOCK>{stage}, s, a, o, r, NoInc{});
+                else term = sim_step<REG>(P, g, GlobalSearchView{cnt}, s, a, o, r, NoInc{});
+                ++steps;
+#ifdef FBA_PROFILE_SEARCH
+                prof_[11] += 1;
+#endif
+                path16[0] = (uint16_t)((a << 12) | (et_reward_code(r) << 14));
+                plen = 1;
+                if (term) { mode = 0; rret = 0; }
+                else if ((l1_exists >> o) & 1u) { node = -1 - o; --dtg; }   // (a continuing step is a `listen`: the child after observation o)
+                else {  // expand: the node below the root lives in LDS; then rollout(depth_to_go - 1)
+                    ++n_nodes;
+                    uint32_t* nd = l1 + (size_t)o * ET_NODE_WORDS * SEARCH_BLOCK;
+#pragma unroll
+                    for (int k = 0; k < ET_NODE_WORDS; ++k) nd[k * SEARCH_BLOCK] = 0;
+                    l1_exists |= 1u << o;
+                    mode = 2; rdepth = dtg - 1; rret = 0; rdisc = 1;
+                    if (rdepth == 0) mode = 0;
+                }
+            }
+        }
+        PROF_MARK(7)
         bool finish = false, do_step = mode != 0;   // (lanes at a boundary sit the rest of the trip out)
         double delayed = 0;
-        int a = 0;
         if (mode == 1) {  // traverseActionNode
             tree_depth = max(tree_depth, max_tree_depth - dtg);
             if (dtg == 0) { finish = true; do_step = false; }
             else if (ETIGER) {
-                // the node's statistics from where they live -- registers (root), LDS (the two nodes below it, node = -1 - o),
-                // HBM (the rest) -- then ONE selection for all lanes
-                int cn[AMAX], vis = r_vis;
+                // the node's statistics from where they live -- LDS (the two nodes below the root, node = -1 - o), HBM (the rest) --
+                // then ONE selection for all lanes.  (The root's step is the boundary phase's: node != 0 here.)
+                int cn[AMAX], vis;
                 double cq[AMAX];
 #pragma unroll
-                for (int a2 = 0; a2 < AMAX; ++a2) { cn[a2] = r_cn[a2]; cq[a2] = r_cq[a2]; }
+                for (int a2 = 3; a2 < AMAX; ++a2) { cn[a2] = 0; cq[a2] = 0.0; }   // (A = 3: never looked at)
                 if (node < 0) {
                     const uint32_t* nd = l1 + (size_t)(-1 - node) * ET_NODE_WORDS * SEARCH_BLOCK;
                     const uint32_t w0 = nd[0], w1 = nd[1 * SEARCH_BLOCK];
@@ -355,7 +423,7 @@ __global__ void __launch_bounds__(SEARCH_BLOCK) search_kernel(Problem P, DeviceS
                     for (int a2 = 0; a2 < 3; ++a2)
                         cq[a2] = __hiloint2double((int)nd[(4 + 2 * a2) * SEARCH_BLOCK], (int)nd[(3 + 2 * a2) * SEARCH_BLOCK]);
                     vis = (cn[0] + cn[1]) + cn[2];
-                } else if (node > 0) {
+                } else {
                     const int32_t* rec = tree + (size_t)node * W;
                     const int4 h      = *reinterpret_cast<const int4*>(rec);
                     const double2 q01 = *reinterpret_cast<const double2*>(rec + 4);
@@ -397,8 +465,7 @@ __global__ void __launch_bounds__(SEARCH_BLOCK) search_kernel(Problem P, DeviceS
                 if (term) finish = true;
                 else {   // (a continuing step is a `listen`: the child after observation o)
                     int c = 0;   // 0 = none yet (the root is nobody's child)
-                    if (node == 0) c = ((l1_exists >> o) & 1u) ? -1 - o : 0;
-                    else if (node < 0) {
+                    if (node < 0) {
                         const uint32_t w2 = l1[((size_t)(-1 - node) * ET_NODE_WORDS + 2) * SEARCH_BLOCK];
                         c = (int)(o ? (w2 >> 16) : (w2 & 0xffffu));
                     } else {
@@ -409,18 +476,11 @@ __global__ void __launch_bounds__(SEARCH_BLOCK) search_kernel(Problem P, DeviceS
                     else {  // expand: new leaf, then rollout(depth_to_go - 1)
                         const int nn = min(n_nodes, D.max_nodes - 1);
                         ++n_nodes;
-                        if (node == 0) {
-                            uint32_t* nd = l1 + (size_t)o * ET_NODE_WORDS * SEARCH_BLOCK;
-#pragma unroll
-                            for (int k = 0; k < ET_NODE_WORDS; ++k) nd[k * SEARCH_BLOCK] = 0;
-                            l1_exists |= 1u << o;
-                        } else {
-                            node_init(D, tree + (size_t)nn * W, P.A, P.O);
-                            if (node < 0) {
-                                uint32_t* w2 = l1 + ((size_t)(-1 - node) * ET_NODE_WORDS + 2) * SEARCH_BLOCK;
-                                *w2 = o ? ((*w2 & 0xffffu) | ((uint32_t)nn << 16)) : ((*w2 & 0xffff0000u) | (uint32_t)nn);
-                            } else tree[(size_t)node * W + D.child_off + 2 * 2 + o] = nn;
-                        }
+                        node_init(D, tree + (size_t)nn * W, P.A, P.O);
+                        if (node < 0) {
+                            uint32_t* w2 = l1 + ((size_t)(-1 - node) * ET_NODE_WORDS + 2) * SEARCH_BLOCK;
+                            *w2 = o ? ((*w2 & 0xffffu) | ((uint32_t)nn << 16)) : ((*w2 & 0xffff0000u) | (uint32_t)nn);
+                        } else tree[(size_t)node * W + D.child_off + 2 * 2 + o] = nn;
                         mode = 2; rdepth = dtg - 1; rret = 0; rdisc = 1;
                         if (rdepth == 0) finish = true;
                     }
@@ -465,9 +525,9 @@ __global__ void __launch_bounds__(SEARCH_BLOCK) search_kernel(Problem P, DeviceS
     }
 #ifdef FBA_PROFILE_SEARCH
     // cycles: lane 0's clock, as ever; trips [5], stepping lanes [8], boundary phases [9] and the lanes they served [10]: from whichever
-    // lane led its wave (the first active lane of a ballot -- lane 0 may belong to an inactive slot)
+    // lane led its wave (the first active lane of a ballot -- lane 0 may belong to an inactive slot); root steps [11]: every lane's own
     for (int r = 0; r < 12; ++r)
-        if ((r == 5 || r >= 8 ? prof_[r] != 0 : lane == 0) && r != 7 && r != 11) atomicAdd(&g_search_prof[r], (unsigned long long)prof_[r]);
+        if (r == 5 || r >= 8 ? prof_[r] != 0 : lane == 0) atomicAdd(&g_search_prof[r], (unsigned long long)prof_[r]);
 #endif
     g.stream(FBA_PHASE_SEARCH, (uint32_t)P.sims + 1u);
     if (n_nodes > D.max_nodes) atomicCAS(D.fault, 0, -(1 + e));  // -> FBA_ESTATE on the host

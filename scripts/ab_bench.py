@@ -27,4 +27,5 @@ for r in range(rounds):
             d = json.loads(p.stdout.strip().splitlines()[-1])
             print(f"{name:24s} tick {d['ms_per_step']:8.2f} ms  search {d['search_kernel']['avg_ms']:8.2f}  belief {d['roofline']['avg_ms']:7.2f}  steps/s {d['value']:.4g}  search steps/s {d['search_kernel']['steps_per_s']:.4g}", flush=True)
         except Exception:
-            print(name, "FAILED", p.stderr[-800:], flush=True)
+            print(name, "FAILED", p.returncode, p.stderr[-800:], flush=True)
+            sys.exit(1)   # (nothing more is started on a GPU that a run may have left in a bad state)

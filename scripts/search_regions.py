@@ -46,18 +46,23 @@ ticks = 2 if cfg in ("c3", "c4") else 3   # the measured ticks
 eng.run_ticks(ticks)
 L.fba_debug_search_profile(out, 0)
 c1 = eng.counters()
-names = ["root sample + particle fetch", "action (UCB / rollout draw)", "simulator step", "child lookup / expand / rollout sums", "back-up", "iterations", "loop head"]
+names = ["root sample + particle fetch", "action (UCB / rollout draw)", "simulator step", "child lookup / expand / rollout sums", "back-up", "iterations", "loop head",
+         "root block (selection, step, child)"]
 v = list(out)
-total = sum(v[i] for i in (0, 1, 2, 3, 4, 6))
+regions = (0, 1, 2, 3, 4, 6) + ((7,) if v[7] else ())   # (the root block: search_kernel's episodic-tiger instantiations only)
+total = sum(v[i] for i in regions)
 steps = c1.sim_steps - c0.sim_steps
 line = {"slots": slots, "config": kw, "waves": slots // (16 if cfg == "c4" else 64), "sim_steps": steps, "wave_iterations": v[5],
         "steps_per_wave_iteration": steps / max(v[5], 1),
         "cycles_per_wave_iteration": total / max(v[5], 1),
-        "share": {names[i]: round(v[i] / total, 4) for i in (0, 1, 2, 3, 4, 6)}}
+        "share": {names[i]: round(v[i] / total, 4) for i in regions}}
 if v[8]:   # search_kernel: what its waves executed.  A trip is charged once per wave, by the first active lane of a ballot, and the lanes that
     # step in it are counted by another, so lane_steps_per_wave_trip is the step's lane utilisation x 64 whatever the schedule is
     # (steps_per_wave_iteration above is that only while a wave's first lane runs as many trips as the wave)
     launches = ticks * line["waves"] * kw["sims"]   # simulations of a wave's trees, as the wave sees them: one per tree and simulation index
     line.update({"quorum": os.environ.get("FBA_SEARCH_QUORUM", "default"), "lane_steps": v[8], "lane_steps_per_wave_trip": v[8] / max(v[5], 1),
-                 "boundary_phases": v[9], "boundary_phases_per_simulation": v[9] / launches, "lanes_per_boundary_phase": v[10] / max(v[9], 1)})
+                 "boundary_phases": v[9], "boundary_phases_per_simulation": v[9] / launches, "lanes_per_boundary_phase": v[10] / max(v[9], 1),
+                 # the steps made by the boundary phase's root block are counted apart (no part of lane_steps); a trip whose step phase had
+                 # no lane to serve still counts as a trip
+                 "root_lane_steps": v[11], "trips_per_simulation": v[5] / launches})
 print(json.dumps(line))
