@@ -5,8 +5,13 @@ element of a ragged chunk or a carry lost between two tiles would pass them all.
 of every switch, with at least three belief updates in a row in some slot (the buffer flip; a resampled filter feeding the next update), and
 every trace field -- weight_total, update_count and belief_hash after every update among them --, statistic, counter and per-run return
 must be the oracle's, bit for bit.  particle_bytes is compared with the format's formula, which says which record format fba_create chose
-at that N.  The two tests without a GPU keep the table honest: the thresholds are read out of the sources, so a moved threshold fails the
-table instead of leaving it beside the switch."""
+at that N.  The composite beliefs (reinvigoration, incubator, cheating-reinvigoration, Metropolis-Hastings, nested) run the same kernels on
+further filters that belief_hash does not cover: their cases also compare every filter of one slot, as the experiment left it, with the
+oracle's after that slot's last run, and test_composite_belief_caps creates contexts at and beyond their largest filters.  The tests
+without a GPU keep the table honest: the thresholds are read out of the sources, so a moved threshold fails the table instead of leaving it
+beside the switch; every family's cheapest case makes three updates in a row, re-draws its filter where the belief has a threshold for it,
+and makes more rejection attempts than one chunk holds where it has two rejection filters (9 s on the oracle for the composite families)."""
+import functools
 import os
 import re
 
@@ -30,7 +35,11 @@ def test_filter_size_equals_the_oracle(name, monkeypatch):
     streak = F.longest_update_streak(ref["trace"])
     print(f"{name}: {len(ref['trace'])} records, {int((ref['trace']['terminal'] == 0).sum())} updates, {streak} in a row")
     assert streak >= MIN_STREAK
-    W.assert_same_experiment(c, W.engine_side(c, fba), ref)   # (engine_side: slots, and particle_bytes against the format's formula)
+    final = []
+    after = (lambda eng: final.append(F.engine_final_filters(c, eng))) if c["family"] in F.FILTERS else None
+    W.assert_same_experiment(c, W.engine_side(c, fba, after=after), ref)   # (engine_side: slots, and particle_bytes against the format's formula)
+    for run, got in final:      # the composite beliefs: the filters themselves, which the trace's belief_hash covers in part
+        F.assert_same_filters(name, run, got, F.oracle_final_filters(c, run))
 
 
 def _constants():
@@ -54,6 +63,28 @@ def _constants():
     assert re.search(r"kernel_key\(K_REJECT_TIGER_LDS\), %s," % v, plan)
     assert re.search(r"reject_key\(false, 2, 0, %s\), %s," % (v, v), plan) and re.search(r"FBA_REJECT\(false, 2, 0, %s\)" % v, kernels)
     k["REJECT_512"] = int(v)
+    # the largest filters of the composite beliefs: what map_incubator, plan_filters and map_nested refuse (fba_engine.hip)
+    with open(os.path.join(CSRC, "fba_engine.hip")) as f:
+        engine = f.read()
+    body = lambda fn: re.search(r"\nint %s\([^)]*\)\n\{\n(.*?)\n\}\n" % fn, engine, re.S).group(1)
+    (v,) = re.findall(r'if \(cfg\.particles > (\w+)\) return fail\(nullptr, FBA_EINVAL, "incubator belief: at most %d particles per slot", (\w+)\);',
+                      body("map_incubator"))
+    assert v == ("IS_LDS_MAX_N", "IS_LDS_MAX_N")
+    k["INCUBATOR_MAX"] = k["IS_LDS_MAX_N"]
+    # (both refusals of plan_filters stand behind D.is_multi: a weighted filter of sw.is_multi_min particles or more)
+    refusals = re.findall(r'D\.is_multi\) return fail\(c, FBA_EINVAL, "([\w-]+) belief: at most %d particles per slot", IS_MAX_CHUNKS \* (\d+)\);',
+                          body("plan_filters"))
+    assert sorted(refusals) == [("cheating-reinvigoration", "256"), ("mh-within-gibbs", "256")]
+    assert re.search(r"D\.is_multi\s*=\s*weighted_filters\(P\) && P\.N >= sw\.is_multi_min;", body("plan_filters"))
+    assert re.search(r"s\.is_multi_min\s*=\s*multi_min \? [^;]* : IS_MAX_CHUNKS \* 256 \+ 1;", engine)
+    k["CHEATING_MAX"] = k["MH_MAX"] = k["IS_MAX_CHUNKS"] * 256
+    (v,) = re.findall(r'if \(cfg\.particles > (\d+)\) return fail\(nullptr, FBA_EINVAL, "nested belief: at most (\d+) count particles',
+                      body("map_nested"))
+    assert v[0] == v[1]
+    k["NESTED_MAX"] = int(v[0])
+    # (one lane per count particle in one workgroup: that is the limit)
+    assert len(re.findall(r"__launch_bounds__\(%s\) nested_(?:fill|update)_kernel\(" % v[0], kernels)) == 2
+    k["wave"] = F.WAVE
     return k
 
 
@@ -77,6 +108,8 @@ def test_filter_size_cases_straddle_every_switch_over():
                 assert k[sw] in chunks, (family, chunks)
                 assert any(0 < m - k[sw] < 8 for m in chunks), (family, chunks)
                 assert k[sw] * 256 in counts and any(n % 4 for n in counts if n > k[sw] * 256), (family, counts)
+            elif sw in F.CAPS:              # the largest filter of a composite belief: a case at exactly that N, none beyond
+                assert max(counts) == k[sw], f"{family}: no case at {k[sw]}, the most particles fba_create takes ({sw})"
             else:
                 c = k[sw] * 256 if sw == "IS_MAX_CHUNKS" else k[sw]
                 assert c in counts and c + 1 in counts, f"{family}: no case at {c} and {c + 1}, the two sides of {sw}"
@@ -92,12 +125,66 @@ def test_filter_size_cases_straddle_every_switch_over():
         assert c["E"] in (2, 3) and c["runs"] in (c["E"] + 1, c["E"] + 2) and kw["sims"] <= 8 and 4 <= kw["horizon"] <= 6
         assert kw.get("episodes", 1) in (1, 2) and kw.get("episodes", 1) * kw["horizon"] <= 126
         assert "episodic" not in c["domain"]
+        assert c["family"] not in F.FILTERS or c["fmt"] == "dense"
 
 
 @pytest.mark.parametrize("family", sorted(F.SWITCHES))
 def test_filter_size_cases_update_three_times_in_a_row(family):
     """the cheapest case of every family on the oracle alone: some slot makes three belief updates in a row within one run"""
     c = F.cheapest_of(family)
-    tr = W.oracle_side(c)["trace"]
+    tr = _oracle_trace(c["name"])
     assert len(tr) > 0
     assert F.longest_update_streak(tr) >= MIN_STREAK, (c["name"], tr["terminal"].tolist())
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle_trace(name):
+    """the oracle's trace of a case, computed once for the tests without a GPU (read only)"""
+    tr = W.oracle_side(F.BY_NAME[name])["trace"]
+    tr.setflags(write=False)
+    return tr
+
+
+@pytest.mark.parametrize("family", ["cheating_factored_tiger", "mh_gibbs_messages", "mh_gibbs_rejection", "mh_nips"])
+def test_filter_size_cases_trigger_the_redraw(family):
+    """the cheapest case of the beliefs that re-draw their filter below a log-likelihood threshold: with a threshold that is never reached
+    the oracle leaves other filters behind, so the case runs cheat_kernel or mh_kernel and not the plain importance filter alone"""
+    c = F.cheapest_of(family)
+    tr = _oracle_trace(c["name"])
+    never = W._run(W.make_oracle(c, runs=c["runs"], threshold=-1e9), True)[0]
+    assert len(tr) > 0 and len(never) > 0
+    n = min(len(tr), len(never))
+    differ = int((tr["belief_hash"][:n] != never["belief_hash"][:n]).sum())
+    print(f"{c['name']}: belief_hash differs in {differ} of {n} records from the run whose re-draw never triggers")
+    assert differ >= 1
+
+
+@pytest.mark.parametrize("family", ["reinvig_factored_tiger", "reinvig_generic", "incubator_factored_tiger", "incubator_collision_avoidance"])
+def test_filter_size_cases_reject_beyond_one_chunk(family):
+    """the cheapest case of the beliefs on two rejection filters: some update makes more attempts than the filter has particles (and than
+    one chunk of REJECT_BLOCK holds), so a further chunk of attempts has run"""
+    c = F.cheapest_of(family)
+    most = int(_oracle_trace(c["name"])["update_count"].max())
+    print(f"{c['name']}: at most {most} attempts in one update of {c['kw']['particles']} particles")
+    assert most > max(c["kw"]["particles"], _constants()["REJECT_BLOCK"])
+
+
+@pytest.mark.gpu
+def test_composite_belief_caps():
+    """what fba_create refuses and takes at the largest filters of the composite beliefs (contexts only: nothing runs)"""
+    k = _constants()
+    ft = dict(model=W.FACT, size=2, sims=8, slots=1)
+    with pytest.raises(ValueError, match=f"at most {k['INCUBATOR_MAX']} particles"):
+        fba.Engine(F.CFTIGER, belief="incubator", particles=k["INCUBATOR_MAX"] + 1, structure_prior=2, resample_amount=6, threshold=0.5, **ft)
+    with pytest.raises(ValueError, match=f"at most {k['CHEATING_MAX']} particles"):
+        fba.Engine(F.CFTIGER, belief="cheating-reinvigoration", particles=k["CHEATING_MAX"] + 1, structure_prior=1, threshold=-1.5,
+                   resample_amount=7, **ft)
+    for belief, option in (("mh-within-gibbs", 0), ("mh-within-gibbs", 1), ("mh-nips", 0)):
+        mh = dict(belief=belief, belief_option=option, structure_prior=2, threshold=-1.0, **ft)
+        with pytest.raises(ValueError, match=f"at most {k['MH_MAX']} particles"):
+            fba.Engine(F.CFTIGER, particles=k["MH_MAX"] + 1, **mh)
+        eng = fba.Engine(F.CFTIGER, particles=k["MH_MAX"], **mh)
+        assert eng.slots == 1 and eng.particle_bytes == W.dense_bytes(eng.ncnt)
+        eng.close()
+    with pytest.raises(ValueError, match=f"at most {k['NESTED_MAX']} count particles"):
+        fba.Engine(F.CTIGER, model=W.TABLE, belief="nested", particles=k["NESTED_MAX"] + 1, sims=8, slots=1)

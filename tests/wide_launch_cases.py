@@ -23,7 +23,7 @@ DOM = {"random-collision-avoidance": orc.DOM_COLLISION_AVOID, "centered-collisio
        "coffee": orc.DOM_COFFEE, "boutilier-coffee": orc.DOM_COFFEE_BOUTILIER, "agr": orc.DOM_AGR}
 BELIEF = {REJ: orc.BELIEF_REJECTION, IS: orc.BELIEF_IMPORTANCE, "reinvigoration": orc.BELIEF_REINVIGORATION,
           "cheating-reinvigoration": orc.BELIEF_CHEATING, "point_estimate": orc.BELIEF_POINT, "mh-within-gibbs": orc.BELIEF_MH_GIBBS,
-          "nested": orc.BELIEF_NESTED, "incubator": orc.BELIEF_INCUBATOR}
+          "mh-nips": orc.BELIEF_MH_NIPS, "nested": orc.BELIEF_NESTED, "incubator": orc.BELIEF_INCUBATOR}
 PLANNER = {"po-uct": orc.PLANNER_POUCT, "random": orc.PLANNER_RANDOM, "ts": orc.PLANNER_TS}
 
 # Domains whose episodes never end before the horizon (no terminal state in the domain): every length is the horizon there, so the
@@ -259,8 +259,9 @@ def oracle_side(c, whole=False):
     return dict(trace=tr, stats=stats, counters=counters, returns=ret, lengths=ln)
 
 
-def engine_side(c, fba, check=None):
-    """The same experiment on the engine, in E slots; the caller has set c["env"].  `check` sees the context before anything runs."""
+def engine_side(c, fba, check=None, after=None):
+    """The same experiment on the engine, in E slots; the caller has set c["env"].  `check` sees the context before anything runs,
+    `after` once everything has run and before the context is closed."""
     eng = fba.Engine(c["domain"], model=c["model"], belief=c["belief"], slots=c["E"], runs=c["runs"], trace=1, **c["kw"])
     assert eng.slots == c["E"]
     assert eng.particle_bytes == expected_particle_bytes(c, eng.ncnt), (eng.particle_bytes, eng.ncnt)
@@ -271,6 +272,8 @@ def engine_side(c, fba, check=None):
     ret, ln = eng.returns()
     out = dict(trace=eng.trace(), stats=[(s.count, s.mean, s.m2) for s in stats], counters=(cn.sim_steps, cn.belief_steps, cn.env_steps),
                returns=ret, lengths=ln)
+    if after:
+        after(eng)
     eng.close()
     return out
 
