@@ -81,6 +81,11 @@ struct fba_ctx {
     // fba_probe: on while probe.count > 0; the buffers probe points into are the context's (fba_probe_enable)
     BeliefProbeArgs probe{};
     int32_t* d_probe_meta = nullptr;   // [2][nodes] seg, rows
+    // fba_step_stats: on while step_stats.bins is set (with D.step_scratch); the buffers are the context's (fba_step_stats_enable)
+    StepStatsArgs step_stats{};
+    double step_stats_ms = 0;          // diagnostic (FBA_STEP_STATS_TIME=1 in the environment, scripts/bench_step_stats.py): the kernel's own time
+    uint64_t step_stats_launches = 0;  // ... by a HIP-event pair around each launch, and the launches
+    bool step_stats_timed = false;
 };
 
 namespace {
@@ -1116,6 +1121,31 @@ void launch_initiate(fba_ctx* c)
     else launch_init(c->P, c->D, c->stream);
 }
 
+// fba_step_stats: the slots that took their step in this tick, reduced into their bins (fba_step_stats.hip; in no time bucket)
+int launch_tick_step_stats(fba_ctx* c)
+{
+    StepStatsArgs a = c->step_stats;
+    a.probe_first = c->probe.first; a.probe_count = c->probe.count; a.probe_step = c->probe.step;
+    if (!c->step_stats_timed) {
+        launch_step_stats(c->P, c->D, a, c->stream);
+        return FBA_OK;
+    }
+    hipEvent_t ev[2];
+    HIPCHK(c, hipEventCreate(&ev[0]));
+    HIPCHK(c, hipEventCreate(&ev[1]));
+    HIPCHK(c, hipEventRecord(ev[0], c->stream));
+    launch_step_stats(c->P, c->D, a, c->stream);
+    HIPCHK(c, hipEventRecord(ev[1], c->stream));
+    HIPCHK(c, hipEventSynchronize(ev[1]));
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
+    (void)hipEventDestroy(ev[0]);
+    (void)hipEventDestroy(ev[1]);
+    c->step_stats_ms += ms;
+    c->step_stats_launches += 1;
+    return FBA_OK;
+}
+
 // one real time-step of every active slot
 int tick(fba_ctx* c)
 {
@@ -1127,6 +1157,8 @@ int tick(fba_ctx* c)
     if (c->probe.count > 0) launch_belief_probe(c->P, c->D, c->probe, c->stream);   // (the slots env_kernel has just flagged for an update; in no time bucket)
     if ((rc = timed(c, k_update_kind(c), [&] { launch_belief_update(c->P, c->D, c->stream); }))) return rc;
     if (c->D.trace_on) launch_flush(c->P, c->D, c->stream);
+    if (c->step_stats.bins)
+        if ((rc = launch_tick_step_stats(c))) return rc;   // (update_count is written; t and episode still address the step)
     launch_advance(c->P, c->D, c->d_n_active, c->stream);
     if ((rc = timed(c, FBA_K_BELIEF_INIT, [&] { launch_initiate(c); }))) return rc;
     if (c->P.model != FBA_MODEL_POMDP)
@@ -3012,6 +3044,7 @@ int fba_probe_enable(fba_ctx* c, int32_t first, int32_t count, int32_t capacity)
     dev_free(c, c->probe.acc);
     dev_free(c, c->probe.recs);
     dev_free(c, c->probe.seen);
+    dev_free(c, c->probe.step);
     dev_free(c, c->d_probe_meta);
     c->probe = BeliefProbeArgs{};
     if (count == 0) return FBA_OK;
@@ -3020,6 +3053,7 @@ int fba_probe_enable(fba_ctx* c, int32_t first, int32_t count, int32_t capacity)
     if ((rc = dev_alloc(c, &a.acc, (size_t)count * 3))) return rc;
     if ((rc = dev_alloc(c, &a.recs, (size_t)capacity))) return rc;
     if ((rc = dev_alloc(c, &a.seen, 1))) return rc;
+    if ((rc = dev_alloc(c, &a.step, (size_t)count * PROBE_STEP_WORDS))) return rc;
     if ((rc = dev_alloc(c, &c->d_probe_meta, (size_t)fl.nn * 2))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->d_probe_meta, fl.seg.data(), (size_t)fl.nn * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->d_probe_meta + fl.nn, fl.rows.data(), (size_t)fl.nn * 4, hipMemcpyHostToDevice, c->stream));
@@ -3059,6 +3093,53 @@ int fba_get_probe(const fba_ctx* cc, fba_probe_rec* out, int32_t cap)
         return a.t < b.t;
     });
     return n;
+}
+
+// fba_step_stats: the bins go into c->step_stats and the per-slot scratch of env_kernel into D.step_scratch; tick() launches
+// step_stats_kernel (fba_step_stats.hip) while they are set
+int fba_step_stats_enable(fba_ctx* c, int32_t on)
+{
+    if (!c) return FBA_EINVAL;
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // (nothing in flight writes the old buffers)
+    dev_free(c, c->step_stats.bins);
+    dev_free(c, c->D.step_scratch);
+    c->step_stats = StepStatsArgs{};
+    if (!on) return FBA_OK;
+    int rc;
+    const size_t n_bins = (size_t)c->P.episodes * (size_t)c->P.horizon;
+    StepStatsArgs a{};
+    if ((rc = dev_alloc(c, &a.bins, n_bins))) return rc;
+    if ((rc = dev_alloc(c, &c->D.step_scratch, (size_t)c->P.E))) { dev_free(c, a.bins); return rc; }
+    // (a mark the probe left while the statistics were off belongs to a step that no bin accounts)
+    if (c->probe.count > 0) HIPCHK(c, hipMemsetAsync(c->probe.step, 0, (size_t)c->probe.count * PROBE_STEP_WORDS * sizeof(double), c->stream));
+    a.n_bins = (int32_t)n_bins;
+    a.rows   = step_stats_rows(a.n_bins, c->P.A);
+    c->step_stats = a;
+    const char* env = std::getenv("FBA_STEP_STATS_TIME");
+    c->step_stats_timed = env && std::atoi(env) != 0;
+    c->step_stats_ms = 0; c->step_stats_launches = 0;
+    return FBA_OK;
+}
+
+int fba_get_step_stats(fba_ctx* c, fba_step_stat* out, int32_t cap)
+{
+    if (!c) return FBA_EINVAL;
+    if (!c->step_stats.bins) return fail(c, FBA_ESTATE, "fba_get_step_stats: the step statistics are off (fba_step_stats_enable)");
+    if (!out || cap < c->step_stats.n_bins)
+        return fail(c, FBA_EINVAL, "fba_get_step_stats: room for %d bins where episodes * horizon = %d are kept", out ? cap : 0, c->step_stats.n_bins);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, c->step_stats.bins, (size_t)c->step_stats.n_bins * sizeof(fba_step_stat), hipMemcpyDeviceToHost));
+    return c->step_stats.n_bins;
+}
+
+// diagnostic (scripts/bench_step_stats.py; not part of include/fba_hip.h): step_stats_kernel's own time since fba_step_stats_enable(1),
+// measured while FBA_STEP_STATS_TIME=1 stood in the environment of that call, and its launches
+int fba_debug_step_stats_ms(fba_ctx* c, double* ms, uint64_t* launches)
+{
+    if (!c) return FBA_EINVAL;
+    if (ms) *ms = c->step_stats_ms;
+    if (launches) *launches = c->step_stats_launches;
+    return FBA_OK;
 }
 
 int fba_belief_set(fba_ctx* c, int32_t slot, const int32_t* state, const double* weight, const float* counts)

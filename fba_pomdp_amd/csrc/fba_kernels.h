@@ -123,13 +123,35 @@ struct BeliefProbeArgs {
     unsigned long long* seen;   // [1] records written or counted since fba_probe_enable
     int32_t capacity;
     BeliefFactorLayout lay;     // chunk: PROBE_CHUNK, or what the LDS holds if that is fewer: one thread per particle in the evidence phase
+    double* step;               // [count][PROBE_STEP_WORDS]: the slot's evidence, next_true, post_true of this tick and a mark (1.0: probed this
+                                // tick) for fba_step_stats, whose kernel clears the mark; written whether or not the record fitted the buffer
 };
+constexpr int PROBE_STEP_WORDS = 4;
 // particles per probe workgroup, where the LDS holds more: one wave's worth for the one-thread-per-particle phases, and three to four
 // workgroups on a CU instead of the two that a full LDS leaves (same-box A/B on the shapes of scripts/bench_belief_probe.py, cost per
 // tick: gridworld 7 history records 104 -> 3.68 ms, 64 -> 2.73, 48 -> 2.91, 32 -> 4.05, 16 -> 7.79; collision avoidance fp32 173 -> 1.83,
 // 64 -> 0.75, 32 -> 0.80, 16 -> 0.95)
 constexpr int PROBE_CHUNK = 64;
 void launch_belief_probe(const Problem& P, const DeviceState& D, const BeliefProbeArgs& a, hipStream_t st);
+// fba_step_stats (fba_step_stats.hip): inside a tick, between the belief update and advance_kernel -- the slots that took their step in this
+// tick (DeviceState::adv != 0) reduced into the bins (episode, t) their steps belong to.  All state of the feature is here and in
+// DeviceState::step_scratch: buffers of the context's that fba_step_stats_enable allocates.  The probe members mirror the BeliefProbeArgs of
+// the tick (probe_count = 0: no probe)
+struct StepStatsArgs {
+    fba_step_stat* bins;        // [n_bins]
+    int32_t n_bins;             // episodes * horizon
+    int32_t rows;               // rows of a workgroup's LDS table: step_stats_rows bins are served per window
+    int32_t probe_first, probe_count;
+    double* probe_step;         // BeliefProbeArgs::step
+};
+constexpr int STEP_STATS_BLOCK  = 1024;  // slots one workgroup reduces per pass: few, large workgroups, so that few rows are added to a bin
+constexpr int STEP_STATS_GROUPS = 128;   // workgroups of a launch at most; beyond BLOCK * GROUPS slots they stride
+constexpr int STEP_STATS_LDS    = 60 * 1024;   // bytes of a workgroup's table of partial rows
+constexpr int STEP_STATS_ROW_TAIL = 17;  // words of fba_step_stat behind root_visits
+// 8-byte words of a partial row: {steps, terminals}, action and root_visits of the model's A actions, the tail
+__host__ __device__ inline int step_stats_row_words(int A) { return 2 + 2 * (A < FBA_MAX_ACTIONS ? A : FBA_MAX_ACTIONS) + STEP_STATS_ROW_TAIL; }
+inline int step_stats_rows(int n_bins, int A) { const int fit = STEP_STATS_LDS / (step_stats_row_words(A) * 8); return n_bins < fit ? n_bins : fit; }
+void launch_step_stats(const Problem& P, const DeviceState& D, const StepStatsArgs& a, hipStream_t st);
 // fba_belief_structures (fba_structures.hip): the parent-set word lists of slots [first, first + count) reduced into device buffers of the
 // caller's; a null output = not wanted (head is always).  The caller zeroes query_mass where nq > STRUCT_QUERY_LDS
 constexpr int STRUCT_TABLE      = FBA_STRUCT_TABLE;   // entries of a slot's table of distinct structures (open addressing, in LDS)

@@ -83,6 +83,7 @@ __global__ void env_kernel(Problem P, DeviceState D, int32_t* n_active)
         rec.reward = r; rec.update_count = -1; rec.weight_total = 0;
         rec.belief_hash = 1;  // "flush pending" marker, overwritten by flush_kernel
     }
+    if (D.step_scratch) D.step_scratch[e] = StepScratch{r, term ? 1 : 0, 0};   // (step statistics: read by step_stats_kernel in this tick)
     // the belief update of this tick still addresses its streams with (run, episode, t): the
     // position only moves in advance_kernel, after that update
     if (!term && t + 1 < P.horizon) {

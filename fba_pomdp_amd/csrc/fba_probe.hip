@@ -141,6 +141,8 @@ __global__ void __launch_bounds__(256) probe_finish_kernel(Problem P, DeviceStat
     rec.next_true = W > 0.0 ? acc[1] / W : 0.0;
     rec.post_true = W > 0.0 ? acc[2] / W : 0.0;
     acc[0] = acc[1] = acc[2] = 0.0;   // zeroed for the slot's next step
+    double* step = a.step + (size_t)b * PROBE_STEP_WORDS;   // for fba_step_stats: every evaluated step, whatever the buffer holds
+    step[0] = rec.evidence; step[1] = rec.next_true; step[2] = rec.post_true; step[3] = 1.0;
     const unsigned long long idx = atomicAdd(a.seen, 1ull);   // every record is counted, those below the capacity are kept
     if (idx < (unsigned long long)a.capacity) a.recs[idx] = rec;
 }

@@ -30,6 +30,13 @@
 
 namespace fba {
 
+// what env_kernel leaves of a real step for fba_step_stats (fba_step_stats.hip): the two fields of the step's trace record that live
+// nowhere else while the trace is off
+struct StepScratch {
+    double reward;
+    int32_t terminal, pad;
+};
+
 struct DeviceState {
     // --- per-slot experiment position ---
     int32_t* run;       // [E] global run index
@@ -175,6 +182,7 @@ struct DeviceState {
     int32_t* trace_count;
     int32_t trace_cap;
     int32_t trace_on;
+    StepScratch* step_scratch;  // [E] or null (step statistics off): env_kernel writes the reward and the terminal flag of the slot's step here
 };
 
 }  // namespace fba

@@ -35,7 +35,7 @@ namespace {
 struct Options {
     std::string mode;
     std::string domain, planner = "po-uct", belief = "rejection_sampling", seed, output_file = "results.txt", structure_prior,
-                                dirichlet = "expected", id, belief_option, probe_file, probe_slots, belief_in, belief_out, structure_out;
+                                dirichlet = "expected", id, belief_option, probe_file, probe_slots, step_stats_file, belief_in, belief_out, structure_out;
     int verbose = 0, runs = 1, horizon = 10, sims = 1000, max_depth = -1, particles = 100, size = 0, height = 0, width = 0,
         episodes = 1, slots = 0, device = 0, resample_amount = 0, first_episode = 0, stop_episode = -1;
     double discount = .95, exploration = 100, threshold = 0;
@@ -81,6 +81,10 @@ void usage()
         "      --probe-file FILE          (bapomdp, fbapomdp) one line per real step that a belief update follows:\n"
         "                                 run episode t action obs state evidence next_true post_true (fba_probe)\n"
         "      --probe-slots FIRST:COUNT  the slots whose steps are probed (all)\n"
+        "      --step-stats-file FILE     (every mode) one line per (episode, t) at which a step was taken, summed over all runs on the device:\n"
+        "                                 episode t steps terminals, the steps by action, reward_sum reward_sq_sum value_sum nodes_sum depth_sum\n"
+        "                                 attempts_steps attempts_sum, and -- fed by --probe-file's probe, else 0 -- probed evidence_zero\n"
+        "                                 evidence_sum log_evidence_sum log_evidence_sq_sum next_true_sum post_ratio_sum (fba_step_stats)\n"
         "      --first-episode K          (bapomdp, fbapomdp) run episodes [K, M) of every run only (0, --episodes): the result file\n"
         "      --stop-episode M           has one line per episode of the span\n"
         "      --belief-in FILE           the filters the runs continue from at episode K: one snapshot block for every run, or one\n"
@@ -145,6 +149,7 @@ bool parse(int argc, char** argv, Options& o, std::string& err)
             else if (k == "--slots") o.slots = std::stoi(v);
             else if (k == "--device") o.device = std::stoi(v);
             else if (k == "--probe-file") o.probe_file = v;
+            else if (k == "--step-stats-file") o.step_stats_file = v;
             else if (k == "--first-episode") o.first_episode = std::stoi(v);
             else if (k == "--stop-episode") o.stop_episode = std::stoi(v);
             else if (k == "--belief-in") o.belief_in = v;
@@ -252,6 +257,31 @@ bool write_probe(fba_ctx* ctx, const std::string& path)
         std::fprintf(f, "%d %d %d %d %d %d %.17g %.17g %.17g\n", r.run, r.episode, r.t, r.action, r.obs, r.state, r.evidence, r.next_true, r.post_true);
     }
     if (seen > got) std::fprintf(f, "# %lld steps were probed, %d records were kept\n", (long long)seen, got);
+    return std::fclose(f) == 0;
+}
+
+// --step-stats-file: one line per bin (episode, t) in which a step was taken; a leading comment line names the columns
+bool write_step_stats(fba_ctx* ctx, const fba_config& cfg, int A, const std::string& path)
+{
+    std::vector<fba_step_stat> bins((size_t)cfg.episodes * (size_t)cfg.horizon);
+    if (fba_get_step_stats(ctx, bins.data(), (int32_t)bins.size()) != (int)bins.size()) return false;
+    FILE* f = std::fopen(path.c_str(), "w");
+    if (!f) return false;
+    std::fprintf(f, "# episode t steps terminals");
+    for (int a = 0; a < A; ++a) std::fprintf(f, " action_%d", a);
+    std::fprintf(f, " reward_sum reward_sq_sum value_sum nodes_sum depth_sum attempts_steps attempts_sum probed evidence_zero evidence_sum log_evidence_sum "
+                    "log_evidence_sq_sum next_true_sum post_ratio_sum\n");
+    for (int e = 0; e < cfg.episodes; ++e)
+        for (int t = 0; t < cfg.horizon; ++t) {
+            const fba_step_stat& b = bins[(size_t)e * (size_t)cfg.horizon + (size_t)t];
+            if (!b.steps) continue;
+            std::fprintf(f, "%d %d %llu %llu", e, t, (unsigned long long)b.steps, (unsigned long long)b.terminals);
+            for (int a = 0; a < A; ++a) std::fprintf(f, " %llu", (unsigned long long)b.action[a]);
+            std::fprintf(f, " %.17g %.17g %.17g %llu %llu %llu %llu %llu %llu %.17g %.17g %.17g %.17g %.17g\n", b.reward_sum, b.reward_sq_sum, b.value_sum,
+                         (unsigned long long)b.nodes_sum, (unsigned long long)b.depth_sum, (unsigned long long)b.attempts_steps,
+                         (unsigned long long)b.attempts_sum, (unsigned long long)b.probed, (unsigned long long)b.evidence_zero, b.evidence_sum,
+                         b.log_evidence_sum, b.log_evidence_sq_sum, b.next_true_sum, b.post_ratio_sum);
+        }
     return std::fclose(f) == 0;
 }
 
@@ -390,6 +420,11 @@ int main(int argc, char** argv)
             return 1;
         }
     }
+    if (!o.step_stats_file.empty() && fba_step_stats_enable(ctx, 1) != FBA_OK) {
+        std::fprintf(stderr, "ERROR: %s\n", fba_last_error(ctx));
+        fba_destroy(ctx);
+        return 1;
+    }
     if (!o.structure_out.empty()) {
         const char* what = nullptr;
         if (o.mode != "fbapomdp") what = "--structure-out needs a factored Bayes-adaptive experiment (fbapomdp): only its particles carry a graph";
@@ -471,6 +506,15 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "ERROR: the probe's records could not be written to %s: %s\n", o.probe_file.c_str(), fba_last_error(ctx));
         fba_destroy(ctx);
         return 1;
+    }
+    if (!o.step_stats_file.empty()) {
+        int32_t S, A, O;
+        fba_domain_sizes(ctx, &S, &A, &O);
+        if (!write_step_stats(ctx, cfg, A, o.step_stats_file)) {
+            std::fprintf(stderr, "ERROR: the step statistics could not be written to %s: %s\n", o.step_stats_file.c_str(), fba_last_error(ctx));
+            fba_destroy(ctx);
+            return 1;
+        }
     }
     if (!o.belief_out.empty()) {   // run r's filter stands in slot r (runs <= slots)
         std::vector<char> out((size_t)cfg.runs * (size_t)per_block);

@@ -247,6 +247,20 @@ class Engine:
             capacity = max(self.cfg.runs, 1) * max(self.cfg.episodes, 1) * self.cfg.horizon
         self._chk(self.L.fba_probe_enable(self.h, first, count, capacity))
 
+    def step_stats_enable(self, on=True):
+        """Accumulate, for every real step run_planning / run_bapomdp / run_ticks make from now on, the per-(episode, t) statistics of
+        fba_step_stat on the device (fba_step_stats_enable); on=True allocates and clears the bins, on=False frees them.  A probe that
+        is enabled as well feeds the probe members, whatever its capacity.  Read-only on everything else."""
+        self._chk(self.L.fba_step_stats_enable(self.h, 1 if on else 0))
+
+    def step_stats(self):
+        """The bins as a structured array (N.STEP_STAT_DTYPE) of shape (episodes, horizon); raises FbaError while the statistics are off."""
+        out = np.zeros((max(self.cfg.episodes, 1), self.cfg.horizon), N.STEP_STAT_DTYPE)
+        n = self.L.fba_get_step_stats(self.h, out.ctypes.data, out.size)
+        if n < 0:
+            self._chk(n)
+        return out
+
     def probe(self):
         """The probe's records as a structured array (N.PROBE_DTYPE) sorted by (run, episode, t), with `.seen`."""
         seen = C.c_int64()

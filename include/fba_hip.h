@@ -468,6 +468,9 @@ int fba_get_counters(fba_ctx* ctx, fba_counters* out);
 int fba_get_return_sums(fba_ctx* ctx, double* out /* [3] */);
 int fba_get_kernel_times(fba_ctx* ctx, fba_kernel_time* out /* [FBA_K_COUNT] */);
 int fba_reset_kernel_times(fba_ctx* ctx);
+/* The records kept: min(records written, capacity).  The trace holds at most 2^22 records (2^18 with cfg.trace = 2, whose histograms take
+ * 256 bytes more per record), and never more than the experiment asked room for; records beyond the capacity are dropped silently.  With
+ * fba_step_stats on, the sum of `steps` over all bins exceeding fba_trace_count says the trace was truncated. */
 int fba_trace_count(const fba_ctx* ctx);
 int fba_get_trace(const fba_ctx* ctx, fba_trace_rec* out, int32_t cap);
 /* cfg.trace = 2: hist[i][s] = how many particles of the filter held domain state s after the belief update of trace record i
@@ -512,6 +515,41 @@ typedef struct fba_probe_rec {
 int fba_probe_enable(fba_ctx* ctx, int32_t first, int32_t count, int32_t capacity); /* count = 0: off, the buffer is freed */
 int fba_probe_count(const fba_ctx* ctx, int64_t* seen);  /* returns the records stored; *seen (may be NULL) counts every step probed, so seen > stored says the buffer was too small */
 int fba_get_probe(const fba_ctx* ctx, fba_probe_rec* out, int32_t cap);
+/* Per-step statistics of every run, reduced on the device inside the tick: episodes * horizon bins of 536 bytes whatever the number of runs,
+ * where the trace (capped, above) and the probe (a buffer with a capacity) cannot follow.  Bin (e, t) is a reduction over the trace records
+ * that fba_run_planning, fba_run_bapomdp, fba_run_bapomdp_span and fba_run_ticks would write for episode e, step t with cfg.trace = 1 and
+ * unlimited capacity, each member from the record's own fields (action, terminal, reward, n_nodes, tree_depth, root_n, root_q,
+ * update_count) -- filled whether or not cfg.trace is set.  Episodes are counted from 0 of the run; a span fills only its own episodes; the
+ * per-call interface writes nothing (its host holds every value).  A new fba_run_* does not clear the bins, as with the probe: runs
+ * executed one after the other by one slot, experiments run one after the other and spans add up; fba_step_stats_enable(1) clears them.
+ * Budgeted searches (search_budget > 0) are covered: a tick accounts only the slots that took their step in it.
+ * The probe members are filled for the steps a probe evaluates -- fba_probe_enable is on and covers the slot -- whether or not the step's
+ * record fitted the probe's buffer, so fba_probe_enable(first, count, 0) feeds the bins without keeping a record; without a probe they
+ * stay 0.  The logarithm is the engine's deterministic one (det_log), within 3e-16 * max(1, |log x|) of libm's.
+ * Every model (a plain POMDP included), belief, planner and record format is served.  FBA_EINVAL: a null ctx, out == NULL, cap < episodes *
+ * horizon; FBA_ESTATE: fba_get_step_stats while the statistics are off.  fba_get_step_stats synchronises the stream, like fba_get_probe.
+ * Read-only on everything else: with the statistics on, every trace record (belief_hash included), return, statistic, counter, probe
+ * record, fba_last_step_info, Philox position and particle keeps its bits; with them off a tick launches exactly what it launched before.
+ * The values are OUTSIDE the parity contract for their double sums only: the integer members are exact; a double member summed over n
+ * terms x_i is within n * 2^-52 * sum |x_i| of the exact sum, and exact where every term is (the built-in domains' rewards are multiples
+ * of 0.5 of magnitude <= 1000, so reward_sum and reward_sq_sum are exact below 2^53); each post_ratio term carries the one rounding of
+ * its division, each log term det_log's distance from libm. */
+typedef struct fba_step_stat {              /* one per (episode, t); every member 8-byte aligned, 536 bytes */
+    uint64_t steps;                         /* real steps taken at this (episode, t), over all runs            */
+    uint64_t terminals;                     /* of them terminal (no belief update follows)                     */
+    uint64_t action[FBA_MAX_ACTIONS];       /* steps by the action taken                                       */
+    uint64_t root_visits[FBA_MAX_ACTIONS];  /* sum of root_n[a] of the step's search                           */
+    uint64_t nodes_sum, depth_sum;          /* sum of n_nodes, tree_depth                                      */
+    uint64_t attempts_steps, attempts_sum;  /* non-terminal steps whose update reports update_count >= 0, and the sum of those counts */
+    int32_t  nodes_max, depth_max, attempts_max, reserved;
+    double   reward_sum, reward_sq_sum;     /* r, r*r                                                          */
+    double   value_sum, value_sq_sum;       /* q = root_q[action taken], q*q                                   */
+    uint64_t probed, evidence_zero;         /* steps the probe evaluated; of them with evidence == 0.0         */
+    double   evidence_sum, log_evidence_sum, log_evidence_sq_sum;   /* logs over the probed steps with evidence > 0 */
+    double   next_true_sum, post_ratio_sum; /* next_true; post_true / evidence (evidence > 0)                  */
+} fba_step_stat;
+int fba_step_stats_enable(fba_ctx* ctx, int32_t on);   /* 1: allocate (episodes * horizon bins) and clear; 0: free */
+int fba_get_step_stats(fba_ctx* ctx, fba_step_stat* out, int32_t cap);   /* out[episodes][horizon]; returns episodes * horizon */
 
 /* Belief snapshots: keeping, moving and copying the main filter of a slot in the record format the context stores (fba_particle_bytes) --
  * no count table is built anywhere, so a 16 384-particle gridworld filter is 3.0 MB, not the 3.1 GB fba_belief_get would hand out, and the
