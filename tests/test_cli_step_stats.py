@@ -7,7 +7,7 @@ import pytest
 
 import fba_pomdp_amd as fba
 from fba_pomdp_amd import _native as N
-from test_gpu_step_stats import _Ref
+from step_stats_size_cases import WINDOW_SHAPES, Ref as _Ref, fit
 
 pytestmark = pytest.mark.gpu
 
@@ -99,3 +99,22 @@ def test_planning_and_fbapomdp_are_accepted(cli, tmp_path):
     assert r.returncode == 0, r.stderr
     text = stats.read_text().splitlines()
     assert len(text) > 1 and sum(int(l.split()[2]) for l in text[1:] if int(l.split()[1]) == 0) == 4 * 2
+
+
+def test_more_bins_than_one_window(cli, tmp_path):
+    """the continuous tiger never ends an episode: every one of the episodes x horizon bins has a row, and they are more than a workgroup's
+    LDS table holds (step_stats_size_cases.fit)"""
+    e, h = WINDOW_SHAPES[1]
+    assert fit(3) < e * h <= 2 * fit(3)
+    out, stats = tmp_path / "ba.res", tmp_path / "stats.txt"
+    r = subprocess.run([cli, "bapomdp", "-D", "continuous-tiger", "-s", "4", "--particle-amount", "8", "--runs", "5", "--episodes", str(e), "-H", str(h),
+                        "--seed", "windows", "-f", str(out), "--step-stats-file", str(stats)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    eng = fba.Engine("continuous-tiger", model=N.MODEL_BA_TABLE, sims=4, particles=8, runs=5, episodes=e, horizon=h, seed=_seed("windows"), trace=1)
+    eng.step_stats_enable()
+    eng.run_bapomdp()
+    st = eng.step_stats()
+    rows = _rows(stats, eng.A)
+    assert len(rows) == e * h == st.size and np.all(st["steps"] == 5)
+    _compare(rows, st, eng.A, False, _Ref(eng, eng.trace()))
+    eng.close()

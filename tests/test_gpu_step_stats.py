@@ -7,22 +7,16 @@ terms x_i compares within n * 2^-52 * sum |x_i| of the fsum, the bound include/f
 Engine.probe() the same way, with the allowances the header names: one rounding per post_ratio term, and det_log's distance from libm,
 3e-16 * max(1, |log x|) per term (tests/test_oracle_golden.py pins it).  For log_evidence_sq_sum a term l^2 computed from a logarithm
 that is off by d <= 3e-16 * max(1, |l|) is off by at most 2 |l| d + d^2, plus the rounding of the square, 2^-53 l^2."""
-import math
-
 import numpy as np
 import pytest
 
 import fba_pomdp_amd as fba
 from fba_pomdp_amd import _native as N
+from step_stats_size_cases import INTS, Ref as _Ref, check_probe as _check_probe, probe_ref as _probe_ref      # (shared with test_gpu_step_stats_sizes.py)
 
 pytestmark = pytest.mark.gpu
 
 POMDP, TABLE, FACT = N.MODEL_POMDP, N.MODEL_BA_TABLE, N.MODEL_BA_FACTORED
-U = 2.0 ** -53
-INTS = ["steps", "terminals", "action", "root_visits", "nodes_sum", "depth_sum", "attempts_steps", "attempts_sum", "nodes_max", "depth_max",
-        "attempts_max", "reserved"]
-PROBE_INTS = ["probed", "evidence_zero"]
-PROBE_DOUBLES = ["evidence_sum", "log_evidence_sum", "log_evidence_sq_sum", "next_true_sum", "post_ratio_sum"]
 
 TIGER = dict(domain="episodic-tiger", model=TABLE, belief="rejection_sampling", runs=150, slots=70, episodes=3, horizon=6, sims=32, particles=64, seed=9101)
 GRID = dict(domain="gridworld", model=FACT, belief="importance_sampling", size=3, structure_prior=2, runs=40, slots=40, episodes=2, horizon=5, sims=64,
@@ -41,53 +35,6 @@ def _engine(cfg, **kw):
 
 def _run(eng):
     return eng.run_planning() if eng.cfg.model == POMDP else eng.run_bapomdp()
-
-
-class _Ref:
-    """the trace aggregated by (episode, t): the integer members exactly, the terms of every double member kept for fsum and the bound"""
-
-    def __init__(self, eng, tr):
-        E, H = max(eng.cfg.episodes, 1), eng.cfg.horizon
-        self.ints = np.zeros((E, H), N.STEP_STAT_DTYPE)
-        self.terms = {f: [[[] for _ in range(H)] for _ in range(E)] for f in ("reward_sum", "reward_sq_sum", "value_sum", "value_sq_sum")}
-        b = self.ints
-        for r in tr:
-            k = (int(r["episode"]), int(r["t"]))
-            a, q, rew = int(r["action"]), float(r["root_q"][int(r["action"])]), float(r["reward"])
-            b["steps"][k] += 1
-            b["terminals"][k] += int(r["terminal"] != 0)
-            b["action"][k][a] += 1
-            b["root_visits"][k] += r["root_n"].astype(np.uint64)
-            b["nodes_sum"][k] += int(r["n_nodes"])
-            b["depth_sum"][k] += int(r["tree_depth"])
-            b["nodes_max"][k] = max(b["nodes_max"][k], r["n_nodes"])
-            b["depth_max"][k] = max(b["depth_max"][k], r["tree_depth"])
-            if not r["terminal"] and r["update_count"] >= 0:
-                b["attempts_steps"][k] += 1
-                b["attempts_sum"][k] += int(r["update_count"])
-                b["attempts_max"][k] = max(b["attempts_max"][k], r["update_count"])
-            for f, v in (("reward_sum", rew), ("reward_sq_sum", rew * rew), ("value_sum", q), ("value_sq_sum", q * q)):
-                self.terms[f][k[0]][k[1]].append(v)
-
-    def check(self, st, what, probe=True):
-        assert st.shape == self.ints.shape, what
-        for f in INTS:
-            assert np.array_equal(st[f], self.ints[f]), f"{what}: {f}\n{st[f]}\n{self.ints[f]}"
-        worst = 0.0
-        for f, terms in self.terms.items():
-            for e, row in enumerate(terms):
-                for t, x in enumerate(row):
-                    dev, ref = float(st[f][e, t]), math.fsum(x)
-                    if f.startswith("reward"):
-                        assert dev == ref, f"{what}: {f}[{e}][{t}] {dev!r} != {ref!r}"
-                    else:
-                        bound = len(x) * 2 * U * math.fsum(abs(v) for v in x)
-                        worst = max(worst, abs(dev - ref) / bound if bound else 0.0)
-                        assert abs(dev - ref) <= bound, f"{what}: {f}[{e}][{t}] {dev!r} against {ref!r}, bound {bound:.3e}"
-        print(f"{what}: largest value-sum error / bound {worst:.3e}")
-        if probe:
-            for f in PROBE_INTS + PROBE_DOUBLES:
-                assert not np.any(st[f]), f"{what}: {f} without a probe"
 
 
 def _exercises(tr, st, what, terminals=True):
@@ -185,44 +132,6 @@ def test_read_only(particles):
 
 PROBE_TIGER = dict(TIGER, runs=70)
 PROBE_GRID = dict(GRID, search_budget=0)
-
-
-def _probe_ref(recs, shape):
-    terms = {f: [[[] for _ in range(shape[1])] for _ in range(shape[0])] for f in PROBE_DOUBLES + ["log_err", "log_sq_err", "ratio_err"]}
-    ints = np.zeros(shape, N.STEP_STAT_DTYPE)
-    for r in recs:
-        e, t = int(r["episode"]), int(r["t"])
-        ev, nt, pt = float(r["evidence"]), float(r["next_true"]), float(r["post_true"])
-        ints["probed"][e, t] += 1
-        ints["evidence_zero"][e, t] += int(ev == 0.0)
-        terms["evidence_sum"][e][t].append(ev)
-        terms["next_true_sum"][e][t].append(nt)
-        if ev > 0.0:
-            l = math.log(ev)
-            d = 3e-16 * max(1.0, abs(l))
-            terms["post_ratio_sum"][e][t].append(pt / ev)
-            terms["ratio_err"][e][t].append(U * pt / ev)
-            terms["log_evidence_sum"][e][t].append(l)
-            terms["log_err"][e][t].append(d)
-            terms["log_evidence_sq_sum"][e][t].append(l * l)
-            terms["log_sq_err"][e][t].append(2 * abs(l) * d + d * d + U * l * l)
-    return ints, terms
-
-
-def _check_probe(st, ints, terms, what):
-    for f in PROBE_INTS:
-        assert np.array_equal(st[f], ints[f]), f"{what}: {f}"
-    extra = {"evidence_sum": None, "next_true_sum": None, "post_ratio_sum": "ratio_err", "log_evidence_sum": "log_err", "log_evidence_sq_sum": "log_sq_err"}
-    for f in PROBE_DOUBLES:
-        for e in range(st.shape[0]):
-            for t in range(st.shape[1]):
-                x = terms[f][e][t]
-                mag = math.fsum(abs(v) for v in x)
-                bound = len(x) * 2 * U * mag + (math.fsum(terms[extra[f]][e][t]) if extra[f] else U * mag)
-                dev, ref = float(st[f][e, t]), math.fsum(x)
-                assert abs(dev - ref) <= bound, f"{what}: {f}[{e}][{t}] {dev!r} against {ref!r}, bound {bound:.3e}"
-                if not x:
-                    assert dev == 0.0
 
 
 @pytest.mark.parametrize("name", ["tiger", "gridworld"])
