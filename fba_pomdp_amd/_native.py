@@ -12,8 +12,8 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB_PATH = os.environ.get("FBA_LIB") or os.path.join(HERE, "libfba_hip.so")   # (FBA_LIB: an instrumented build of the same sources, scripts/search_regions.py)
-SOURCES = [os.path.join(HERE, "csrc", f) for f in ("fba_search.hip", "fba_kernels.hip", "fba_summary.hip", "fba_predict.hip", "fba_forecast.hip", "fba_probe.hip", "fba_step_stats.hip", "fba_structures.hip", "fba_snapshot.hip", "fba_convert.hip", "fba_restore.hip", "fba_engine.hip")]
-HEADERS = [os.path.join(HERE, "csrc", f) for f in ("fba_device.h", "fba_state.h", "fba_kernels.h", "fba_launch_plan.h", "fba_kernels_common.h", "fba_belief_factors.h", "fba_snapshot_format.h", "fba_structures.h", "fba_search_hist2.inc")] + [
+SOURCES = [os.path.join(HERE, "csrc", f) for f in ("fba_search.hip", "fba_kernels.hip", "fba_summary.hip", "fba_predict.hip", "fba_forecast.hip", "fba_probe.hip", "fba_step_stats.hip", "fba_structures.hip", "fba_structure_stats.hip", "fba_snapshot.hip", "fba_convert.hip", "fba_restore.hip", "fba_engine.hip")]
+HEADERS = [os.path.join(HERE, "csrc", f) for f in ("fba_device.h", "fba_state.h", "fba_kernels.h", "fba_launch_plan.h", "fba_kernels_common.h", "fba_belief_factors.h", "fba_snapshot_format.h", "fba_structures.h", "fba_structures_table.h", "fba_search_hist2.inc")] + [
     os.path.join(ROOT, "include", "fba_hip.h")]
 OBJ_DIR = os.path.join(HERE, "build")   # per-source objects (git-ignored): a change to one translation unit recompiles that one
 
@@ -143,6 +143,13 @@ STEP_STAT_DTYPE = np.dtype([
     ("evidence_sum", "<f8"), ("log_evidence_sum", "<f8"), ("log_evidence_sq_sum", "<f8"), ("next_true_sum", "<f8"), ("post_ratio_sum", "<f8"),
 ], align=True)
 
+# fba_structure_stat: the head of one bin (episode, t) of Engine.structure_stats
+STRUCT_STATS_MAX_QUERIES = 16
+STRUCTURE_STAT_DTYPE = np.dtype([
+    ("steps", "<u8"), ("weightless", "<u8"), ("overflowed", "<u8"), ("collapsed", "<u8"), ("distinct_sum", "<u8"),
+    ("distinct_max", "<i4"), ("reserved", "<i4"),
+], align=True)
+
 # fba_snapshot_head: the 64 bytes a belief snapshot block starts with
 SNAPSHOT_MAGIC, SNAPSHOT_VERSION, SNAPSHOT_CHECK_MUL = 0x53414246, 1, 0x9E3779B97F4A7C15
 SNAPSHOT_HEAD_DTYPE = np.dtype([
@@ -168,7 +175,7 @@ EXPORTS = [
     "fba_belief_update", "fba_belief_get", "fba_belief_get_particle", "fba_belief_set", "fba_belief_get_fully_connected", "fba_belief_get_nested", "fba_belief_get_shadow", "fba_belief_summary", "fba_predict_lens", "fba_belief_predict", "fba_belief_forecast", "fba_structure_lens", "fba_belief_structures", "fba_last_step_info",
     "fba_run_planning", "fba_run_bapomdp", "fba_run_ticks", "fba_get_returns", "fba_get_counters", "fba_get_return_sums",
     "fba_get_kernel_times", "fba_reset_kernel_times", "fba_trace_count", "fba_get_trace", "fba_get_trace_hist",
-    "fba_probe_enable", "fba_probe_count", "fba_get_probe", "fba_step_stats_enable", "fba_get_step_stats",
+    "fba_probe_enable", "fba_probe_count", "fba_get_probe", "fba_step_stats_enable", "fba_get_step_stats", "fba_structure_stats_enable", "fba_get_structure_stats",
     "fba_belief_snapshot_bytes", "fba_belief_export", "fba_belief_import", "fba_belief_replicate", "fba_run_bapomdp_span",
     "fba_snapshot_block_bytes", "fba_belief_convert",
     "fba_selftest_ucb", "fba_stat_add", "fba_stat_var", "fba_stat_stder",
@@ -297,6 +304,11 @@ def load():
         L.fba_step_stats_enable.argtypes = [vp, C.c_int32]
         L.fba_get_step_stats.argtypes = [vp, vp, C.c_int32]   # out: STEP_STAT_DTYPE[episodes * horizon], cap
         L.fba_debug_step_stats_ms.argtypes = [vp, P(C.c_double), P(C.c_uint64)]   # diagnostic, not in include/fba_hip.h
+    if not os.environ.get("FBA_LIB") or hasattr(L, "fba_structure_stats_enable"):
+        L.fba_structure_stats_enable.argtypes = [vp, C.c_int32, C.c_int32, vp]   # on, nq, query (uint32[nq][n_words])
+        # cap_bins; head (STRUCTURE_STAT_DTYPE), set_frac, query_frac (double), query_held, query_sole (uint64)
+        L.fba_get_structure_stats.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp]
+        L.fba_debug_structure_stats_ms.argtypes = [vp, P(C.c_double), P(C.c_uint64)]   # diagnostic, not in include/fba_hip.h
     if not os.environ.get("FBA_LIB") or hasattr(L, "fba_belief_export"):
         L.fba_belief_snapshot_bytes.argtypes = [vp, P(C.c_int64)]
         L.fba_belief_export.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int64]    # first, count, buf, cap

@@ -86,6 +86,11 @@ struct fba_ctx {
     double step_stats_ms = 0;          // diagnostic (FBA_STEP_STATS_TIME=1 in the environment, scripts/bench_step_stats.py): the kernel's own time
     uint64_t step_stats_launches = 0;  // ... by a HIP-event pair around each launch, and the launches
     bool step_stats_timed = false;
+    // fba_structure_stats: on while struct_stats.bins is set; the buffers are the context's (fba_structure_stats_enable)
+    StructStatsArgs struct_stats{};
+    double struct_stats_ms = 0;          // diagnostic (FBA_STRUCT_STATS_TIME=1 in the environment, scripts/bench_structure_stats.py): the
+    uint64_t struct_stats_launches = 0;  // kernels' own time by a HIP-event pair around the launches of a tick, and those ticks
+    bool struct_stats_timed = false;
 };
 
 namespace {
@@ -1146,6 +1151,34 @@ int launch_tick_step_stats(fba_ctx* c)
     return FBA_OK;
 }
 
+// fba_structure_stats: the main filters of the slots that took their step in this tick, a chunk of slots at a time, reduced into their
+// bins (fba_structure_stats.hip; in no time bucket)
+int launch_tick_structure_stats(fba_ctx* c)
+{
+    StructStatsArgs a = c->struct_stats;
+    hipEvent_t ev[2];
+    if (c->struct_stats_timed) {
+        HIPCHK(c, hipEventCreate(&ev[0]));
+        HIPCHK(c, hipEventCreate(&ev[1]));
+        HIPCHK(c, hipEventRecord(ev[0], c->stream));
+    }
+    for (int done = 0; done < c->P.E; done += a.chunk) {
+        a.first = done;
+        a.count = std::min(a.chunk, c->P.E - done);
+        launch_structure_stats(c->P, c->D, a, c->stream);
+    }
+    if (!c->struct_stats_timed) return FBA_OK;
+    HIPCHK(c, hipEventRecord(ev[1], c->stream));
+    HIPCHK(c, hipEventSynchronize(ev[1]));
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
+    (void)hipEventDestroy(ev[0]);
+    (void)hipEventDestroy(ev[1]);
+    c->struct_stats_ms += ms;
+    c->struct_stats_launches += 1;
+    return FBA_OK;
+}
+
 // one real time-step of every active slot
 int tick(fba_ctx* c)
 {
@@ -1155,6 +1188,8 @@ int tick(fba_ctx* c)
     if ((rc = timed(c, FBA_K_SEARCH, [&] { launch_search(c->P, c->D, c->stream); }))) return rc;
     if ((rc = timed(c, FBA_K_ENV, [&] { launch_env(c->P, c->D, c->d_n_active, c->stream); }))) return rc;
     if (c->probe.count > 0) launch_belief_probe(c->P, c->D, c->probe, c->stream);   // (the slots env_kernel has just flagged for an update; in no time bucket)
+    if (c->struct_stats.bins)
+        if ((rc = launch_tick_structure_stats(c))) return rc;   // (adv, episode and t address the step; the filter has not seen it)
     if ((rc = timed(c, k_update_kind(c), [&] { launch_belief_update(c->P, c->D, c->stream); }))) return rc;
     if (c->D.trace_on) launch_flush(c->P, c->D, c->stream);
     if (c->step_stats.bins)
@@ -2624,6 +2659,59 @@ int fba_structure_lens(const fba_ctx* c, int32_t* n_words, int32_t* n_sets)
     return FBA_OK;
 }
 
+// What fba_belief_structures and fba_structure_stats_enable (`who`) refuse alike, each with one text: the context ...
+static int structures_check_context(fba_ctx* c, const char* who, int32_t* n_words, int32_t* n_sets)
+{
+    const Problem& P = c->P;
+    if (P.nested)
+        return fail(c, FBA_EINVAL, "%s: the nested belief's particles are (model, state filter) pairs; read them with "
+                                   "fba_belief_get and fba_belief_get_nested", who);
+    fba_structure_lens(c, n_words, n_sets);
+    if (*n_words == 0)
+        return fail(c, FBA_EINVAL, "%s: the model has no parent-set words (fba_structure_lens is 0, 0): %s", who,
+                    P.model == FBA_MODEL_BA_FACTORED ? "its graph is fixed" : "only a factored model under a structure prior learns its graph");
+    return FBA_OK;
+}
+// ... the queries ...
+static int structures_check_queries(fba_ctx* c, const char* who, int32_t nq, int32_t nq_max, const char* nq_max_text, const uint32_t* query, int nw)
+{
+    if (nq < 0 || nq > nq_max) return fail(c, FBA_EINVAL, "%s: %d queries (0 to %s are served)", who, nq, nq_max_text);
+    if (nq > 0 && !query) return fail(c, FBA_EINVAL, "%s: %d queries and no query array", who, nq);
+    std::vector<uint32_t> limit;
+    structure_limits(c, limit);
+    for (int q = 0; q < nq; ++q)
+        for (int m = 0; m < nw; ++m)
+            if (query[(size_t)q * nw + m] >= limit[(size_t)m])
+                return fail(c, FBA_EINVAL, "%s: query %d, word %d: 0x%x names a parent beyond the node's candidates (legal below 0x%x)", who, q, m,
+                            query[(size_t)q * nw + m], limit[(size_t)m]);
+    return FBA_OK;
+}
+// ... and a record layout whose words the kernels cannot find
+static int structures_check_layout(fba_ctx* c, const char* who, int nw)
+{
+    const Problem& P = c->P;
+    if (P.hist && (P.hist != 1 || nw != 2 * P.A || nw >= 32)) return fail(c, FBA_ESTATE, "%s: history records without their %d parent-set words", who, 2 * P.A);
+    if (P.ft_packed && nw != 1) return fail(c, FBA_ESTATE, "%s: packed factored-tiger records of %d parent-set words", who, nw);
+    return FBA_OK;
+}
+// the queries as the records hold a structure ([nq][n_keys]): history records keep one bit per word (the word is 3 or 7, fba_belief_get
+// expands it), one key word in all
+static void structure_query_keys(const Problem& P, int nq, int nw, const uint32_t* query, std::vector<uint32_t>& keys)
+{
+    const int nk = P.hist ? 1 : nw;
+    keys.assign((size_t)nq * nk, 0u);
+    for (int q = 0; q < nq; ++q) {
+        const uint32_t* qw = query + (size_t)q * nw;
+        if (!P.hist) { std::copy(qw, qw + nw, keys.begin() + (size_t)q * nk); continue; }
+        uint32_t bits = 0;
+        for (int m = 0; m < nw; ++m) {
+            if (qw[m] == 7u) bits |= 1u << m;
+            else if (qw[m] != 3u) { bits = 0xffffffffu; break; }   // (legal for the node, but no record holds it: mass 0)
+        }
+        keys[(size_t)q] = bits;
+    }
+}
+
 // The parent-set word lists of slots [first, first + count) reduced on the device (fba_structures.hip), a chunk of slots at a time so that
 // the buffers of a chunk stay below 256 MB.  Reads the context only, as fba_belief_summary does.
 int fba_belief_structures(fba_ctx* c, int32_t first, int32_t count, int32_t top_k, int32_t nq, const uint32_t* query, fba_structure_head* head,
@@ -2631,47 +2719,19 @@ int fba_belief_structures(fba_ctx* c, int32_t first, int32_t count, int32_t top_
 {
     if (!c) return FBA_EINVAL;
     const Problem& P = c->P;
-    if (P.nested)
-        return fail(c, FBA_EINVAL, "fba_belief_structures: the nested belief's particles are (model, state filter) pairs; read them with "
-                                   "fba_belief_get and fba_belief_get_nested");
     int32_t nw = 0, ns = 0;
-    fba_structure_lens(c, &nw, &ns);
-    if (nw == 0)
-        return fail(c, FBA_EINVAL, "fba_belief_structures: the model has no parent-set words (fba_structure_lens is 0, 0): %s",
-                    P.model == FBA_MODEL_BA_FACTORED ? "its graph is fixed" : "only a factored model under a structure prior learns its graph");
+    TRY(structures_check_context(c, "fba_belief_structures", &nw, &ns));
     if (first < 0 || count < 0 || (long long)first + count > P.E)
         return fail(c, FBA_EINVAL, "fba_belief_structures: slots [%d, %lld) are not within the context's %d", first, (long long)first + count, P.E);
     if (top_k < 0 || top_k > FBA_STRUCT_MAX_TOP) return fail(c, FBA_EINVAL, "fba_belief_structures: top_k %d (0 to %d are served)", top_k, FBA_STRUCT_MAX_TOP);
-    if (nq < 0 || nq > (1 << 16)) return fail(c, FBA_EINVAL, "fba_belief_structures: %d queries (0 to 65 536 are served)", nq);
-    if (nq > 0 && !query) return fail(c, FBA_EINVAL, "fba_belief_structures: %d queries and no query array", nq);
-    std::vector<uint32_t> limit;
-    structure_limits(c, limit);
-    for (int q = 0; q < nq; ++q)
-        for (int m = 0; m < nw; ++m)
-            if (query[(size_t)q * nw + m] >= limit[(size_t)m])
-                return fail(c, FBA_EINVAL, "fba_belief_structures: query %d, word %d: 0x%x names a parent beyond the node's candidates (legal below 0x%x)", q, m,
-                            query[(size_t)q * nw + m], limit[(size_t)m]);
+    TRY(structures_check_queries(c, "fba_belief_structures", nq, 1 << 16, "65 536", query, nw));
     if (top_k == 0) { top_words = nullptr; top_mass = nullptr; }
     if (nq == 0) query_mass = nullptr;
     if (count == 0 || (!head && !set_mass && !top_words && !top_mass && !query_mass)) return FBA_OK;
-    if (P.hist && (P.hist != 1 || nw != 2 * P.A || nw >= 32)) return fail(c, FBA_ESTATE, "fba_belief_structures: history records without their %d parent-set words", 2 * P.A);
-    if (P.ft_packed && nw != 1) return fail(c, FBA_ESTATE, "fba_belief_structures: packed factored-tiger records of %d parent-set words", nw);
-    // the queries as the records hold a structure: history records keep one bit per word (the word is 3 or 7, fba_belief_get expands it)
+    TRY(structures_check_layout(c, "fba_belief_structures", nw));
     const int nk = P.hist ? 1 : nw;
     std::vector<uint32_t> keys;
-    if (query_mass) {
-        keys.assign((size_t)nq * nk, 0u);
-        for (int q = 0; q < nq; ++q) {
-            const uint32_t* qw = query + (size_t)q * nw;
-            if (!P.hist) { std::copy(qw, qw + nw, keys.begin() + (size_t)q * nk); continue; }
-            uint32_t bits = 0;
-            for (int m = 0; m < nw; ++m) {
-                if (qw[m] == 7u) bits |= 1u << m;
-                else if (qw[m] != 3u) { bits = 0xffffffffu; break; }   // (legal for the node, but no record holds it: mass 0)
-            }
-            keys[(size_t)q] = bits;
-        }
-    }
+    if (query_mass) structure_query_keys(P, nq, nw, query, keys);
     uint64_t keep = ~0ull;   // (FBA_STRUCT_HASH_KEEP in the environment: the bits of the table's hash that count, read at every call -- the tests' way to equal hashes)
     if (const char* ev = std::getenv("FBA_STRUCT_HASH_KEEP")) keep = std::strtoull(ev, nullptr, 0);
     const size_t per_slot = sizeof(fba_structure_head) + (set_mass ? (size_t)nw * ns * 8 : 0) + (top_words ? (size_t)top_k * nw * 4 : 0) +
@@ -3139,6 +3199,81 @@ int fba_debug_step_stats_ms(fba_ctx* c, double* ms, uint64_t* launches)
     if (!c) return FBA_EINVAL;
     if (ms) *ms = c->step_stats_ms;
     if (launches) *launches = c->step_stats_launches;
+    return FBA_OK;
+}
+
+// fba_structure_stats: bins, per-slot rows and the queries go into c->struct_stats; tick() launches the kernels of fba_structure_stats.hip
+// while they are set
+int fba_structure_stats_enable(fba_ctx* c, int32_t on, int32_t nq, const uint32_t* query)
+{
+    if (!c) return FBA_EINVAL;
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // (nothing in flight writes the old buffers)
+    dev_free(c, c->struct_stats.bins);
+    dev_free(c, c->struct_stats.rows);
+    dev_free(c, c->struct_stats.query);
+    c->struct_stats = StructStatsArgs{};
+    if (!on) return FBA_OK;
+    int32_t nw = 0, ns = 0;
+    TRY(structures_check_context(c, "fba_structure_stats_enable", &nw, &ns));
+    TRY(structures_check_queries(c, "fba_structure_stats_enable", nq, FBA_STRUCT_STATS_MAX_QUERIES, "16", query, nw));
+    TRY(structures_check_layout(c, "fba_structure_stats_enable", nw));
+    std::vector<uint32_t> keys;
+    structure_query_keys(c->P, nq, nw, query, keys);
+    StructStatsArgs a{};
+    a.n_bins = (int32_t)((size_t)c->P.episodes * (size_t)c->P.horizon);
+    a.nq = nq; a.n_words = nw; a.n_sets = ns; a.n_keys = c->P.hist ? 1 : nw; a.ncounts = c->fdesc.ncounts;
+    a.row_words = struct_stats_row_words(nw, ns, nq);
+    a.chunk     = struct_stats_chunk(c->P.E, a.row_words);
+    a.cols      = struct_stats_cols(a.row_words);
+    a.win_rows  = struct_stats_win_rows(a.n_bins, a.cols);
+    a.hash_keep = ~0ull;   // (FBA_STRUCT_HASH_KEEP in the environment, as fba_belief_structures reads it: here once, at enable)
+    if (const char* ev = std::getenv("FBA_STRUCT_HASH_KEEP")) a.hash_keep = std::strtoull(ev, nullptr, 0);
+    uint32_t* d_query = nullptr;
+    int rc;
+    if ((rc = dev_alloc(c, &a.bins, (size_t)a.n_bins * a.row_words))) return rc;
+    if ((rc = dev_alloc(c, &a.rows, (size_t)a.chunk * (STRUCT_STATS_SLOT_HEAD + a.row_words - STRUCT_STATS_BIN_HEAD)))) { dev_free(c, a.bins); return rc; }
+    if ((rc = dev_alloc(c, &d_query, keys.size()))) { dev_free(c, a.bins); dev_free(c, a.rows); return rc; }
+    a.query = d_query;
+    c->struct_stats = a;   // (from here on a failure leaves buffers the next enable or fba_destroy frees)
+    if (!keys.empty()) HIPCHK(c, hipMemcpyAsync(d_query, keys.data(), keys.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // (keys is the host's)
+    const char* env = std::getenv("FBA_STRUCT_STATS_TIME");
+    c->struct_stats_timed = env && std::atoi(env) != 0;
+    c->struct_stats_ms = 0; c->struct_stats_launches = 0;
+    return FBA_OK;
+}
+
+int fba_get_structure_stats(fba_ctx* c, int32_t cap_bins, fba_structure_stat* head, double* set_frac, double* query_frac, uint64_t* query_held,
+                            uint64_t* query_sole)
+{
+    if (!c) return FBA_EINVAL;
+    const StructStatsArgs& a = c->struct_stats;
+    if (!a.bins) return fail(c, FBA_ESTATE, "fba_get_structure_stats: the structure statistics are off (fba_structure_stats_enable)");
+    if (cap_bins < a.n_bins)
+        return fail(c, FBA_EINVAL, "fba_get_structure_stats: room for %d bins where episodes * horizon = %d are kept", cap_bins, a.n_bins);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<uint64_t> h((size_t)a.n_bins * a.row_words);
+    HIPCHK(c, hipMemcpy(h.data(), a.bins, h.size() * 8, hipMemcpyDeviceToHost));
+    const size_t cells = (size_t)a.n_words * a.n_sets, nq = (size_t)a.nq;
+    for (size_t b = 0; b < (size_t)a.n_bins; ++b) {   // a bin's words: head | set_frac | query_frac | query_held | query_sole (fba_kernels.h)
+        const uint64_t* w = h.data() + b * a.row_words;
+        if (head) std::memcpy(head + b, w, sizeof(fba_structure_stat));
+        w += STRUCT_STATS_BIN_HEAD;
+        if (set_frac) std::memcpy(set_frac + b * cells, w, cells * 8);
+        if (query_frac && nq) std::memcpy(query_frac + b * nq, w + cells, nq * 8);
+        if (query_held && nq) std::memcpy(query_held + b * nq, w + cells + nq, nq * 8);
+        if (query_sole && nq) std::memcpy(query_sole + b * nq, w + cells + 2 * nq, nq * 8);
+    }
+    return a.n_bins;
+}
+
+// diagnostic (scripts/bench_structure_stats.py; not part of include/fba_hip.h): the time of the kernels of fba_structure_stats.hip since
+// fba_structure_stats_enable(1), measured while FBA_STRUCT_STATS_TIME=1 stood in the environment of that call, and the ticks that launched them
+int fba_debug_structure_stats_ms(fba_ctx* c, double* ms, uint64_t* launches)
+{
+    if (!c) return FBA_EINVAL;
+    if (ms) *ms = c->struct_stats_ms;
+    if (launches) *launches = c->struct_stats_launches;
     return FBA_OK;
 }
 

@@ -172,6 +172,44 @@ struct BeliefStructuresArgs {
     double* query_mass;             // [count][nq]
 };
 void launch_belief_structures(const Problem& P, const DeviceState& D, const BeliefStructuresArgs& a, hipStream_t st);
+// fba_structure_stats (fba_structure_stats.hip): inside a tick, between the environment step and the belief update -- the main filters of
+// the slots that took their step in this tick (DeviceState::adv != 0) reduced as fba_belief_structures reduces them, and those per-slot
+// rows into the bins (episode, t) their steps belong to.  All state of the feature is here: buffers of the context's that
+// fba_structure_stats_enable allocates.  A bin, and a row of the reduction, is a list of 8-byte words:
+//   the fba_structure_stat head (STRUCT_STATS_BIN_HEAD words) | set_frac [n_words][n_sets] | query_frac [nq] | query_held [nq] | query_sole [nq]
+// and the row a slot's workgroup leaves in `rows` the same behind a head of its own (STRUCT_STATS_SLOT_HEAD words: bin + 1 in the low half
+// of the first -- 0: the slot took no step -- with the flags weightless (bit 32) and overflowed (bit 33); `distinct` in the second)
+constexpr int STRUCT_STATS_BIN_HEAD    = 6;      // 8-byte words of fba_structure_stat
+constexpr int STRUCT_STATS_SLOT_HEAD   = 2;
+constexpr int STRUCT_STATS_BLOCK       = 256;    // stage one: threads of a slot's workgroup
+constexpr int STRUCT_STATS_BINS_BLOCK  = 1024;   // stage two: threads of a workgroup
+constexpr int STRUCT_STATS_GROUP_SLOTS = 256;    // stage two: slots one workgroup reduces
+constexpr int STRUCT_STATS_LDS_WORDS   = 7680;   // stage two: 8-byte words of a workgroup's window of partial rows (60 KB) ...
+constexpr int STRUCT_STATS_COLS        = 96;     // ... of which a bin takes this many at most: a longer row is reduced a window of words at a time
+constexpr int STRUCT_STATS_CHUNK_SLOTS = 32768;  // slots of one pair of launches at most, as fba_belief_structures has it ...
+constexpr size_t STRUCT_STATS_ROWS_BYTES = (size_t)64 << 20;   // ... and what their rows may take
+struct StructStatsArgs {
+    unsigned long long* bins;   // [n_bins][row_words]
+    unsigned long long* rows;   // [chunk][STRUCT_STATS_SLOT_HEAD + row_words - STRUCT_STATS_BIN_HEAD]
+    uint32_t* query;            // [nq][n_keys] in key form (BeliefStructuresArgs::query)
+    int32_t n_bins;             // episodes * horizon
+    int32_t nq, n_words, n_sets, n_keys, ncounts;   // as in BeliefStructuresArgs
+    int32_t row_words;          // struct_stats_row_words
+    int32_t chunk;              // struct_stats_chunk: slots per pair of launches
+    int32_t cols, win_rows;     // stage two's LDS window: words of a row, bins (struct_stats_cols, struct_stats_win_rows)
+    int32_t first, count;       // the slots of this pair of launches
+    uint64_t hash_keep;         // struct_hash's `keep`
+};
+inline int struct_stats_row_words(int n_words, int n_sets, int nq) { return STRUCT_STATS_BIN_HEAD + n_words * n_sets + 3 * nq; }
+inline int struct_stats_cols(int row_words) { return row_words < STRUCT_STATS_COLS ? row_words : STRUCT_STATS_COLS; }
+inline int struct_stats_win_rows(int n_bins, int cols) { const int fit = STRUCT_STATS_LDS_WORDS / cols; return n_bins < fit ? n_bins : fit; }
+inline int struct_stats_chunk(int slots, int row_words)
+{
+    const size_t fit = STRUCT_STATS_ROWS_BYTES / ((size_t)(STRUCT_STATS_SLOT_HEAD + row_words - STRUCT_STATS_BIN_HEAD) * 8);
+    const int cap = fit < (size_t)STRUCT_STATS_CHUNK_SLOTS ? (int)fit : STRUCT_STATS_CHUNK_SLOTS;
+    return slots < cap ? (slots > 0 ? slots : 1) : (cap > 0 ? cap : 1);
+}
+void launch_structure_stats(const Problem& P, const DeviceState& D, const StructStatsArgs& a, hipStream_t st);   // one chunk: [a.first, a.first + a.count)
 // belief snapshots (fba_snapshot.hip): the blocks of `count` slots stand in `stage` at per_slot bytes each, laid out as include/fba_hip.h
 // states it (fba_snapshot_head, weights, records); slot first + b owns block b.  All state of the feature is in these arguments
 constexpr int SNAPSHOT_MAX_SLOTS = 32768;            // slots of one launch (a grid row each)

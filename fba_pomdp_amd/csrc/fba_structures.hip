@@ -9,22 +9,12 @@
 //
 // LDS of a workgroup: the table (STRUCT_TABLE entries of hash, mass, representative: 40 KB), STRUCT_HIST_CELLS histogram cells (8 KB)
 // and STRUCT_QUERY_LDS query masses (8 KB) -- 56 KB and a little, so that two workgroups share a CU's 160 KB.
-#include "fba_kernels_common.h"
-#include "fba_structures.h"
+#include "fba_structures_table.h"
 
 namespace fba {
 
 constexpr int STRUCT_BLOCK = 256;
 static_assert((STRUCT_TABLE & (STRUCT_TABLE - 1)) == 0, "a probe wraps with a mask");
-
-// word m of what identifies a record's structure: the words themselves, or -- history records -- the bits of rec[1] that stand for them
-// (one key word; record_mask_word expands bit m to the word 3 or 7 on output)
-__device__ __forceinline__ uint32_t record_key_word(const Problem& P, const BeliefStructuresArgs& a, const float* rec, int m)
-{
-    if (P.hist) return __float_as_uint(rec[1]) & ((1u << a.n_words) - 1u);
-    if (P.ft_packed) return __float_as_uint(rec[a.ncounts / 2]);
-    return __float_as_uint(rec[a.ncounts + m]);
-}
 
 // Dynamic LDS: [STRUCT_TABLE] hashes, [STRUCT_TABLE] masses, [STRUCT_HIST_CELLS] histogram, [STRUCT_QUERY_LDS] query masses (doubles and
 // 64-bit words), then [STRUCT_TABLE] representatives (int).
@@ -61,7 +51,7 @@ __global__ void __launch_bounds__(STRUCT_BLOCK) structures_kernel(Problem P, Dev
         const bool live = i < P.N;
         const float* rec = r.rec + (size_t)(live ? i : 0) * r.stride;
         const double w   = live ? particle_weight(P, D, r, i) : 0.0;
-        const auto key   = [&](int m) { return record_key_word(P, a, rec, m); };
+        const auto key   = [&](int m) { return record_key_word(P, nw, a.ncounts, rec, m); };
         lw += w;
         if (live) {
             if (a.set_mass)
@@ -80,45 +70,11 @@ __global__ void __launch_bounds__(STRUCT_BLOCK) structures_kernel(Problem P, Dev
                     }
                 }
         }
-        // The table: claim a free entry with the hash, or find the entry of that hash whose representative holds the same words; two
-        // structures of one hash are two entries.  A thread never waits for another: where an entry's owner has not named the
-        // representative yet, the thread leaves the round, and the barrier between rounds makes the name visible.
+        // The table (struct_table_rounds, fba_structures_table.h): claim a free entry with the hash, or find the entry of that hash whose
+        // representative holds the same words
         const unsigned long long h = live ? struct_hash(key, nk, a.hash_keep) : 0ull;
-        uint32_t pos = (uint32_t)(h >> 20) & (STRUCT_TABLE - 1);
-        int probes   = 0;
-        bool pending = live;
-        for (;;) {
-            while (pending) {
-                if (probes == STRUCT_TABLE) {   // every entry holds another structure
-                    unsafeAtomicAdd(&s_tot[1], w);
-                    s_flag[0] = 1;
-                    pending   = false;
-                    break;
-                }
-                const unsigned long long old = atomicCAS(&s_hash[pos], (unsigned long long)STRUCT_HASH_FREE, h);
-                if (old == STRUCT_HASH_FREE) {
-                    reinterpret_cast<volatile int*>(s_rep)[pos] = i;
-                    unsafeAtomicAdd(&s_mass[pos], w);
-                    pending = false;
-                    break;
-                }
-                if (old == h) {
-                    const int rp = reinterpret_cast<volatile int*>(s_rep)[pos];
-                    if (rp < 0) break;   // (next round)
-                    const float* rr = r.rec + (size_t)rp * r.stride;
-                    bool same = true;
-                    for (int m = 0; m < nk && same; ++m) same = key(m) == record_key_word(P, a, rr, m);
-                    if (same) {
-                        unsafeAtomicAdd(&s_mass[pos], w);
-                        pending = false;
-                        break;
-                    }
-                }
-                pos = (pos + 1) & (STRUCT_TABLE - 1);
-                ++probes;
-            }
-            if (!__syncthreads_or(pending ? 1 : 0)) break;
-        }
+        struct_table_rounds<STRUCT_TABLE>(s_hash, s_mass, s_rep, &s_tot[1], &s_flag[0], live, i, w, h, key,
+                                          [&](int rp, int m) { return record_key_word(P, nw, a.ncounts, r.rec + (size_t)rp * r.stride, m); }, nk);
     }
     unsafeAtomicAdd(&s_tot[0], lw);
     __syncthreads();

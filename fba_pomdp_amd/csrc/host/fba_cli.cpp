@@ -35,7 +35,8 @@ namespace {
 struct Options {
     std::string mode;
     std::string domain, planner = "po-uct", belief = "rejection_sampling", seed, output_file = "results.txt", structure_prior,
-                                dirichlet = "expected", id, belief_option, probe_file, probe_slots, step_stats_file, belief_in, belief_out, structure_out;
+                                dirichlet = "expected", id, belief_option, probe_file, probe_slots, step_stats_file, belief_in, belief_out, structure_out, structure_stats_file;
+    std::vector<std::string> structure_stats_queries;   // --structure-stats-query, as given
     int verbose = 0, runs = 1, horizon = 10, sims = 1000, max_depth = -1, particles = 100, size = 0, height = 0, width = 0,
         episodes = 1, slots = 0, device = 0, resample_amount = 0, first_episode = 0, stop_episode = -1;
     double discount = .95, exploration = 100, threshold = 0;
@@ -95,7 +96,12 @@ void usage()
         "      --belief-out FILE          every run's filter when the span is over (needs runs <= slots)\n"
         "      --structure-out FILE       (fbapomdp) one line per run when the experiment or span is over (needs runs <= slots):\n"
         "                                 run weight_total distinct overflow stored, then per stored structure of the top 8\n"
-        "                                 its mass and its parent-set words, hexadecimal, joined by commas (fba_belief_structures)");
+        "                                 its mass and its parent-set words, hexadecimal, joined by commas (fba_belief_structures)\n"
+        "      --structure-stats-file FILE  (fbapomdp) one line per (episode, t) at which a step was taken, summed over all runs on the device,\n"
+        "                                 whatever runs and slots: episode t steps weightless overflowed collapsed distinct_sum distinct_max,\n"
+        "                                 per query frac held sole, then per parent-set word the sums of set_mass / W joined by commas\n"
+        "                                 (fba_structure_stats)\n"
+        "      --structure-stats-query W0:W1:...  a graph the statistics follow: its parent-set words, hexadecimal (repeatable, at most 16)");
 }
 
 bool parse(int argc, char** argv, Options& o, std::string& err)
@@ -156,6 +162,13 @@ bool parse(int argc, char** argv, Options& o, std::string& err)
             else if (k == "--belief-out") o.belief_out = v;
             else if (k == "--belief-fit") { o.belief_fit = true; o.belief_fit_seed = std::stoull(v); }
             else if (k == "--structure-out") o.structure_out = v;
+            else if (k == "--structure-stats-file") o.structure_stats_file = v;
+            else if (k == "--structure-stats-query") {
+                if (v.empty() || v.find_first_not_of("0123456789abcdefABCDEF:") != std::string::npos || v.front() == ':' || v.back() == ':' ||
+                    v.find("::") != std::string::npos)
+                    throw std::invalid_argument(v);
+                o.structure_stats_queries.push_back(v);
+            }
             else if (k == "--probe-slots") {
                 const size_t colon = v.find(':');
                 if (colon == std::string::npos || std::stoi(v.substr(0, colon)) < 0 || std::stoi(v.substr(colon + 1)) < 1) throw std::invalid_argument(v);
@@ -285,6 +298,49 @@ bool write_step_stats(fba_ctx* ctx, const fba_config& cfg, int A, const std::str
     return std::fclose(f) == 0;
 }
 
+// --structure-stats-query: the words of one query, hexadecimal and joined by colons (parse has seen that nothing else stands there)
+std::vector<uint32_t> query_words(const std::string& v)
+{
+    std::vector<uint32_t> w;
+    for (size_t at = 0; at <= v.size();) {
+        const size_t colon = std::min(v.find(':', at), v.size());
+        w.push_back((uint32_t)std::stoul(v.substr(at, colon - at), nullptr, 16));
+        at = colon + 1;
+    }
+    return w;
+}
+
+// --structure-stats-file: one line per bin (episode, t) in which a step was taken; a leading comment line names the columns
+bool write_structure_stats(fba_ctx* ctx, const fba_config& cfg, int nq, const std::string& path)
+{
+    int32_t nw = 0, ns = 0;
+    fba_structure_lens(ctx, &nw, &ns);
+    const size_t bins = (size_t)cfg.episodes * (size_t)cfg.horizon, cells = (size_t)nw * ns;
+    std::vector<fba_structure_stat> head(bins);
+    std::vector<double> set_frac(bins * cells), query_frac(bins * nq);
+    std::vector<uint64_t> held(bins * nq), sole(bins * nq);
+    if (fba_get_structure_stats(ctx, (int32_t)bins, head.data(), set_frac.data(), query_frac.data(), held.data(), sole.data()) != (int)bins) return false;
+    FILE* f = std::fopen(path.c_str(), "w");
+    if (!f) return false;
+    std::fprintf(f, "# episode t steps weightless overflowed collapsed distinct_sum distinct_max");
+    for (int q = 0; q < nq; ++q) std::fprintf(f, " frac_%d held_%d sole_%d", q, q, q);
+    for (int m = 0; m < nw; ++m) std::fprintf(f, " set_frac_%d[%d]", m, ns);
+    std::fprintf(f, "\n");
+    for (size_t b = 0; b < bins; ++b) {
+        const fba_structure_stat& h = head[b];
+        if (!h.steps) continue;
+        std::fprintf(f, "%d %d %llu %llu %llu %llu %llu %d", (int)(b / (size_t)cfg.horizon), (int)(b % (size_t)cfg.horizon), (unsigned long long)h.steps,
+                     (unsigned long long)h.weightless, (unsigned long long)h.overflowed, (unsigned long long)h.collapsed,
+                     (unsigned long long)h.distinct_sum, h.distinct_max);
+        for (int q = 0; q < nq; ++q)
+            std::fprintf(f, " %.17g %llu %llu", query_frac[b * nq + q], (unsigned long long)held[b * nq + q], (unsigned long long)sole[b * nq + q]);
+        for (int m = 0; m < nw; ++m)
+            for (int v = 0; v < ns; ++v) std::fprintf(f, "%s%.17g", v ? "," : " ", set_frac[b * cells + (size_t)m * ns + v]);
+        std::fprintf(f, "\n");
+    }
+    return std::fclose(f) == 0;
+}
+
 // -v 1 / 2 / 3 in the reference's own format, "V%vlevel: %fbase\t%msg" (ArgumentParser.cpp:16-20), from the trace the engine kept:
 //   V1  run / episode                                       BAPOMDPExperiment.cpp:56, PlanningExperiment.cpp:41
 //   V2  the real step, the end of an episode                 Episode.cpp:44, :58
@@ -396,6 +452,19 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "ERROR: %s\n", err.c_str());
         return 1;
     }
+    {   // --structure-stats-file, --structure-stats-query: what is refused before a device is asked for
+        std::string what;
+        if (!o.structure_stats_file.empty() && o.mode != "fbapomdp")
+            what = "--structure-stats-file needs a factored Bayes-adaptive experiment (fbapomdp): only its particles carry a graph";
+        else if (o.structure_stats_queries.size() > FBA_STRUCT_STATS_MAX_QUERIES)
+            what = "--structure-stats-query: " + std::to_string(o.structure_stats_queries.size()) + " graphs where at most 16 are followed";
+        else if (o.structure_stats_file.empty() && !o.structure_stats_queries.empty())
+            what = "--structure-stats-query names a graph for --structure-stats-file, which is not given";
+        if (!what.empty()) {
+            std::fprintf(stderr, "ERROR: %s\n", what.c_str());
+            return 1;
+        }
+    }
     fba_ctx* ctx = nullptr;
     if (fba_create(&cfg, &ctx) != FBA_OK) {
         std::fprintf(stderr, "ERROR: %s\n", fba_last_error(nullptr));
@@ -424,6 +493,27 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "ERROR: %s\n", fba_last_error(ctx));
         fba_destroy(ctx);
         return 1;
+    }
+    if (!o.structure_stats_file.empty()) {
+        std::string what;
+        int32_t nw = 0, ns = 0;
+        fba_structure_lens(ctx, &nw, &ns);
+        std::vector<uint32_t> query;
+        for (const std::string& v : o.structure_stats_queries) {
+            const std::vector<uint32_t> w = query_words(v);
+            if (nw > 0 && (int)w.size() != nw) {
+                what = "--structure-stats-query " + v + ": " + std::to_string(w.size()) + " words where the model's particles carry " + std::to_string(nw);
+                break;
+            }
+            query.insert(query.end(), w.begin(), w.end());
+        }
+        if (what.empty() && fba_structure_stats_enable(ctx, 1, (int32_t)o.structure_stats_queries.size(), query.empty() ? nullptr : query.data()) != FBA_OK)
+            what = fba_last_error(ctx);
+        if (!what.empty()) {
+            std::fprintf(stderr, "ERROR: %s\n", what.c_str());
+            fba_destroy(ctx);
+            return 1;
+        }
     }
     if (!o.structure_out.empty()) {
         const char* what = nullptr;
@@ -529,6 +619,11 @@ int main(int argc, char** argv)
             fba_destroy(ctx);
             return 1;
         }
+    }
+    if (!o.structure_stats_file.empty() && !write_structure_stats(ctx, cfg, (int)o.structure_stats_queries.size(), o.structure_stats_file)) {
+        std::fprintf(stderr, "ERROR: the structure statistics could not be written to %s: %s\n", o.structure_stats_file.c_str(), fba_last_error(ctx));
+        fba_destroy(ctx);
+        return 1;
     }
     if (!o.structure_out.empty() && !write_structures(ctx, cfg.runs, o.structure_out)) {
         std::fprintf(stderr, "ERROR: the structures could not be written to %s: %s\n", o.structure_out.c_str(), fba_last_error(ctx));

@@ -96,6 +96,12 @@ class BeliefStructures:
         self.query_mass = query_mass                      # [slots][nq]
 
 
+class StructureStats(collections.namedtuple("StructureStats", "head set_frac query_frac query_held query_sole")):
+    """What Engine.structure_stats returns: the fba_structure_stat heads [episodes][horizon] and, with the same two leading axes, the
+    sums of set_mass / W [n_words][n_sets] and query_mass / W [nq] over the bin's steps and the steps that held / held only query q."""
+    __slots__ = ()
+
+
 class DeviceArray(collections.namedtuple("DeviceArray", "name elem_bytes elems slot_elems buffers")):
     """One entry of Engine.device_arrays()."""
     __slots__ = ()
@@ -260,6 +266,35 @@ class Engine:
         if n < 0:
             self._chk(n)
         return out
+
+    def structure_stats_enable(self, queries=None, on=True):
+        """Accumulate, for every real step run_bapomdp / run_bapomdp_span / run_ticks make from now on, the graph posterior of the
+        step's main filter into per-(episode, t) bins on the device (fba_structure_stats_enable): how many graphs the filter holds,
+        the mass per (word, parent set) and, for each of `queries` (uint32[nq][n_words] word lists as belief_get shows them, at most
+        N.STRUCT_STATS_MAX_QUERIES), its mass and whether the filter still holds it.  on=True allocates and clears the bins, on=False
+        frees them.  Read-only on everything else."""
+        nw, _ = self.structure_lens()
+        q = None if queries is None or not on else np.ascontiguousarray(queries, np.uint32).reshape(-1, max(nw, 1))
+        nq = 0 if q is None else q.shape[0]
+        self._chk(self.L.fba_structure_stats_enable(self.h, 1 if on else 0, nq, q.ctypes.data if nq else None))
+        self._structure_stats_nq = nq if on else 0
+
+    def structure_stats(self):
+        """The bins (fba_get_structure_stats): a StructureStats of `head` (N.STRUCTURE_STAT_DTYPE, shape (episodes, horizon)),
+        `set_frac` (episodes, horizon, n_words, n_sets), `query_frac`, `query_held` and `query_sole` (episodes, horizon, nq); raises
+        FbaError while the statistics are off."""
+        ep, hz = max(self.cfg.episodes, 1), self.cfg.horizon
+        nw, ns = self.structure_lens()
+        nq = getattr(self, "_structure_stats_nq", 0)
+        head = np.zeros((ep, hz), N.STRUCTURE_STAT_DTYPE)
+        sf = np.zeros((ep, hz, nw, ns), np.float64)
+        qf = np.zeros((ep, hz, nq), np.float64)
+        qh = np.zeros((ep, hz, nq), np.uint64)
+        qs = np.zeros((ep, hz, nq), np.uint64)
+        n = self.L.fba_get_structure_stats(self.h, head.size, head.ctypes.data, sf.ctypes.data, qf.ctypes.data, qh.ctypes.data, qs.ctypes.data)
+        if n < 0:
+            self._chk(n)
+        return StructureStats(head, sf, qf, qh, qs)
 
     def probe(self):
         """The probe's records as a structured array (N.PROBE_DTYPE) sorted by (run, episode, t), with `.seen`."""

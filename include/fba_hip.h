@@ -550,6 +550,50 @@ typedef struct fba_step_stat {              /* one per (episode, t); every membe
 } fba_step_stat;
 int fba_step_stats_enable(fba_ctx* ctx, int32_t on);   /* 1: allocate (episodes * horizon bins) and clear; 0: free */
 int fba_get_step_stats(fba_ctx* ctx, fba_step_stat* out, int32_t cap);   /* out[episodes][horizon]; returns episodes * horizon */
+/* The graph posterior per step of every run, reduced on the device inside the tick: episodes * horizon bins whatever the number of runs,
+ * where fba_belief_structures answers only for the filters as they stand between two calls and, after an experiment, for the last run
+ * of each slot.  Built like fba_step_stats; neither it nor the probe looks at a parent-set word.
+ * A STEP of a slot is a real step that fba_run_bapomdp, fba_run_bapomdp_span or fba_run_ticks takes, terminal steps included; with a
+ * search budget only the slots that take their step in a tick are accounted in it.  The step's FILTER is the main filter as it stands
+ * when the step is taken, before the belief update that may follow: the filter the step was planned from, the one fba_probe reads.  For
+ * that filter, in the notation of fba_belief_structures: W the weight total, set_mass[m][v] and query_mass[q] the unnormalised masses,
+ * `distinct` and `overflow` those of the FBA_STRUCT_TABLE table, and cnt[q] the number of particles, whatever their weight, whose whole
+ * word list equals query[q].  Bin (episode, t), the episode counted from 0 of the run as in fba_step_stats, accumulates over all steps of
+ * all runs the head below and, beside the heads, as arrays of their own because their lengths follow the model (fba_structure_lens) and nq:
+ *   set_frac  [bins][n_words][n_sets]  double    sum over the steps with finite W > 0 of set_mass[m][v] / W
+ *   query_frac[bins][nq]               double    sum over the same steps of query_mass[q] / W
+ *   query_held[bins][nq]               uint64_t  steps with cnt[q] > 0: the filter still holds graph q
+ *   query_sole[bins][nq]               uint64_t  steps with cnt[q] == particles: the filter holds nothing else
+ * fba_structure_stats_enable(on = 1, nq, query) allocates the bins, clears them and stores the queries (uint32[nq][n_words] word lists as
+ * fba_belief_get shows them, nq at most FBA_STRUCT_STATS_MAX_QUERIES); on = 0 frees them (nq and query are ignored).  A new fba_run_* does
+ * not clear the bins: runs, experiments and spans add up, as with fba_step_stats and the probe; a span fills only its own episodes.  The
+ * per-call interface writes nothing.  fba_get_structure_stats synchronises the stream; any of its pointers may be NULL; it returns
+ * episodes * horizon.
+ * Every context fba_belief_structures serves is served: every record format with parent-set words, flat and weighted filters, the main
+ * filter of the reinvigoration, cheating, incubator and both Metropolis-Hastings beliefs, either Dirichlet mode.  FBA_EINVAL for the
+ * nested belief, a model without parent-set words (with the message of fba_belief_structures), nq outside 0..16, query == NULL with
+ * nq > 0, a query word that is illegal for its node (the rule and message of fba_belief_structures) and cap_bins < episodes * horizon;
+ * FBA_ESTATE for fba_get_structure_stats while the statistics are off and for a record layout fba_belief_structures refuses with
+ * FBA_ESTATE.  A refused enable leaves the context as it was, its statistics off.
+ * Read-only on everything else: with the statistics on, every particle, trace record (belief_hash included), return, statistic, counter,
+ * probe record, fba_step_stats bin, fba_last_step_info and Philox position keeps its bits; with them off a tick launches exactly what
+ * it launched before.
+ * The integer members are exact.  The double members are OUTSIDE the parity contract: each term carries the bound of
+ * fba_belief_structures on its mass and on W (8 * particles * 2^-53 relative each) plus the one rounding of its division, and the sum
+ * over n steps adds n * 2^-53 relative; a member is exactly 0.0 where every term is.  In a flat filter every term is k / N: with N a power
+ * of two all terms and their sums are exact, and the bins repeat bit for bit. */
+#define FBA_STRUCT_STATS_MAX_QUERIES 16
+typedef struct fba_structure_stat {   /* one per (episode, t); 48 bytes, every member 8-byte aligned */
+    uint64_t steps;          /* steps taken at this (episode, t), over all runs                                        */
+    uint64_t weightless;     /* of them from a filter with W == 0 or not finite: they enter no fraction                */
+    uint64_t overflowed;     /* of them whose filter held more than FBA_STRUCT_TABLE distinct graphs                   */
+    uint64_t collapsed;      /* of them whose filter held exactly one graph (distinct == 1, overflow == 0)             */
+    uint64_t distinct_sum;   /* sum of `distinct` as fba_belief_structures reports it (a lower bound where overflowed) */
+    int32_t  distinct_max, reserved;
+} fba_structure_stat;
+int fba_structure_stats_enable(fba_ctx* ctx, int32_t on, int32_t nq, const uint32_t* query /* [nq][n_words]; NULL iff nq == 0 */);
+int fba_get_structure_stats(fba_ctx* ctx, int32_t cap_bins, fba_structure_stat* head, double* set_frac, double* query_frac,
+                            uint64_t* query_held, uint64_t* query_sole);   /* any pointer may be NULL; returns episodes * horizon */
 
 /* Belief snapshots: keeping, moving and copying the main filter of a slot in the record format the context stores (fba_particle_bytes) --
  * no count table is built anywhere, so a 16 384-particle gridworld filter is 3.0 MB, not the 3.1 GB fba_belief_get would hand out, and the
