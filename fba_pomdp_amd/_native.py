@@ -12,7 +12,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB_PATH = os.environ.get("FBA_LIB") or os.path.join(HERE, "libfba_hip.so")   # (FBA_LIB: an instrumented build of the same sources, scripts/search_regions.py)
-SOURCES = [os.path.join(HERE, "csrc", f) for f in ("fba_search.hip", "fba_kernels.hip", "fba_summary.hip", "fba_predict.hip", "fba_forecast.hip", "fba_probe.hip", "fba_step_stats.hip", "fba_structures.hip", "fba_structure_stats.hip", "fba_snapshot.hip", "fba_convert.hip", "fba_restore.hip", "fba_engine.hip")]
+SOURCES = [os.path.join(HERE, "csrc", f) for f in ("fba_search.hip", "fba_kernels.hip", "fba_summary.hip", "fba_predict.hip", "fba_forecast.hip", "fba_probe.hip", "fba_step_stats.hip", "fba_structures.hip", "fba_structure_stats.hip", "fba_snapshot.hip", "fba_convert.hip", "fba_restore.hip", "fba_retire.hip", "fba_engine.hip")]
 HEADERS = [os.path.join(HERE, "csrc", f) for f in ("fba_device.h", "fba_state.h", "fba_kernels.h", "fba_launch_plan.h", "fba_kernels_common.h", "fba_belief_factors.h", "fba_snapshot_format.h", "fba_structures.h", "fba_structures_table.h", "fba_search_hist2.inc")] + [
     os.path.join(ROOT, "include", "fba_hip.h")]
 OBJ_DIR = os.path.join(HERE, "build")   # per-source objects (git-ignored): a change to one translation unit recompiles that one
@@ -133,6 +133,15 @@ PROBE_DTYPE = np.dtype([
     ("evidence", "<f8"), ("next_true", "<f8"), ("post_true", "<f8"),
 ], align=True)
 
+# fba_retired_rec, and the arguments of fba_giveup_policy
+REJECT_QUANTUM, UPDATE_GAVE_UP = 1024, -2
+GIVEUP_STOP, GIVEUP_RETIRE = 0, 1
+GIVEUP_NAMES = {"stop": GIVEUP_STOP, "retire": GIVEUP_RETIRE}
+RETIRED_DTYPE = np.dtype([
+    ("run", "<i4"), ("episode", "<i4"), ("t", "<i4"), ("slot", "<i4"),
+    ("reason", "<i4"), ("counted", "<i4"), ("max_attempts", "<i4"), ("reserved", "<i4"),
+], align=True)
+
 # fba_step_stat: one bin (episode, t) of Engine.step_stats
 STEP_STAT_DTYPE = np.dtype([
     ("steps", "<u8"), ("terminals", "<u8"), ("action", "<u8", (MAX_ACTIONS,)), ("root_visits", "<u8", (MAX_ACTIONS,)),
@@ -173,7 +182,7 @@ EXPORTS = [
     "fba_domain_sizes", "fba_counts_len", "fba_slots", "fba_device_arrays", "fba_particle_bytes", "fba_set_model_tabular", "fba_set_model_factored", "fba_log_bd_score", "fba_selftest_lgamma", "fba_get_prior", "fba_get_factored_layout",
     "fba_set_position", "fba_belief_init", "fba_belief_reset_domain_state", "fba_select_action",
     "fba_belief_update", "fba_belief_get", "fba_belief_get_particle", "fba_belief_set", "fba_belief_get_fully_connected", "fba_belief_get_nested", "fba_belief_get_shadow", "fba_belief_summary", "fba_predict_lens", "fba_belief_predict", "fba_belief_forecast", "fba_structure_lens", "fba_belief_structures", "fba_last_step_info",
-    "fba_run_planning", "fba_run_bapomdp", "fba_run_ticks", "fba_get_returns", "fba_get_counters", "fba_get_return_sums",
+    "fba_run_planning", "fba_run_bapomdp", "fba_run_ticks", "fba_giveup_policy", "fba_retired_count", "fba_get_retired", "fba_get_returns", "fba_get_counters", "fba_get_return_sums",
     "fba_get_kernel_times", "fba_reset_kernel_times", "fba_trace_count", "fba_get_trace", "fba_get_trace_hist",
     "fba_probe_enable", "fba_probe_count", "fba_get_probe", "fba_step_stats_enable", "fba_get_step_stats", "fba_structure_stats_enable", "fba_get_structure_stats",
     "fba_belief_snapshot_bytes", "fba_belief_export", "fba_belief_import", "fba_belief_replicate", "fba_run_bapomdp_span",
@@ -300,6 +309,10 @@ def load():
         L.fba_probe_enable.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]   # first, count, capacity
         L.fba_probe_count.argtypes = [vp, P(C.c_int64)]
         L.fba_get_probe.argtypes = [vp, vp, C.c_int32]
+    if not os.environ.get("FBA_LIB") or hasattr(L, "fba_giveup_policy"):
+        L.fba_giveup_policy.argtypes = [vp, C.c_int32, C.c_int32]   # policy, max_attempts
+        L.fba_retired_count.argtypes = [vp, P(C.c_int64)]
+        L.fba_get_retired.argtypes = [vp, vp, C.c_int32]   # out: RETIRED_DTYPE[cap]
     if not os.environ.get("FBA_LIB") or hasattr(L, "fba_step_stats_enable"):
         L.fba_step_stats_enable.argtypes = [vp, C.c_int32]
         L.fba_get_step_stats.argtypes = [vp, vp, C.c_int32]   # out: STEP_STAT_DTYPE[episodes * horizon], cap

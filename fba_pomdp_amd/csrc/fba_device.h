@@ -350,6 +350,8 @@ struct Problem {
     uint32_t gw_goalcell0, gw_goalcell1, gw_goalcell2, gw_goalcell3;  // gridworld: x*N + y of goal g, 8 bits each, four goals per word (scalars, not an
                                                                       // array: an indexed member pins the whole by-value struct to scratch memory)
     int32_t search_budget;  // > 0: search_hist_kernel stops at the first simulation boundary behind this many loop iterations and parks the search (fba_hip.h)
+    int32_t reject_max = 1 << 28;   // attempts after which a rejection update gives up (REJECT_MAX_ATTEMPTS, fba_kernels.h, unless
+                                    // fba_giveup_policy set another): a positive multiple of FBA_REJECT_QUANTUM
     int32_t hist_row;   // the longest Dirichlet row of the model (max(N, G)): picks the row width the kernels are instantiated for
     const float* hist_base;  // the prior count table every particle starts from (max layout, x / y nodes without the goal parent)
     const float* hist_alt;   // [A][2][N*N*G*N]: the x / y transition nodes as a particle with the goal as their third parent starts them

@@ -91,6 +91,10 @@ struct fba_ctx {
     double struct_stats_ms = 0;          // diagnostic (FBA_STRUCT_STATS_TIME=1 in the environment, scripts/bench_structure_stats.py): the
     uint64_t struct_stats_launches = 0;  // kernels' own time by a HIP-event pair around the launches of a tick, and those ticks
     bool struct_stats_timed = false;
+    // fba_giveup_policy: the policy of the experiment loops (the limit itself is P.reject_max) and the list of retired runs, whose buffers
+    // are the context's (fba_giveup_policy allocates them; retired.recs is null in a context that never made the call)
+    int32_t giveup_policy = FBA_GIVEUP_STOP;
+    RetireArgs retired{};
 };
 
 namespace {
@@ -1117,6 +1121,7 @@ void materialize_records(fba_ctx* c, bool reset = false)
     else if (reset) launch_materialize_reset(c->P, c->D, c->stream);
     c->compact_dirty = false;
     c->D.compact_on  = 0;   // the per-call launches never leave a slot compact
+    c->D.retire_on   = 0;   // ... and never retire a run: a per-call update that gives up is an error of its call (check_fault)
 }
 
 // Belief::initiate of the slots that start a run: drawn from the prior, or -- in a resumed span -- taken from the snapshot store
@@ -1185,12 +1190,14 @@ int tick(fba_ctx* c)
     int rc;
     c->D.compact_on = c->compact_ok && c->probe.count == 0 ? 1 : 0;   // (the probe reads records)
     if (c->D.compact_on) c->compact_dirty = true;
+    c->D.retire_on = c->giveup_policy == FBA_GIVEUP_RETIRE && c->retired.recs ? 1 : 0;
     if ((rc = timed(c, FBA_K_SEARCH, [&] { launch_search(c->P, c->D, c->stream); }))) return rc;
     if ((rc = timed(c, FBA_K_ENV, [&] { launch_env(c->P, c->D, c->d_n_active, c->stream); }))) return rc;
     if (c->probe.count > 0) launch_belief_probe(c->P, c->D, c->probe, c->stream);   // (the slots env_kernel has just flagged for an update; in no time bucket)
     if (c->struct_stats.bins)
         if ((rc = launch_tick_structure_stats(c))) return rc;   // (adv, episode and t address the step; the filter has not seen it)
     if ((rc = timed(c, k_update_kind(c), [&] { launch_belief_update(c->P, c->D, c->stream); }))) return rc;
+    if (c->D.retire_on) launch_retire(c->P, c->D, c->retired, c->stream);   // (the slots whose update has just given up; in no time bucket)
     if (c->D.trace_on) launch_flush(c->P, c->D, c->stream);
     if (c->step_stats.bins)
         if ((rc = launch_tick_step_stats(c))) return rc;   // (update_count is written; t and episode still address the step)
@@ -1202,7 +1209,7 @@ int tick(fba_ctx* c)
     return FBA_OK;
 }
 
-// after a synchronisation point: did a rejection update give up (fba_kernels.h REJECT_MAX_ATTEMPTS)?
+// after a synchronisation point: did a rejection update give up (Problem::reject_max; under FBA_GIVEUP_RETIRE a tick raises no fault for that)?
 int check_fault(fba_ctx* c)
 {
     int32_t f = 0;
@@ -1220,8 +1227,10 @@ int check_fault(fba_ctx* c)
         return fail(c, FBA_ESTATE, "the search tree of slot %d outgrew its table of %d buckets (fba_config.tree_buckets; 0 = 2 * (sims + 2), which no search can fill)",
                     -f - 1, 2 * c->D.bkt_lines);
     if (f < 0) return fail(c, FBA_ESTATE, "the search tree of slot %d needed more than the %d node records it has", -f - 1, c->D.max_nodes);
+    HIPCHK(c, hipMemset(c->D.gave_up, 0, (size_t)c->P.E));   // (the flags of the slots that gave up go with the fault that reports them)
     return fail(c, FBA_ESTATE, "rejection sampling in slot %d accepted fewer than %d particles in %d attempts: no particle of the filter "
-                "can produce the observation (the reference loops forever in RejectionSampling.hpp:26-72 here)", f - 1, c->P.N, REJECT_MAX_ATTEMPTS);
+                "can produce the observation (the reference loops forever in RejectionSampling.hpp:26-72 here)", f - 1, c->P.N,
+                c->P.reject_max);
 }
 
 int set_flags(fba_ctx* c, uint8_t* dev, const uint8_t* mask, uint8_t value)
@@ -1280,6 +1289,7 @@ int start_experiment(fba_ctx* c, int runs_total, int first_episode = 0, int stop
     HIPCHK(c, hipMemcpyAsync(c->d_n_active, &n_active, sizeof n_active, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(c->D.bufsel, 0, (size_t)c->P.E, c->stream));
     HIPCHK(c, hipMemsetAsync(c->D.lazy_reset, 0, (size_t)c->P.E, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->D.gave_up, 0, (size_t)c->P.E, c->stream));
     if (c->D.bufsel_fc) HIPCHK(c, hipMemsetAsync(c->D.bufsel_fc, 0, (size_t)c->P.E, c->stream));
     if (c->D.bufsel_sh) HIPCHK(c, hipMemsetAsync(c->D.bufsel_sh, 0, (size_t)c->P.E, c->stream));
     launch_start(c->P, c->D, c->stream);
@@ -1297,6 +1307,7 @@ int run_experiment(fba_ctx* c, fba_stat* stats, int first = 0, int stop = -1, co
     int rc;
     const int runs = c->cfg.runs, E = c->P.E, eps = c->P.episodes;
     if (stop < 0) stop = eps;
+    const int retired0 = std::max(fba_retired_count(c, nullptr), 0);   // (the list is not cleared here: what it holds of earlier experiments)
     if ((rc = ensure_outputs(c, runs))) return rc;
     if ((rc = start_experiment(c, runs, first, stop))) return rc;
     long long max_ticks = (long long)((runs + E - 1) / E) * (stop - first) * c->P.horizon + 2;
@@ -1312,19 +1323,27 @@ int run_experiment(fba_ctx* c, fba_stat* stats, int first = 0, int stop = -1, co
     }
     std::vector<double> ret((size_t)runs * eps);
     HIPCHK(c, hipMemcpy(ret.data(), c->D.returns, ret.size() * sizeof(double), hipMemcpyDeviceToHost));
+    std::vector<int32_t> len((size_t)runs * eps);
+    HIPCHK(c, hipMemcpy(len.data(), c->D.lengths, len.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     std::memset(stats, 0, sizeof(fba_stat) * (size_t)eps);
     for (int r = 0; r < runs; ++r)
-        for (int ep = first; ep < stop; ++ep) fba_stat_add(&stats[ep], ret[(size_t)r * eps + ep]);
+        for (int ep = first; ep < stop; ++ep)
+            if (len[(size_t)r * eps + ep] > 0) fba_stat_add(&stats[ep], ret[(size_t)r * eps + ep]);   // (length 0: a void episode of a retired run, fba_giveup_policy)
     if (c->P.packed || c->P.ft_packed) {
         // what a snapshot header says of a slot's uint16 increments (fba_snapshot_head::updates): the filter a slot is left with is that of
-        // its last run, which has made one update per real step at most, on top of what its block had counted
-        std::vector<int32_t> len((size_t)runs * eps);
-        HIPCHK(c, hipMemcpy(len.data(), c->D.lengths, len.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        // its last run, which has made one update per real step at most, on top of what its block had counted.  The void episodes of a
+        // retired run count nothing (length 0) but the one it was retired in: t updates had succeeded before the step that gave up
         if (c->packed_updates.size() != (size_t)E) c->packed_updates.assign((size_t)E, 0);
+        const int gone1 = std::max(fba_retired_count(c, nullptr), retired0);   // the records [retired0, gone1) are this experiment's
+        std::vector<fba_retired_rec> gone((size_t)(gone1 - retired0));
+        if (!gone.empty())
+            HIPCHK(c, hipMemcpy(gone.data(), c->retired.recs + retired0, gone.size() * sizeof(fba_retired_rec), hipMemcpyDeviceToHost));
         for (int e = 0; e < E && e < runs; ++e) {
             const int r = e + E * ((runs - 1 - e) / E);
             uint32_t n = block_updates ? (*block_updates)[(size_t)r % block_updates->size()] : 0u;
             for (int ep = first; ep < stop; ++ep) n += (uint32_t)len[(size_t)r * eps + ep];
+            for (const fba_retired_rec& g : gone)
+                if (g.run == r + c->cfg.run_offset && !g.counted) n += (uint32_t)g.t;
             c->packed_updates[(size_t)e] = n;
         }
     }
@@ -1886,6 +1905,7 @@ int alloc_slot_state(fba_ctx* c)
                    ARR(upd_compact_full), ARR(upd_compact)));
     TRY(slot_alloc(c, ARR(ep_sums), 3));
     TRY(alloc_each(c, 1, 0, ARR(trace_count), "n_active", &c->d_n_active, ARR(fault)));
+    TRY(dev_alloc(c, ARR(gave_up), E, 1));
     D.trace_on   = c->cfg.trace ? 1 : 0;
     D.runs_total = c->cfg.runs;
     D.run_offset = c->cfg.run_offset;
@@ -3155,6 +3175,66 @@ int fba_get_probe(const fba_ctx* cc, fba_probe_rec* out, int32_t cap)
     return n;
 }
 
+// fba_giveup_policy: the limit goes into P.reject_max, which every rejection kernel tests; the policy and the list into the context, from
+// where tick() sets DeviceState::retire_on and launches retire_kernel (fba_retire.hip)
+int fba_giveup_policy(fba_ctx* c, int32_t policy, int32_t max_attempts)
+{
+    if (!c) return FBA_EINVAL;
+    if (policy != FBA_GIVEUP_STOP && policy != FBA_GIVEUP_RETIRE)
+        return fail(c, FBA_EINVAL, "fba_giveup_policy: policy %d (FBA_GIVEUP_STOP = 0, FBA_GIVEUP_RETIRE = 1)", policy);
+    if (max_attempts < 0 || max_attempts % FBA_REJECT_QUANTUM != 0)
+        return fail(c, FBA_EINVAL, "fba_giveup_policy: max_attempts %d is not a positive multiple of FBA_REJECT_QUANTUM (%d), nor 0 for the default of %d",
+                    max_attempts, FBA_REJECT_QUANTUM, REJECT_MAX_ATTEMPTS);
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // (nothing in flight writes the old list)
+    // max(runs, slots) records: a run is retired once.  (A context made for endless fba_run_ticks names 2^30 runs it never ends: beyond 2^22
+    // records, the trace's own limit, the list keeps room for the slots and counts the rest in `seen`)
+    const int32_t capacity = std::min(std::max(c->cfg.runs, c->P.E), std::max(c->P.E, 1 << 22));
+    if (!c->retired.recs) {
+        int rc;
+        RetireArgs a{};
+        if ((rc = dev_alloc(c, "retired", &a.recs, (size_t)capacity))) return rc;   // (in the report of fba_device_arrays from this call on)
+        if ((rc = dev_alloc(c, "retired_seen", &a.seen, 1))) return rc;
+        a.capacity = capacity;
+        c->retired = a;
+    } else {
+        HIPCHK(c, hipMemset(c->retired.recs, 0, (size_t)capacity * sizeof(fba_retired_rec)));
+        HIPCHK(c, hipMemset(c->retired.seen, 0, sizeof(unsigned long long)));
+    }
+    HIPCHK(c, hipMemset(c->D.gave_up, 0, (size_t)c->P.E));
+    c->giveup_policy = policy;
+    c->P.reject_max  = max_attempts ? max_attempts : REJECT_MAX_ATTEMPTS;
+    return FBA_OK;
+}
+
+int fba_retired_count(const fba_ctx* cc, int64_t* seen)
+{
+    fba_ctx* c = const_cast<fba_ctx*>(cc);
+    if (!c) return FBA_EINVAL;
+    if (seen) *seen = 0;
+    if (!c->retired.recs) return 0;
+    unsigned long long n = 0;
+    if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(&n, c->retired.seen, sizeof n, hipMemcpyDeviceToHost) != hipSuccess) return FBA_EHIP;
+    if (seen) *seen = (int64_t)n;
+    return (int)std::min<unsigned long long>(n, (unsigned long long)c->retired.capacity);
+}
+
+int fba_get_retired(const fba_ctx* cc, fba_retired_rec* out, int32_t cap)
+{
+    fba_ctx* c = const_cast<fba_ctx*>(cc);
+    if (!c || !out) return FBA_EINVAL;
+    const int stored = fba_retired_count(c, nullptr);
+    if (stored <= 0 || cap <= 0) return std::min(stored, 0);
+    // every stored record is sorted, then the first `cap` are handed over: the records of one launch are appended in no fixed order, so a
+    // short buffer gets the retirements of the lowest runs, not whichever were appended first.  By run; a run that stands in the list more
+    // than once (experiments repeated on one context) in the order of its retirements, which are launches apart
+    std::vector<fba_retired_rec> all((size_t)stored);
+    HIPCHK(c, hipMemcpy(all.data(), c->retired.recs, all.size() * sizeof(fba_retired_rec), hipMemcpyDeviceToHost));
+    std::stable_sort(all.begin(), all.end(), [](const fba_retired_rec& a, const fba_retired_rec& b) { return a.run < b.run; });
+    const int n = std::min(stored, cap);
+    std::memcpy(out, all.data(), (size_t)n * sizeof(fba_retired_rec));
+    return n;
+}
+
 // fba_step_stats: the bins go into c->step_stats and the per-slot scratch of env_kernel into D.step_scratch; tick() launches
 // step_stats_kernel (fba_step_stats.hip) while they are set
 int fba_step_stats_enable(fba_ctx* c, int32_t on)
@@ -4038,6 +4118,16 @@ int fba_debug_compact_slots(fba_ctx* c, int32_t* n)
     *n = 0;
     for (uint8_t v : h) *n += v != 0;
     return FBA_OK;
+}
+
+// diagnostic, not in include/fba_hip.h: the kernels launch_belief_update launches for this context, in order, as update_plan
+// (fba_launch_plan.h) names them -- what a test asks that wants to know which kernel its case runs.  Returns the number of steps
+int fba_debug_update_plan(fba_ctx* c, uint32_t* keys, int32_t cap)
+{
+    if (!c || (!keys && cap > 0)) return FBA_EINVAL;
+    const LaunchPlan pl = update_plan(c->P, c->D);
+    for (int i = 0; i < pl.n && i < cap; ++i) keys[i] = pl.step[i].kernel;
+    return pl.n;
 }
 
 int fba_reset_kernel_times(fba_ctx* c)

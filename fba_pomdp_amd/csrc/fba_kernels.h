@@ -14,7 +14,9 @@ constexpr int REJECT_BLOCK  = 256;   // attempts per chunk of the rejection filt
 // (which kernel a tick launch runs under these limits: search_plan / update_plan / reset_plan, fba_launch_plan.h)
 constexpr int TIGER_LDS_MAX_N = 4096;  // reject_tiger_lds_kernel: filters up to this many packed tiger particles are parked in LDS
 constexpr int TIGER_ONCE_MIN_N = 3584;  // reject_tiger_once_kernel from here up: 13 N + 8.3 KB of reject_tiger_lds_kernel no longer fit three times into a CU's 160 KB
-constexpr int REJECT_MAX_ATTEMPTS = 1 << 28;  // per update: beyond this the observation is taken to be impossible under the filter
+constexpr int REJECT_MAX_ATTEMPTS = 1 << 28;  // per update: beyond this the observation is taken to be impossible under the filter -- the default of
+                                              // Problem::reject_max, which is what the kernels test (fba_giveup_policy sets another)
+static_assert(REJECT_MAX_ATTEMPTS % FBA_REJECT_QUANTUM == 0, "the default limit is a multiple of the quantum, like every other");
 constexpr int IS_BLOCK      = 512;   // one workgroup per slot in the importance filter (same-box A/B on the bench shape: 1024 -> 37.3 ms, 512 -> 31.1, 256 -> 32.3: three workgroups per CU overlap their barrier-separated phases)
 constexpr int PARTICLE_TILE = 4096;  // particles one workgroup initialises / resets
 constexpr int CARRY_TILE    = 2048;  // chunk totals staged in LDS per step of the carry chain
@@ -152,6 +154,15 @@ constexpr int STEP_STATS_ROW_TAIL = 17;  // words of fba_step_stat behind root_v
 __host__ __device__ inline int step_stats_row_words(int A) { return 2 + 2 * (A < FBA_MAX_ACTIONS ? A : FBA_MAX_ACTIONS) + STEP_STATS_ROW_TAIL; }
 inline int step_stats_rows(int n_bins, int A) { const int fit = STEP_STATS_LDS / (step_stats_row_words(A) * 8); return n_bins < fit ? n_bins : fit; }
 void launch_step_stats(const Problem& P, const DeviceState& D, const StepStatsArgs& a, hipStream_t st);
+// fba_giveup_policy, FBA_GIVEUP_RETIRE (fba_retire.hip): inside a tick, between the belief update and flush_kernel -- the slots whose
+// rejection update has just given up (DeviceState::gave_up) are reported and their runs ended.  The list is the context's
+// (fba_giveup_policy allocates and clears it); everything else the kernel touches is the slot's own state in DeviceState
+struct RetireArgs {
+    fba_retired_rec* recs;      // [capacity]
+    unsigned long long* seen;   // [1] retirements since fba_giveup_policy
+    int32_t capacity;
+};
+void launch_retire(const Problem& P, const DeviceState& D, const RetireArgs& a, hipStream_t st);
 // fba_belief_structures (fba_structures.hip): the parent-set word lists of slots [first, first + count) reduced into device buffers of the
 // caller's; a null output = not wanted (head is always).  The caller zeroes query_mass where nq > STRUCT_QUERY_LDS
 constexpr int STRUCT_TABLE      = FBA_STRUCT_TABLE;   // entries of a slot's table of distinct structures (open addressing, in LDS)

@@ -113,8 +113,8 @@ __global__ void advance_kernel(Problem P, DeviceState D, int32_t* n_active)
     const int adv = D.adv[e];
     D.adv[e]      = 0;
     if (adv == 1) { D.t[e] += 1; return; }
-    if (adv != 2) return;
-    int run = D.run[e], ep = D.episode[e] + 1;
+    if (adv != 2 && adv != 3) return;
+    int run = D.run[e], ep = adv == 3 ? D.stop_episode : D.episode[e] + 1;   // (3: retire_kernel has ended the run, fba_retire.hip)
     if (ep < D.stop_episode) {
         D.episode[e]    = ep;
         D.need_reset[e] = P.model != FBA_MODEL_POMDP;
@@ -366,9 +366,25 @@ __device__ __forceinline__ int record_group(int C4)
 // per CU changes nothing -- the kernel is bound by the memory system's rate for random 128-byte lines.
 // `fc` = 1 runs the update on the reinvigoration belief's fully connected filter (launched before
 // the main filter's update, which is the one that clears the request flag).
+// A rejection update gives up where a round would start at Problem::reject_max attempts with fewer than N of them accepted: the limit is a
+// multiple of FBA_REJECT_QUANTUM and every kernel's round divides that, so the rule is "the N-th acceptance is not among the first
+// reject_max attempts" exactly.  One thread per slot: the slot is flagged (DeviceState::gave_up) and its request cleared, so whatever
+// follows in the plan leaves the slot alone.  Then either the context is stopped -- the first such slot in D.fault, the slot parked -- or,
+// in a tick under FBA_GIVEUP_RETIRE, nothing more: retire_kernel (fba_retire.hip) finds the flag and the slot stays active for advance_kernel
+__device__ __forceinline__ void reject_give_up(const DeviceState& D, int e)
+{
+    D.gave_up[e]     = 1;
+    D.need_update[e] = 0;
+    if (D.retire_on) return;
+    atomicCAS(D.fault, 0, 1 + e);
+    D.active[e] = 0;
+}
+#define FBA_REJECT_ROUND(BLK) static_assert(FBA_REJECT_QUANTUM % (BLK) == 0, "a round of attempts divides FBA_REJECT_QUANTUM: the limit is tested where a round starts")
+
 template <bool REG, int TIGER_TABLE, int FTIGER = 0, int BLK = REJECT_BLOCK, bool FTP = false>
 __global__ void __launch_bounds__(BLK) reject_kernel(Problem P, DeviceState D, int fc)
 {
+    FBA_REJECT_ROUND(BLK);
     if (FTIGER > 0) {  // factored tiger with FTIGER binary state features (see search_kernel)
         P.model = FBA_MODEL_BA_FACTORED;
         P.S = 1 << FTIGER; P.A = 3; P.O = 2;
@@ -406,14 +422,10 @@ __global__ void __launch_bounds__(BLK) reject_kernel(Problem P, DeviceState D, i
 
     int acc = 0, base = 0;
     while (acc < N) {
-        if (base >= REJECT_MAX_ATTEMPTS) {
+        if (base >= P.reject_max) {
             // The reference would spin forever here (no particle can produce the observation); a GPU must
-            // not.  Park the slot and tell the host, which turns it into an error.
-            if (tid == 0) {
-                atomicCAS(D.fault, 0, 1 + e);
-                D.need_update[e] = 0;
-                D.active[e]      = 0;
-            }
+            // not.  Park the slot and tell the host, which turns it into an error -- or retire the slot's run (reject_give_up).
+            if (tid == 0) reject_give_up(D, e);
             return;
         }
         const int k = base + tid;
@@ -479,6 +491,7 @@ template <int K>
 __global__ void __launch_bounds__(REJECT_BLOCK) reject_hist_kernel(Problem P, DeviceState D)
 {
     constexpr int BLK = REJECT_BLOCK;
+    FBA_REJECT_ROUND(BLK);
     extern __shared__ uint4 s_prior_rows[];   // K > 0: one byte per row slot (HistRowIds numbering), then the distinct rows
     __shared__ int32_t s_src[BLK];
     __shared__ __attribute__((aligned(8))) int32_t s_side[2 * BLK];   // accepted attempt j of the chunk: {s', the step's entry}
@@ -513,12 +526,8 @@ __global__ void __launch_bounds__(REJECT_BLOCK) reject_hist_kernel(Problem P, De
 
     int acc = 0, base = 0;
     while (acc < N) {
-        if (base >= REJECT_MAX_ATTEMPTS) {   // (as reject_kernel: park the slot, the host reports "accepted fewer than")
-            if (tid == 0) {
-                atomicCAS(D.fault, 0, 1 + e);
-                D.need_update[e] = 0;
-                D.active[e]      = 0;
-            }
+        if (base >= P.reject_max) {   // (as reject_kernel: park the slot, the host reports "accepted fewer than", or retire its run)
+            if (tid == 0) reject_give_up(D, e);
             return;
         }
         const int k = base + tid;
@@ -581,6 +590,7 @@ __global__ void __launch_bounds__(REJECT_BLOCK) reject_hist_kernel(Problem P, De
 __global__ void __launch_bounds__(REJECT_BLOCK) reject_tab_hist_kernel(Problem P, DeviceState D)
 {
     constexpr int BLK = REJECT_BLOCK;
+    FBA_REJECT_ROUND(BLK);
     __shared__ int32_t s_src[BLK];
     __shared__ __attribute__((aligned(8))) int32_t s_side[2 * BLK];   // accepted attempt j of the chunk: {s', the step's entry}
     __shared__ int32_t s_wave[BLK / 64];
@@ -609,12 +619,8 @@ __global__ void __launch_bounds__(REJECT_BLOCK) reject_tab_hist_kernel(Problem P
 
     int acc = 0, base = 0;
     while (acc < N) {
-        if (base >= REJECT_MAX_ATTEMPTS) {   // (as reject_kernel: park the slot, the host reports "accepted fewer than")
-            if (tid == 0) {
-                atomicCAS(D.fault, 0, 1 + e);
-                D.need_update[e] = 0;
-                D.active[e]      = 0;
-            }
+        if (base >= P.reject_max) {   // (as reject_kernel: park the slot, the host reports "accepted fewer than", or retire its run)
+            if (tid == 0) reject_give_up(D, e);
             return;
         }
         const int k = base + tid;
@@ -703,6 +709,7 @@ __device__ unsigned long long g_reject_prof[4];
 template <int BLK>
 __global__ void __launch_bounds__(BLK) reject_tiger_lds_kernel(Problem P, DeviceState D)
 {
+    FBA_REJECT_ROUND(BLK);
     P.model = FBA_MODEL_BA_TABLE;
     P.S = 2; P.A = 3; P.O = 2; P.phi_len = 12; P.C = 12; P.Cs = 16;
     if (P.domain != FBA_DOM_TIGER_CONTINUOUS) P.domain = FBA_DOM_TIGER_EPISODIC;
@@ -736,12 +743,8 @@ __global__ void __launch_bounds__(BLK) reject_tiger_lds_kernel(Problem P, Device
     REJECT_PROF_MARK(0)
     int acc = 0, base = 0;
     while (acc < N) {
-        if (base >= REJECT_MAX_ATTEMPTS) {  // see reject_kernel
-            if (tid == 0) {
-                atomicCAS(D.fault, 0, 1 + e);
-                D.need_update[e] = 0;
-                D.active[e]      = 0;
-            }
+        if (base >= P.reject_max) {  // see reject_kernel
+            if (tid == 0) reject_give_up(D, e);
             return;
         }
         const int k = base + tid;
@@ -824,7 +827,7 @@ __global__ void __launch_bounds__(BLK) reject_tiger_lds_kernel(Problem P, Device
 // the stores of a round drain under the next round's draws (a round has one barrier, which waits for LDS only; s_wave has a half per
 // parity of the round so that the second one could go).  Otherwise (the continuous tiger after an `open`) the accepted attempts are
 // listed and the listed sources gathered behind the loop, as above.
-// A slot that gives up at REJECT_MAX_ATTEMPTS has by then written part of its OTHER buffer: harmless, bufsel is not flipped, the filter
+// A slot that gives up at Problem::reject_max has by then written part of its OTHER buffer: harmless, bufsel is not flipped, the filter
 // it holds is untouched and the next update overwrites that buffer.
 // The same holds for the compact flag (DeviceState::compact), which is written beside bufsel and nowhere else in here.
 // Compact filters (fba_state.h; D.compact_on, the experiment loop's launches only): on that clean path, after a `listen`, the record the
@@ -837,6 +840,7 @@ __global__ void __launch_bounds__(BLK) reject_tiger_lds_kernel(Problem P, Device
 template <int BLK, bool GATHER>
 __device__ __forceinline__ void reject_tiger_once_body(Problem P, const DeviceState& D)
 {
+    FBA_REJECT_ROUND(BLK);
     P.model = FBA_MODEL_BA_TABLE;
     P.S = 2; P.A = 3; P.O = 2; P.phi_len = 12; P.C = 12; P.Cs = 16;
     if (P.domain != FBA_DOM_TIGER_CONTINUOUS) P.domain = FBA_DOM_TIGER_EPISODIC;
@@ -919,12 +923,8 @@ __device__ __forceinline__ void reject_tiger_once_body(Problem P, const DeviceSt
     const uint32_t add_o = o ? 0x10000u : 1u;
     int acc = 0, base = 0, half = 0;
     while (acc < N) {
-        if (base >= REJECT_MAX_ATTEMPTS) {  // see reject_kernel (records of earlier rounds are in the other buffer by now; the slot's filter is as it was)
-            if (tid == 0) {
-                atomicCAS(D.fault, 0, 1 + e);
-                D.need_update[e] = 0;
-                D.active[e]      = 0;
-            }
+        if (base >= P.reject_max) {  // see reject_kernel (records of earlier rounds are in the other buffer by now; the slot's filter is as it was)
+            if (tid == 0) reject_give_up(D, e);
             return;
         }
         const int k = base + tid;

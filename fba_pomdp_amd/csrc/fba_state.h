@@ -46,7 +46,11 @@ struct DeviceState {
     uint8_t* need_update;  // [E] belief update pending (last env step was not terminal)
     uint8_t* need_reset;   // [E] resetDomainStateDistribution pending (new episode)
     uint8_t* need_init;    // [E] Belief::initiate pending (new run)
-    uint8_t* adv;          // [E] set by env_kernel: 1 = next time-step, 2 = episode ended
+    uint8_t* gave_up;      // [E] the slot's rejection update of this launch gave up at Problem::reject_max (reject_give_up, fba_kernels.hip);
+                           //     retire_kernel consumes the flag, the host clears the array in front of an experiment and with the fault it reports
+    int8_t retire_on;      // this launch retires the run of a slot that gives up instead of stopping the context (set by tick() under
+                           //     FBA_GIVEUP_RETIRE; 0 in every per-call launch)
+    uint8_t* adv;          // [E] set by env_kernel: 1 = next time-step, 2 = episode ended; 3 = run ended (retire_kernel, fba_retire.hip)
     int32_t* env_state; // [E] true environment state
     double* ret;        // [E] discounted return so far
     double* disc;       // [E] accumulated discount
@@ -70,7 +74,7 @@ struct DeviceState {
     int8_t compact_on;  // this launch may leave slots compact (set by tick() in a context that fba_create found eligible; 0 in every per-call launch)
     unsigned long long* upd_compact_full;  // [E] particles written compact from 64-byte sources
     unsigned long long* upd_compact;       // [E] particles written compact from compact sources
-    int32_t* fault;     // [1] 0, or 1 + the slot whose rejection update exceeded REJECT_MAX_ATTEMPTS (host reports it)
+    int32_t* fault;     // [1] 0, or 1 + the first slot whose rejection update exceeded Problem::reject_max (host reports it; not under retire_on)
     uint8_t* cheat_pending;  // [E] the update of this tick pushed log(likelihood) below the threshold (mh-within-gibbs: an update has run, mh_kernel has work)
     // mh-within-gibbs belief: the run's (action, observation) history by episode; lik[e] is the log likelihood, lik[E] the threshold
     int16_t* mh_a;      // [E][episodes * horizon]

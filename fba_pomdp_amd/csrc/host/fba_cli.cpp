@@ -35,10 +35,10 @@ namespace {
 struct Options {
     std::string mode;
     std::string domain, planner = "po-uct", belief = "rejection_sampling", seed, output_file = "results.txt", structure_prior,
-                                dirichlet = "expected", id, belief_option, probe_file, probe_slots, step_stats_file, belief_in, belief_out, structure_out, structure_stats_file;
+                                dirichlet = "expected", id, belief_option, probe_file, probe_slots, step_stats_file, belief_in, belief_out, structure_out, structure_stats_file, on_giveup, retired_file;
     std::vector<std::string> structure_stats_queries;   // --structure-stats-query, as given
     int verbose = 0, runs = 1, horizon = 10, sims = 1000, max_depth = -1, particles = 100, size = 0, height = 0, width = 0,
-        episodes = 1, slots = 0, device = 0, resample_amount = 0, first_episode = 0, stop_episode = -1;
+        episodes = 1, slots = 0, device = 0, resample_amount = 0, first_episode = 0, stop_episode = -1, reject_attempts = 0;
     double discount = .95, exploration = 100, threshold = 0;
     float noise = 0, counts_total = 10000;
     bool help = false, belief_fit = false;
@@ -86,6 +86,10 @@ void usage()
         "                                 episode t steps terminals, the steps by action, reward_sum reward_sq_sum value_sum nodes_sum depth_sum\n"
         "                                 attempts_steps attempts_sum, and -- fed by --probe-file's probe, else 0 -- probed evidence_zero\n"
         "                                 evidence_sum log_evidence_sum log_evidence_sq_sum next_true_sum post_ratio_sum (fba_step_stats)\n"
+        "      --on-giveup stop|retire    a run whose rejection update gives up: stop fails the experiment (default); retire takes the run out,\n"
+        "                                 voids its unfinished episodes and lets the slot go on with its next run (fba_giveup_policy)\n"
+        "      --reject-attempts N        attempts after which a rejection update gives up: a multiple of 1024 (0: 2^28)\n"
+        "      --retired-file FILE        one line per retired run: run episode t slot reason counted max_attempts\n"
         "      --first-episode K          (bapomdp, fbapomdp) run episodes [K, M) of every run only (0, --episodes): the result file\n"
         "      --stop-episode M           has one line per episode of the span\n"
         "      --belief-in FILE           the filters the runs continue from at episode K: one snapshot block for every run, or one\n"
@@ -156,6 +160,12 @@ bool parse(int argc, char** argv, Options& o, std::string& err)
             else if (k == "--device") o.device = std::stoi(v);
             else if (k == "--probe-file") o.probe_file = v;
             else if (k == "--step-stats-file") o.step_stats_file = v;
+            else if (k == "--on-giveup") {
+                if (v != "stop" && v != "retire") throw std::invalid_argument(v);
+                o.on_giveup = v;
+            }
+            else if (k == "--reject-attempts") o.reject_attempts = std::stoi(v);
+            else if (k == "--retired-file") o.retired_file = v;
             else if (k == "--first-episode") o.first_episode = std::stoi(v);
             else if (k == "--stop-episode") o.stop_episode = std::stoi(v);
             else if (k == "--belief-in") o.belief_in = v;
@@ -270,6 +280,25 @@ bool write_probe(fba_ctx* ctx, const std::string& path)
         std::fprintf(f, "%d %d %d %d %d %d %.17g %.17g %.17g\n", r.run, r.episode, r.t, r.action, r.obs, r.state, r.evidence, r.next_true, r.post_true);
     }
     if (seen > got) std::fprintf(f, "# %lld steps were probed, %d records were kept\n", (long long)seen, got);
+    return std::fclose(f) == 0;
+}
+
+// --retired-file: the runs retired under --on-giveup retire, by run; a leading comment line names the columns
+bool write_retired(fba_ctx* ctx, const std::string& path, int& got)
+{
+    const int n = fba_retired_count(ctx, nullptr);
+    if (n < 0) return false;
+    std::vector<fba_retired_rec> rr((size_t)std::max(n, 1));
+    got = n ? fba_get_retired(ctx, rr.data(), n) : 0;
+    if (got < 0) return false;
+    if (path.empty()) return true;
+    FILE* f = std::fopen(path.c_str(), "w");
+    if (!f) return false;
+    std::fprintf(f, "# run episode t slot reason counted max_attempts\n");
+    for (int i = 0; i < got; ++i) {
+        const fba_retired_rec& r = rr[(size_t)i];
+        std::fprintf(f, "%d %d %d %d %d %d %d\n", r.run, r.episode, r.t, r.slot, r.reason, r.counted, r.max_attempts);
+    }
     return std::fclose(f) == 0;
 }
 
@@ -489,6 +518,12 @@ int main(int argc, char** argv)
             return 1;
         }
     }
+    const bool giveup = !o.on_giveup.empty() || o.reject_attempts != 0 || !o.retired_file.empty();
+    if (giveup && fba_giveup_policy(ctx, o.on_giveup == "retire" ? FBA_GIVEUP_RETIRE : FBA_GIVEUP_STOP, o.reject_attempts) != FBA_OK) {
+        std::fprintf(stderr, "ERROR: %s\n", fba_last_error(ctx));
+        fba_destroy(ctx);
+        return 1;
+    }
     if (!o.step_stats_file.empty() && fba_step_stats_enable(ctx, 1) != FBA_OK) {
         std::fprintf(stderr, "ERROR: %s\n", fba_last_error(ctx));
         fba_destroy(ctx);
@@ -596,6 +631,17 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "ERROR: the probe's records could not be written to %s: %s\n", o.probe_file.c_str(), fba_last_error(ctx));
         fba_destroy(ctx);
         return 1;
+    }
+    if (giveup) {
+        int retired = 0;
+        if (!write_retired(ctx, o.retired_file, retired)) {
+            std::fprintf(stderr, "ERROR: the retired runs could not be written to %s: %s\n", o.retired_file.c_str(), fba_last_error(ctx));
+            fba_destroy(ctx);
+            return 1;
+        }
+        if (o.on_giveup == "retire")
+            std::fprintf(stderr, "NOTICE: (%s): %d of %d runs were retired: their rejection updates gave up; the statistics are over the others\n", o.id.c_str(),
+                         retired, cfg.runs);
     }
     if (!o.step_stats_file.empty()) {
         int32_t S, A, O;

@@ -63,6 +63,12 @@ class ProbeRecords(np.ndarray):
     seen = 0
 
 
+class RetiredRecords(np.ndarray):
+    """What Engine.retired returns: the fba_retired_rec records stored, ordered by run; `.seen` counts every retirement since
+    Engine.giveup_policy, so seen > len(records) says the list was too small (endless run_ticks only)."""
+    seen = 0
+
+
 class BeliefSummary:
     """What Engine.belief_summary returns: numpy arrays with one row per slot of the range (None where not asked for)."""
 
@@ -308,6 +314,26 @@ class Engine:
             self._chk(n)
         out = out[:n]
         out = out[np.lexsort((out["t"], out["episode"], out["run"]))].view(ProbeRecords)
+        out.seen = seen.value
+        return out
+
+    def giveup_policy(self, policy="stop", max_attempts=0):
+        """What becomes of a run whose rejection update gives up (fba_giveup_policy): "stop" fails the whole experiment, as ever; "retire"
+        takes that run out, reports it in retired() and lets the slot go on with its next run.  `max_attempts` is the limit after which an
+        update gives up, a positive multiple of N.REJECT_QUANTUM (0: 2^28); it holds for belief_update too.  Clears the list."""
+        self._chk(self.L.fba_giveup_policy(self.h, _enum(policy, N.GIVEUP_NAMES, "giveup policy"), max_attempts))
+
+    def retired(self):
+        """The runs retired since giveup_policy as a structured array (N.RETIRED_DTYPE) ordered by run, with `.seen` as probe() has it."""
+        seen = C.c_int64()
+        n = self.L.fba_retired_count(self.h, C.byref(seen))
+        if n < 0:
+            self._chk(n)
+        out = np.zeros(max(n, 1), N.RETIRED_DTYPE)
+        n = self.L.fba_get_retired(self.h, out.ctypes.data, len(out)) if n else 0
+        if n < 0:
+            self._chk(n)
+        out = out[:n].view(RetiredRecords)
         out.seen = seen.value
         return out
 

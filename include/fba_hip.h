@@ -147,13 +147,14 @@ typedef struct fba_trace_rec {
     int32_t action, state, obs;
     int32_t terminal;
     int32_t n_nodes, tree_depth;
-    int32_t update_count;
+    int32_t update_count;    /* attempts of the step's rejection update; -1: none (terminal step); FBA_UPDATE_GAVE_UP: see fba_giveup_policy */
     int32_t root_n[FBA_MAX_ACTIONS];
     double root_q[FBA_MAX_ACTIONS];
     double reward;
     double weight_total;
     uint64_t belief_hash;
 } fba_trace_rec;
+#define FBA_UPDATE_GAVE_UP (-2)   /* fba_trace_rec.update_count of the step at which a run was retired (fba_giveup_policy) */
 
 /* utils::Statistic (src/utils/Statistic.cpp:5-46) */
 typedef struct fba_stat {
@@ -218,7 +219,7 @@ int fba_particle_bytes(const fba_ctx* ctx); /* HBM bytes of one particle record.
 int fba_slots(const fba_ctx* ctx);      /* slots actually resident (cfg.slots, or the library's choice) */
 
 /* The device arrays the context holds for its slots, filters, composite beliefs, search trees and -- once an experiment has been
- * started -- its per-run returns and trace, in allocation order: what a context of this configuration takes in HBM (the sum of
+ * started -- its per-run returns and trace, and from fba_giveup_policy on the list of retired runs ("retired"), in allocation order: what a context of this configuration takes in HBM (the sum of
  * elems * elem_bytes; the prior's tables and the probe, a few kilobytes to megabytes, are not listed) and where one slot's part of an
  * array stands.  A per-slot array is `buffers` buffers of fba_slots slots of slot_elems
  * elements each: the part of slot e in buffer b starts at element (b * fba_slots + e) * slot_elems.  History records keep one buffer
@@ -459,6 +460,54 @@ int fba_run_bapomdp(fba_ctx* ctx, fba_stat* stats);
 /* throughput driver used by bench.py: advance every slot by `ticks` real time-steps
  * (search + env step + belief update), restarting episodes/runs as they finish. */
 int fba_run_ticks(fba_ctx* ctx, int32_t ticks);
+
+/* What becomes of a run whose rejection update gives up.  The reference's rejectSample (RejectionSampling.hpp:26-72) loops until it has
+ * accepted `particles` attempts; the engine cannot loop forever, so an update GIVES UP iff its particles-th acceptance is not among its
+ * first max_attempts attempts, i.e. iff its update_count would exceed max_attempts.  That holds exactly for every rejection kernel -- the
+ * plain, fully connected, packed tiger (LDS / once / compact), packed factored-tiger and history-record ones: they test the limit where a
+ * round of attempts starts, every round size divides FBA_REJECT_QUANTUM, and max_attempts must be a positive multiple of it (0: 2^28, the
+ * limit of a context that never made this call); anything else is FBA_EINVAL and leaves policy and limit as they were.  The limit also
+ * holds for fba_belief_update, which otherwise behaves as ever: it returns FBA_ESTATE with a message that names the slot and the limit in
+ * force, and the context stays usable.  (The nested belief counts its own attempts and the Metropolis-Hastings beliefs have limits of
+ * their own: neither is touched.)
+ *   FBA_GIVEUP_STOP    (default) the first such slot stops the whole fba_run_* with FBA_ESTATE, as that message says.
+ *   FBA_GIVEUP_RETIRE  in fba_run_planning, fba_run_bapomdp, fba_run_bapomdp_span and fba_run_ticks a slot whose update gives up, in any of
+ *                      its rejection filters (the main one, or the fully connected / correct-graph filter of the reinvigoration,
+ *                      incubator and cheating beliefs), RETIRES its run.  Runs never couple -- their streams are addressed by run -- so
+ *                      nothing else changes by a bit:
+ *     - the real step has been taken and is accounted like any other (trace record, fba_step_stats, fba_structure_stats, probe); its
+ *       trace record carries update_count = FBA_UPDATE_GAVE_UP, and its weight_total and belief_hash are unspecified;
+ *     - if that step was the last of the horizon its episode's return is recorded and stays counted (counted = 1); else the episode is
+ *       void, and so is every later episode of the run.  A void episode has lengths == 0 and returns == 0.0 in fba_get_returns and enters
+ *       neither the per-episode statistics, whose `count` drops, nor fba_get_return_sums;
+ *     - a given-up update adds nothing to fba_counters.belief_steps, as under STOP;
+ *     - the slot goes on with its next run (run + slots) exactly as behind a run's last episode, or becomes inactive if there is none;
+ *     - one fba_retired_rec is appended to the list.
+ *     Every run that is not retired keeps every bit it has under STOP: trace records, returns, lengths, its contributions to counters,
+ *     probe records and statistics bins, Philox positions, final filter.  A retired run keeps every bit up to and including the step that
+ *     gave up, but for the three record members named above.  The filter a retired run leaves in a slot whose last run it was is
+ *     unspecified in content but valid: fba_belief_export / fba_belief_import take it, fba_belief_init and every later call work.
+ *     Retiring conditions every statistic on survival; the list is there so that the caller can judge what was taken out.
+ * The list has room for max(runs, slots) records (at most max(slots, 2^22), the trace's own limit: only a context made for endless
+ * fba_run_ticks names more runs than that); this call allocates and clears it (under either policy), a new fba_run_* does not, as
+ * with the probe.  fba_retired_count returns the records stored and *seen (may be NULL) every retirement since this call: seen > stored
+ * can happen only under endless fba_run_ticks.  fba_get_retired copies up to `cap` of them ordered by run.  Retirement is per call: a later
+ * span (fba_run_bapomdp_span) starts every run it is given, so dropping retired runs between spans is the caller's job, from this list.
+ * The other faults keep stopping the context under either policy: search-tree tables, the room of history records, and a Metropolis-
+ * Hastings belief that cannot reproduce the run's history.  With FBA_GIVEUP_STOP and max_attempts = 0 a tick launches exactly what it
+ * launched before this call existed. */
+#define FBA_REJECT_QUANTUM 1024            /* max_attempts is a multiple of this; every rejection kernel's round of attempts divides it */
+enum { FBA_GIVEUP_STOP = 0, FBA_GIVEUP_RETIRE = 1 };
+int fba_giveup_policy(fba_ctx* ctx, int32_t policy, int32_t max_attempts /* 0 = 2^28, today's limit */);
+#define FBA_RETIRED_REJECTION 1
+typedef struct fba_retired_rec {           /* 32 bytes */
+    int32_t run, episode, t, slot;         /* the real step whose belief update gave up, addressed as in fba_trace_rec */
+    int32_t reason;                        /* FBA_RETIRED_REJECTION (1): rejection sampling accepted fewer than `particles` in max_attempts attempts */
+    int32_t counted;                       /* 1: the episode had already ended with this step and its return is counted; 0: the episode is void */
+    int32_t max_attempts, reserved;
+} fba_retired_rec;
+int fba_retired_count(const fba_ctx* ctx, int64_t* seen);   /* records stored; *seen (may be NULL) every retirement, as fba_probe_count */
+int fba_get_retired(const fba_ctx* ctx, fba_retired_rec* out, int32_t cap);   /* ordered by (run) */
 
 /* per-(run, episode) discounted returns of the last fba_run_*: returns[runs * episodes] */
 int fba_get_returns(const fba_ctx* ctx, double* returns, int32_t* lengths);
